@@ -23,10 +23,22 @@ STRONG scaling by default (the same 1024 seeds sharded); the weak figure (1024 s
 
 Timing.  `--prewarm-ms` of untimed launches, W untimed warm-up steps, then exactly K steps: barrier + synchronize, clock, the K
 steps (+ the exchange of a partly filled bucket), this rank's synchronize, clock; maximum over ranks.  The group's CLOSING barrier
-follows the clock (recorded in config.timed_region.closing_barrier_us).  The region is measured `--repeats` times; the MEDIAN is
-reported (a region under 0.4 ms `--short-region-repeats` more times).  The headline is what a FRESH ShardedRefiner does by default --
-the streams it created, no selection among stream pairs; for short N > 1 regions the figure with `calibrate_streams()` (a
-best-of-30 pick of the stream pair, r4's headline) is the secondary key `ms_per_step_calibrated_streams`.
+follows the clock (recorded in config.timed_region.closing_barrier_us).  The region is measured `--repeats` times (default: once;
+five times with --full); the MEDIAN is reported (with --full a region under 0.4 ms `--short-region-repeats` more times).  The
+headline is what a FRESH ShardedRefiner does by default -- the streams it created, no selection among stream pairs; for short N > 1
+regions --full adds the figure with `calibrate_streams()` (a best-of-30 pick of the stream pair, r4's headline) as the secondary key
+`ms_per_step_calibrated_streams`.
+
+Plain run vs --full.  Without --full the run does only what the headline needs: set up, warm up, time the K steps, write the outputs
+(--dump-outputs), print the line.  --full adds everything else the line can carry: the roofline (isolated kernel time, committed
+counters), host enqueue cost, stream calibration, all-gather latency, the selection check, plan_search, the sibling workloads and the
+CPU baselines.
+
+--dump-outputs DIR.  After the timed steps, the arrays the last timed step produced -- what a caller of the ShardedRefiner receives:
+x [rows, d], the per-row cost / pose errors / masks, the per-seed summary [S, 8] (and the selected seed after the exchange) -- go to
+DIR/<name>.npy as float32 (float64 for integers), at most 64 MB in all (a seeded sample of rows beyond that, its indices in
+sampled_rows.npy).  N > 1: every rank writes its own shard as <name>_rank<r>.npy.  The inputs are seeded: the same arguments give
+the same inputs in every run, so two builds can be compared output for output.
 
 Prints ONE JSON line (rank 0).
 """
@@ -134,8 +146,13 @@ def parse_args(argv=None):
     ap.add_argument("--waypoints", type=int, default=256)
     ap.add_argument("--lm-steps", type=int, default=10, help="K fused LM iterations per launch")
     ap.add_argument("--scaling", choices=["auto", "weak", "strong"], default="auto", help="auto = strong for N > 1 (BASELINE.json configs[3])")
-    ap.add_argument("--repeats", type=int, default=5, help="the timed region is measured this many times back to back; the MEDIAN is reported")
-    ap.add_argument("--short-region-repeats", type=int, default=16, help="a region shorter than 0.4 ms is measured this many times more; 0 = never")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline (roofline, calibration, selection check, siblings, CPU baselines)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs to DIR/<name>.npy")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="the timed region is measured this many times back to back; the MEDIAN is reported (default 1, 5 with --full)")
+    ap.add_argument("--short-region-repeats", type=int, default=None,
+                    help="a region shorter than 0.4 ms is measured this many times more; 0 = never (default 0, 16 with --full)")
     ap.add_argument("--kernel-reps", type=int, default=400, help="isolated launches behind roofline.kernel_ms (median of HIP-event pairs)")
     ap.add_argument("--prewarm-ms", type=float, default=60.0, help="untimed launches before the warm-up steps, to reach sustained clocks")
     ap.add_argument("--gather-every", type=int, default=0, help="N > 1: steps per all-gather of the per-seed summaries (0 = distributed.launch_plan)")
@@ -155,6 +172,10 @@ def parse_args(argv=None):
     ap.add_argument("--transport", choices=["cabi", "c10d", "none"], default="cabi", help="N > 1: the all-gather's transport (distributed.pick_transport)")
     ap.add_argument("--config", choices=["C2", "C3", "C4", "C5"], default=None, help="BASELINE.json configs[1..4] geometry (default = C4)")
     args = ap.parse_args(argv)
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if args.short_region_repeats is None:
+        args.short_region_repeats = 16 if args.full else 0
     if args.config is not None:
         preset = {"C2": ("panda", 128, 64, False), "C3": ("fetch", 512, 256, True), "C4": ("panda", 1024, 256, True),
                   "C5": ("chain12", 4096, 512, True)}[args.config]  # robot, seeds, waypoints, collision fused
@@ -205,13 +226,14 @@ def launch_ranks(args) -> int:
 def timed(run, steps, warmup, prewarm_ms, barrier, repeats=1, closing_barrier=None):
     """`prewarm_ms` of untimed launches, W untimed warm-up steps, then `repeats` times: opening barrier + synchronize, clock, exactly
     `steps` steps (+ the exchange of a partly filled bucket), THIS RANK's synchronize, clock; the group's closing barrier follows.
-    Returns (elapsed seconds of every repetition, seconds the closing barrier took each time)."""
+    Returns (elapsed seconds of every repetition, seconds the closing barrier took each time, ring position the last one started at)."""
     run.prewarm(prewarm_ms)
     run.run_steps(warmup)
     run.drain()
     out, closing = [], []
     for _ in range(max(1, repeats)):
         barrier()
+        start = run.step_no if run.start_bucket is None else run.start_bucket * run.G  # (where run_region begins)
         t0 = time.perf_counter()
         run.run_region(steps)
         run.synchronize()
@@ -220,7 +242,50 @@ def timed(run, steps, warmup, prewarm_ms, barrier, repeats=1, closing_barrier=No
         if closing_barrier is not None:
             closing_barrier()
             closing.append(time.perf_counter() - t1)
-    return out, closing
+    return out, closing, start
+
+
+def last_step_slot(run, start, steps):
+    """Ring slot written by the last of `steps` steps that ShardedRefiner.run_steps issues from ring position `start` (its walk:
+    a whole bucket per graph replay, else launches of B steps, a shorter one at the end)."""
+    pos, last = start, None
+    while steps > 0:
+        b = pos % run.NBUF
+        c = run.G if (run.graphs is not None and b % run.G == 0 and steps >= run.G) else min(run.B, steps)
+        last, pos, steps = b + c - 1, pos + max(c, run.B), steps - c
+    return last
+
+
+DUMP_BUDGET_BYTES = 60_000_000  # under 64 MB in all, the .npy headers included
+
+
+def dump_outputs(run, slot, out_dir, rank, world):
+    """The arrays ring slot `slot` holds -- one step's result as a caller of the ShardedRefiner receives it -- as DIR/<name>.npy in
+    float32 (float64 for integer data); per-row arrays on a fixed seeded sample of rows when the whole would exceed the budget."""
+    from cppflow_amd.distributed import unpack_rows
+
+    run.synchronize()
+    rows = {"x": run.x_outs[slot]}
+    if run.collide:
+        names = ("ext_cost", "pos_err_m", "rot_err_rad", "self_mask", "env_mask", "jlim_mask")
+        rows.update(zip(names, unpack_rows(run.packeds[slot], run.n)))
+        per_seed = {"seed_summary": run.summ_all[slot].cpu().numpy().astype(np.float32)}
+    else:
+        rows.update(zip(("pos_err_m", "rot_err_rad"), run.errs[slot]))
+        per_seed = {}
+    if run.selected is not None:  # the exchange step's selection over all ranks' seeds for this step
+        per_seed["selected_seed"] = run.selected[slot // run.G][slot % run.G].cpu().numpy().astype(np.float64)
+    rows = {k: v.cpu().numpy().reshape(run.n, -1).astype(np.float32) for k, v in rows.items()}
+    budget = DUMP_BUDGET_BYTES // world - sum(a.nbytes for a in per_seed.values())
+    row_bytes = sum(a.shape[1] * 4 for a in rows.values())
+    if run.n * row_bytes > budget:
+        keep = np.sort(np.random.default_rng(0).choice(run.n, size=budget // (row_bytes + 8), replace=False))
+        rows = {k: a[keep] for k, a in rows.items()}
+        rows["sampled_rows"] = keep.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for k, a in {**rows, **per_seed}.items():
+        np.save(os.path.join(out_dir, f"{k}{suffix}.npy"), np.squeeze(a, axis=1) if a.ndim == 2 and a.shape[1] == 1 else a)
 
 
 def host_enqueue_us(run):
@@ -420,34 +485,37 @@ def main():
         return r, G_req
 
     def measure(run, steps, warmup, prewarm_ms, repeats):
-        el, cl = timed(run, steps, warmup, prewarm_ms, barrier, repeats, closing)
-        return [max_over_ranks(t) for t in el], [1e6 * max_over_ranks(t) for t in cl]
+        el, cl, start = timed(run, steps, warmup, prewarm_ms, barrier, repeats, closing)
+        return [max_over_ranks(t) for t in el], [1e6 * max_over_ranks(t) for t in cl], start
 
     x0, target, inputs_desc = inputs_for(scaling, args.inputs)
     run, G_req = refiner(x0, target, args.steps)
     n = run.n
     # ---- the headline: a fresh ShardedRefiner's default streams, `--repeats` regions, a short region more often ----
-    reps_s, closing_us = measure(run, args.steps, args.warmup, args.prewarm_ms, args.repeats)
+    reps_s, closing_us, start = measure(run, args.steps, args.warmup, args.prewarm_ms, args.repeats)
     if args.short_region_repeats > 0 and float(np.median(reps_s)) < 0.4e-3:  # (decided on the maximum over ranks: every rank alike)
-        more, more_c = measure(run, args.steps, args.warmup, args.prewarm_ms, args.short_region_repeats)
+        more, more_c, start = measure(run, args.steps, args.warmup, args.prewarm_ms, args.short_region_repeats)
         reps_s, closing_us = reps_s + more, closing_us + more_c
     elapsed = float(np.median(reps_s))
+    if args.dump_outputs:  # before anything else is launched: the ring slots still hold what the timed steps wrote
+        dump_outputs(run, last_step_slot(run, start, args.steps), args.dump_outputs, rank, world)
     # ---- secondary: the same regions on a calibrated stream pair (r4's headline; a best-of-30 pick, disclosed as such) ----
     calibrated = None
     want_cal = args.calibrate_streams == "on" or (args.calibrate_streams == "auto" and args.steps <= 64)
-    if want_cal and run.transport is not None and run.n_streams >= 2:
+    if args.full and want_cal and run.transport is not None and run.n_streams >= 2:
         rec = run.calibrate_streams(args.steps, barrier)
-        cal_s, _ = measure(run, args.steps, args.warmup, args.prewarm_ms, len(reps_s))
+        cal_s, _, _ = measure(run, args.steps, args.warmup, args.prewarm_ms, len(reps_s))
         calibrated = {"ms_per_step": 1e3 * float(np.median(cal_s)) / args.steps, "calibration": rec,
                       "note": "ShardedRefiner.calibrate_streams(): the fastest of the ordered stream pairs / start buckets tried during warm-up; NOT the headline"}
-    host_us = host_enqueue_us(run)
-    kstats = kernel_ms(run, max(200, args.kernel_reps))
-    ag_latency = run.allgather_latency_us(100)
-
-    outputs = run.outputs  # sanity on the result of the last step (not timed): most rows converged
-    conv_frac = float((outputs["pos_err_m"] < 1e-4).float().mean().item())
+    host_us = kstats = ag_latency = conv_frac = None
+    if args.full:
+        host_us = host_enqueue_us(run)
+        kstats = kernel_ms(run, max(200, args.kernel_reps))
+        ag_latency = run.allgather_latency_us(100)
+        conv_frac = float((run.outputs["pos_err_m"] < 1e-4).float().mean().item())  # sanity on one step's result: most rows converged
+    outputs = run.outputs
     selected = selection_check = None
-    if run.selected is not None:
+    if args.full and run.selected is not None:
         torch.cuda.synchronize()
         selected = [int(v) for v in run.selected[0][0].cpu()]
         # Self-verification of the exchange step: (1) every rank must hold the same selection; (2) under strong scaling it must equal
@@ -471,7 +539,7 @@ def main():
     # Once per planning call (not per step): ShardedRefiner.gather_and_search -- every rank gets ALL ranks' per-row costs / masks and
     # candidate paths and runs dp_search over them (cppflow/search.py:146-173).  Untimed here, reported beside the headline.
     plan_search = None
-    if collide:
+    if args.full and collide:
         torch.cuda.synchronize()
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         for _ in range(2):
@@ -526,7 +594,7 @@ def main():
         return out
 
     siblings = {}
-    if not args.no_siblings:
+    if args.full and not args.no_siblings:
         sib_steps = min(args.steps, 1000)
         if world > 1:
             other = "weak" if scaling == "strong" else "strong"
@@ -549,17 +617,17 @@ def main():
             r["what"] = "latency view: this rank's shard of ONE request per launch on one stream (no batching over requests, no exchange)"
             siblings["latency_one_request"] = r
 
-    census = D.device_census(rank, dev_index, dist is not None) if not share_gpu else None
+    census = D.device_census(rank, dev_index, dist is not None) if (args.full and not share_gpu) else None
     cpu_legs = {}
-    if world == 1 and rank == 0 and not args.no_cpu_baseline and args.inputs == "problem":
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline and args.inputs == "problem":
         x_h, t_h = x0.cpu(), target.cpu()
         pe_h, re_h = outputs["pos_err_m"].cpu(), outputs["rot_err_rad"].cpu()
         from oracle import cpu_baseline as cpu  # the checker's arithmetic timed beside the GPU: the only use of oracle/ in this file
 
         cpu_legs["cpu_baseline"] = cpu.cpu_baseline_torch(args.robot, obstacles, x_h, t_h, pe_h, re_h, K)
         cpu_legs["cpu_baseline_c"] = cpu.cpu_baseline_c(args.robot, obstacles, x_h, t_h, pe_h, K)
-    if rank == 0:
-        iters = float(n) * K * args.steps * world
+    def roofline():
+        """--full: the isolated kernel time against the committed counters of this launch shape and library build"""
         alg_flops = n * (K * algorithmic_flops_per_row_iter(d)
                          + (algorithmic_flops_collision(robot.n_capsules, robot.n_collision_pairs, len(obstacles)) if collide else 0.0))  # fmt: skip
         t_k = kstats["median"] * 1e-3
@@ -617,6 +685,10 @@ def main():
         if kprof and abs(kstats["median"] / kprof["ms"] - 1.0) > 0.15:
             print(f"bench: WARNING: live kernel time {1e3 * kstats['median']:.1f} us differs from the committed rocprofv3 average "
                   f"{1e3 * kprof['ms']:.1f} us by more than 15 %", file=sys.stderr)
+        return roof
+
+    if rank == 0:
+        iters = float(n) * K * args.steps * world
         line = {
             "metric": METRIC, "value": iters / elapsed, "unit": "LM-IK iterations/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
@@ -640,7 +712,7 @@ def main():
                 "hip_graphs": (f"on: each stream's {run.G} consecutive steps replayed as one captured graph" if run.graphs is not None else "off (one host call per launch)"),
                 "kernel_shape": args.shape, "solver": args.solver + (" (fp32 + conditioning-gated double-precision redo, the default)" if args.solver == "auto" else ""),
                 "early_out": "off (every row runs all K iterations: the metric counts K iterations per row)",
-                "prewarm_ms": args.prewarm_ms, "host_enqueue_us_per_step": host_us, "robot": args.robot,
+                "prewarm_ms": args.prewarm_ms, "robot": args.robot,
                 "seeds_total": S_cfg * (world if scaling == "weak" else 1), "seeds_per_gpu": run.S, "waypoints": W, "ndof": d,
                 "lm_iterations_per_step": K, "collision_fused": collide, "obstacles": len(obstacles),
                 "world_size": dist.get_world_size() if dist is not None else 1,
@@ -652,18 +724,21 @@ def main():
                 "allgather_bytes_per_rank_per_step": int(run.summ_all[0].numel() * 4) if run.gathered is not None else 0,
                 "steps_per_allgather": run.G if run.gathered is not None else 0,
                 "steps_per_allgather_requested": G_req if run.gathered is not None else 0,
-                "selected_seed_last_bucket": selected, "converged_frac_pos_err_lt_1e-4": conv_frac,
             },
-            "roofline": roof,
         }
+        if args.full:
+            line["config"].update({"host_enqueue_us_per_step": host_us, "selected_seed_last_bucket": selected, "converged_frac_pos_err_lt_1e-4": conv_frac})
+            line["roofline"] = roofline()
         if calibrated is not None:
             line["ms_per_step_calibrated_streams"] = calibrated["ms_per_step"]
             line["calibrated_streams"] = calibrated
         if plan_search is not None:
             line["plan_search"] = plan_search
         if rccl_rec is not None:
-            line["rccl"] = dict(rccl_rec, ranks=census, allgather_latency_us=ag_latency,
-                                allgather_latency_what="mean of 100 bare all-gathers of one step's [S,8] summaries on an idle stream (untimed diagnostic)")
+            line["rccl"] = dict(rccl_rec)
+            if args.full:
+                line["rccl"].update(ranks=census, allgather_latency_us=ag_latency,
+                                    allgather_latency_what="mean of 100 bare all-gathers of one step's [S,8] summaries on an idle stream (untimed diagnostic)")
         elif census is not None:
             line["devices"] = census
         if selection_check is not None:

@@ -5,5 +5,5 @@ set -e
 for rep in 1 2 3; do
 for lib in cppflow_amd/csrc/libcppflow_hip.so "$@"; do
   echo -n "$lib  "
-  CPPFLOW_HIP_LIB=$lib python bench.py --no-cpu-baseline --no-siblings --repeats 3 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('us/step %.2f   isolated kernel %.2f us' % (d['ms_per_step']*1e3, d['roofline']['kernel_ms']*1e3))"
+  CPPFLOW_HIP_LIB=$lib python bench.py --full --no-cpu-baseline --no-siblings --repeats 3 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('us/step %.2f   isolated kernel %.2f us' % (d['ms_per_step']*1e3, d['roofline']['kernel_ms']*1e3))"
 done; done

@@ -2,7 +2,7 @@
 """Dispatch timeline of the driver's own bench command under `rocprofv3 --kernel-trace` -> profiles/<round>_overlap.json.
 
     cd /tmp && rocprofv3 --kernel-trace --output-format csv -d $OUT/overlap -o kt -- python3 $ROOT/bench.py --gpus 1 --steps 20 \
-        --warmup 5 --no-cpu-baseline --no-siblings > $OUT/overlap_stdout.txt
+        --warmup 5 --full --no-cpu-baseline --no-siblings > $OUT/overlap_stdout.txt
     python3 scripts/overlap_summary.py $OUT/overlap $OUT/overlap_stdout.txt profiles/r5_overlap.json [steps]
 
 bench.py's headline `ms_per_step` (two launches in flight on two streams) is BELOW the fused kernel's own duration; this shows why
@@ -76,7 +76,7 @@ def main():
     alone = [c for c in cl if region_stats(c)["max_resident"] == 1]
     iso = [e - s for c in alone for s, e, _, _ in c][-400:]
     rec = {
-        "what": "rocprofv3 --kernel-trace of `python3 bench.py --gpus 1 --steps %d --warmup 5 --no-cpu-baseline --no-siblings`: every timed region "
+        "what": "rocprofv3 --kernel-trace of `python3 bench.py --gpus 1 --steps %d --warmup 5 --full --no-cpu-baseline --no-siblings`: every timed region "
                 "(a run of exactly %d overlapped lm_fused_kernel dispatches on two queues)" % (steps, steps),
         "library_build_id": line["roofline"]["library_build_id"] if line else None,
         "bench_ms_per_step_under_profiler": line["ms_per_step"] if line else None,

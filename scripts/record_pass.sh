@@ -26,10 +26,10 @@ fi
 if want full quick pmc; then
     cd /tmp
     echo "== rocprofv3 kernel trace of the headline command (one launch in flight)"
-    timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt" -o kt -- python3 "$ROOT/bench.py" --steps 200 --warmup 10 --no-cpu-baseline --no-siblings --streams 1 --pace off > "$OUT/kt_stdout.txt" 2> "$OUT/kt_stderr.txt"
+    timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt" -o kt -- python3 "$ROOT/bench.py" --full --steps 200 --warmup 10 --no-cpu-baseline --no-siblings --streams 1 --pace off > "$OUT/kt_stdout.txt" 2> "$OUT/kt_stderr.txt"
     echo "== rocprofv3 pmc FETCH_SIZE / WRITE_SIZE"
-    timeout -k 10 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -o pmc -- python3 "$ROOT/bench.py" --steps 5 --warmup 2 --prewarm-ms 0 --no-cpu-baseline --no-siblings --streams 1 > /dev/null 2> "$OUT/pmc_fetch_stderr.txt"
-    timeout -k 10 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write" -o pmc -- python3 "$ROOT/bench.py" --steps 5 --warmup 2 --prewarm-ms 0 --no-cpu-baseline --no-siblings --streams 1 > /dev/null 2> "$OUT/pmc_write_stderr.txt"
+    timeout -k 10 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -o pmc -- python3 "$ROOT/bench.py" --full --steps 5 --warmup 2 --prewarm-ms 0 --no-cpu-baseline --no-siblings --streams 1 > /dev/null 2> "$OUT/pmc_fetch_stderr.txt"
+    timeout -k 10 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write" -o pmc -- python3 "$ROOT/bench.py" --full --steps 5 --warmup 2 --prewarm-ms 0 --no-cpu-baseline --no-siblings --streams 1 > /dev/null 2> "$OUT/pmc_write_stderr.txt"
     echo "== rocprofv3 pmc SQ counters over scripts/pmc_probe.py (four passes)"
     timeout -k 10 600 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES SQ_BUSY_CYCLES SQ_INSTS_MFMA --output-format csv -d "$OUT/pmc_p1" -o pmc -- python3 "$ROOT/scripts/pmc_probe.py" panda > /dev/null 2> "$OUT/pmc_p1_stderr.txt"
     python3 "$ROOT/scripts/trim_pmc.py" "$OUT/pmc_p1/pmc_counter_collection.csv" 18
@@ -40,7 +40,7 @@ if want full quick pmc; then
     timeout -k 10 600 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_VALU_MFMA_COEXEC_CYCLES SQ_INSTS_VALU_MFMA_F32 SQ_WAIT_ANY --output-format csv -d "$OUT/pmc_p4" -o pmc -- python3 "$ROOT/scripts/pmc_probe.py" panda > /dev/null 2> "$OUT/pmc_p4_stderr.txt"
     python3 "$ROOT/scripts/trim_pmc.py" "$OUT/pmc_p4/pmc_counter_collection.csv" 18
     echo "== rocprofv3 kernel trace of the DRIVER's command (two streams): the overlap behind ms_per_step < kernel time"
-    timeout -k 10 600 rocprofv3 --kernel-trace --output-format csv -d "$OUT/overlap" -o kt -- python3 "$ROOT/bench.py" --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-siblings > "$OUT/overlap_stdout.txt" 2> "$OUT/overlap_stderr.txt"
+    timeout -k 10 600 rocprofv3 --kernel-trace --output-format csv -d "$OUT/overlap" -o kt -- python3 "$ROOT/bench.py" --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-siblings > "$OUT/overlap_stdout.txt" 2> "$OUT/overlap_stderr.txt"
     cd "$ROOT"
     mkdir -p "$OUT/profiles"
     python3 scripts/overlap_summary.py "$OUT/overlap" "$OUT/overlap_stdout.txt" "$OUT/profiles/${ROUND}_overlap.json" 20 | tail -22
@@ -54,36 +54,36 @@ fi
 
 if want full quick bench; then
     echo "== bench, default flags (N = 1, C4, 2000 steps, + one_stream / random_inputs siblings, + cpu baselines)"
-    timeout -k 10 600 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+    timeout -k 10 600 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
     cat "$OUT/bench.json"
     echo "== bench with the DRIVER's flags (--steps 20 --warmup 5)"
-    timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_driverflags.json" 2>> "$OUT/bench.err"
+    timeout -k 10 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_driverflags.json" 2>> "$OUT/bench.err"
     python3 -c "import json; d=json.load(open('$OUT/bench_driverflags.json')); r=d['roofline']; print('driver flags: us/step %.2f  value %.3e  frac %s  kernel %.1f us  overlapped %s  cpu agreement %s' % (d['ms_per_step']*1e3, d['value'], r['frac'], r['kernel_ms']*1e3, r['kernel_ms_overlapped'], d['cpu_baseline']['agreement']['max_abs_pos_err_diff_m']))"
     echo "== one rank's N = 8 shard (128 seeds) with the one-rank RCCL exchange on: driver flags, then 2000 steps"
-    CPPF_BENCH_FORCE_DIST=1 timeout -k 10 300 python bench.py --gpus 1 --seeds 128 --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/bench_shard128_driverflags.json" 2>> "$OUT/bench.err"
-    CPPF_BENCH_FORCE_DIST=1 timeout -k 10 300 python bench.py --gpus 1 --seeds 128 --steps 2000 --warmup 100 --no-cpu-baseline --no-siblings > "$OUT/bench_shard128_2000steps.json" 2>> "$OUT/bench.err"
+    CPPF_BENCH_FORCE_DIST=1 timeout -k 10 300 python bench.py --full --gpus 1 --seeds 128 --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/bench_shard128_driverflags.json" 2>> "$OUT/bench.err"
+    CPPF_BENCH_FORCE_DIST=1 timeout -k 10 300 python bench.py --full --gpus 1 --seeds 128 --steps 2000 --warmup 100 --no-cpu-baseline --no-siblings > "$OUT/bench_shard128_2000steps.json" 2>> "$OUT/bench.err"
     for f in bench_shard128_driverflags bench_shard128_2000steps; do
         python3 -c "import json; d=json.load(open('$OUT/$f.json')); c=d['config']; print('$f: us/step %.2f (calibrated streams: %s)  steps/launch %s  steps/allgather %s  streams %s  frac %s  allgather %.1f us' % (d['ms_per_step']*1e3, d.get('ms_per_step_calibrated_streams'), c['steps_per_launch'], c['steps_per_allgather'], c['streams'], d['roofline']['frac'], d['rccl']['allgather_latency_us']))"
     done
     echo "== bench, one-rank RCCL group at full size (collective + seed selection on the dependency path)"
-    CPPF_BENCH_FORCE_DIST=1 timeout -k 10 300 python bench.py --no-cpu-baseline --no-siblings > "$OUT/bench_dist1.json" 2>> "$OUT/bench.err"
+    CPPF_BENCH_FORCE_DIST=1 timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-siblings > "$OUT/bench_dist1.json" 2>> "$OUT/bench.err"
     echo "== two ranks sharing the one GPU (host-staged gloo: choreography rehearsal, NOT a multi-GPU result), driver flags"
-    CPPF_BENCH_SHARE_GPU=1 timeout -k 10 300 python bench.py --gpus 2 --steps 20 --warmup 5 --no-siblings > "$OUT/bench_2ranks_driverflags.json" 2>> "$OUT/bench.err"
+    CPPF_BENCH_SHARE_GPU=1 timeout -k 10 300 python bench.py --full --gpus 2 --steps 20 --warmup 5 --no-siblings > "$OUT/bench_2ranks_driverflags.json" 2>> "$OUT/bench.err"
     for c in C2 C3 C5; do
         echo "== bench --config $c"
-        timeout -k 10 300 python bench.py --no-cpu-baseline --no-siblings --config $c > "$OUT/bench_$c.json" 2>> "$OUT/bench.err"
+        timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-siblings --config $c > "$OUT/bench_$c.json" 2>> "$OUT/bench.err"
         python3 -c "import json; d=json.load(open('$OUT/bench_$c.json')); r=d['roofline']; print('$c: us/step %.2f  steps/launch %s  frac %s  at step rate %s' % (d['ms_per_step']*1e3, d['config']['steps_per_launch'], r['frac'], r['at_step_rate'].get('frac')))"
     done
     echo "== the other solver modes (what the gate costs)"
-    timeout -k 10 300 python bench.py --no-cpu-baseline --no-siblings --solver f64 --steps 300 > "$OUT/bench_solver_f64.json" 2>> "$OUT/bench.err"
-    timeout -k 10 300 python bench.py --no-cpu-baseline --solver f32 > "$OUT/bench_solver_f32.json" 2>> "$OUT/bench.err"
+    timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-siblings --solver f64 --steps 300 > "$OUT/bench_solver_f64.json" 2>> "$OUT/bench.err"
+    timeout -k 10 300 python bench.py --full --no-cpu-baseline --solver f32 > "$OUT/bench_solver_f32.json" 2>> "$OUT/bench.err"
     echo "== strong-scaling shards on one GPU (what each of 2 / 4 / 8 GPUs runs), batched launches vs one step per launch on 4 streams"
     rm -f "$OUT/shard_streams.txt"
     for s in 512 256 128; do for b in 0 1; do
-        timeout -k 10 200 python bench.py --seeds $s --steps 1000 --warmup 100 --batch $b --no-cpu-baseline --no-siblings 2>> "$OUT/bench.err" | python -c "import json,sys; d=json.loads(sys.stdin.read()); c=d['config']; print('seeds/GPU', c['seeds_per_gpu'], ' steps/launch', c['steps_per_launch'], ' streams', c['streams'], ' graphs', c['hip_graphs'][:3], ' us/step %.2f' % (d['ms_per_step']*1e3), ' isolated launch %.2f us' % (d['roofline']['kernel_ms']*1e3), ' host %.1f us/step' % c['host_enqueue_us_per_step'])" >> "$OUT/shard_streams.txt"
+        timeout -k 10 200 python bench.py --full --seeds $s --steps 1000 --warmup 100 --batch $b --no-cpu-baseline --no-siblings 2>> "$OUT/bench.err" | python -c "import json,sys; d=json.loads(sys.stdin.read()); c=d['config']; print('seeds/GPU', c['seeds_per_gpu'], ' steps/launch', c['steps_per_launch'], ' streams', c['streams'], ' graphs', c['hip_graphs'][:3], ' us/step %.2f' % (d['ms_per_step']*1e3), ' isolated launch %.2f us' % (d['roofline']['kernel_ms']*1e3), ' host %.1f us/step' % c['host_enqueue_us_per_step'])" >> "$OUT/shard_streams.txt"
     done; done
     for g in 16 64; do
-        CPPF_BENCH_FORCE_DIST=1 timeout -k 10 200 python bench.py --seeds 128 --steps 2048 --warmup 256 --gather-every $g --no-cpu-baseline --no-siblings 2>> "$OUT/bench.err" | python -c "import json,sys; d=json.loads(sys.stdin.read()); c=d['config']; print('seeds/GPU 128 + RCCL(1 rank) + select: steps/launch', c['steps_per_launch'], ' steps/allgather', c['steps_per_allgather'], ' streams', c['streams'], ' us/step %.2f' % (d['ms_per_step']*1e3), ' host %.1f us/step' % c['host_enqueue_us_per_step'])" >> "$OUT/shard_streams.txt"
+        CPPF_BENCH_FORCE_DIST=1 timeout -k 10 200 python bench.py --full --seeds 128 --steps 2048 --warmup 256 --gather-every $g --no-cpu-baseline --no-siblings 2>> "$OUT/bench.err" | python -c "import json,sys; d=json.loads(sys.stdin.read()); c=d['config']; print('seeds/GPU 128 + RCCL(1 rank) + select: steps/launch', c['steps_per_launch'], ' steps/allgather', c['steps_per_allgather'], ' streams', c['streams'], ' us/step %.2f' % (d['ms_per_step']*1e3), ' host %.1f us/step' % c['host_enqueue_us_per_step'])" >> "$OUT/shard_streams.txt"
     done
     cat "$OUT/shard_streams.txt"
     echo "== which rows the gate flags, per iteration (bench inputs and independent random configurations)"

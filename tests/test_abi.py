@@ -100,7 +100,7 @@ def test_struct_layouts_match_header_constants():
     assert ctypes.sizeof(_hip.Constraints) == 24
 
 
-def test_batch_item_layout_and_fused_argument_offset(lib):
+def test_batch_item_layout_and_fused_argument_offset(lib, tmp_path):
     """cppf_lm_batch_item as ctypes sees it equals the C struct (two pointers, S, W, the 13 output pointers), and the fused kernel's
     view of its own kernel-argument segment is right: the device code reads the problem of a plain launch at offsetof(FusedArgs,
     single) from the segment's base (csrc/kernels_fused.h: fused_item) -- the code object's metadata must place the kernel's fourth
@@ -119,7 +119,7 @@ def test_batch_item_layout_and_fused_argument_offset(lib):
     sys.path.insert(0, os.path.join(os.path.dirname(build.CSRC), "..", "scripts"))
     import kernel_resources as kr
 
-    co = os.path.join(os.environ.get("TMPDIR", "/tmp"), "cppf_abi_test.co")
+    co = str(tmp_path / "cppf_abi_test.co")
     notes = ""
     for path in kr.extract_code_objects(build.OUT, co):
         notes += subprocess.run([f"{kr.LLVM}/llvm-readelf", "--notes", path], capture_output=True, text=True, check=True).stdout
@@ -136,7 +136,7 @@ def test_batch_item_layout_and_fused_argument_offset(lib):
     assert seen >= 12 * 3, seen  # every shipped table x COLL and every generic ndof x COLL
 
 
-def test_no_test_kernel_ships_in_the_product_library(lib):
+def test_no_test_kernel_ships_in_the_product_library(lib, tmp_path):
     """a test-only kernel (the exhaustive reciprocal sweep) lived in libcppflow_hip.so.  Test kernels are a translation
     unit of their own (tests/native/, built by build_test_kernels into its own shared object); the product library exports no
     cppf_test_* / *_sweep symbol and holds no such kernel."""
@@ -147,7 +147,7 @@ def test_no_test_kernel_ships_in_the_product_library(lib):
     from cppflow_amd import build
 
     out = subprocess.run([sys.executable, os.path.join(os.path.dirname(build.CSRC), "..", "scripts", "kernel_resources.py")],
-                         capture_output=True, text=True, check=True).stdout
+                         capture_output=True, text=True, check=True, env=dict(os.environ, CPPF_CODE_OBJECT_OUT=str(tmp_path / "lib.co"))).stdout
     assert "lm_fused_kernel" in out and "sweep" not in out and "test" not in out.lower().replace("latest", ""), [ln for ln in out.splitlines() if "sweep" in ln or "test" in ln.lower()]
     syms = subprocess.run(["nm", "-D", "--defined-only", build.OUT], capture_output=True, text=True, check=True).stdout
     assert "cppf_lm_batch_launch" in syms and "rcp_sweep" not in syms and "cppf_test_" not in syms
@@ -208,10 +208,14 @@ def test_graft_entry_build_runs():
     entry.build()
 
 
-def test_run_time_specialisation_compiles_without_a_gpu(lib, tmp_path):
+def test_run_time_specialisation_compiles_without_a_gpu(lib, tmp_path, monkeypatch):
     """cppf_robot_specialize's generate -> hipRTC -> cache stages need no device (cppf_debug_rtc_compile): a random 7-DoF chain
     compiles for gfx950, the cache entry appears, and a second call finds it (no recompilation)."""
     import time
+
+    # hipRTC stages the embedded headers under $TMPDIR/include: a private one, not whatever another user left in a shared /tmp
+    (tmp_path / "tmp").mkdir()
+    monkeypatch.setenv("TMPDIR", str(tmp_path / "tmp"))
 
     from cppflow_amd import _hip
     from cppflow_amd.robot_model import canonicalize
@@ -259,7 +263,7 @@ def test_library_carries_the_hash_of_the_sources_it_was_built_from(lib):
     assert not build.needs_build()
 
 
-def test_build_id_covers_every_translation_unit_and_its_flags(monkeypatch):
+def test_build_id_covers_every_translation_unit_and_its_flags(monkeypatch, tmp_path):
     """The library is linked from two translation units (csrc/fused_static.hip holds the headline kernel under other scheduler
     flags): the build id must change when either source, a shared header or the flags of ONE unit change -- otherwise records keyed
     by the build id (profiles/r3_issue.json, bench.py's roofline) could outlive the code they were taken from."""
@@ -281,14 +285,15 @@ def test_build_id_covers_every_translation_unit_and_its_flags(monkeypatch):
     import sys
 
     out = subprocess.run([sys.executable, os.path.join(os.path.dirname(build.CSRC), "..", "scripts", "kernel_resources.py"), "",
-                          "lm_fused_kernel<cppf::StaRobot<cppf::gen::Panda>, 1>"], capture_output=True, text=True, check=True).stdout  # fmt: skip
+                          "lm_fused_kernel<cppf::StaRobot<cppf::gen::Panda>, 1>"], capture_output=True, text=True, check=True,
+                         env=dict(os.environ, CPPF_CODE_OBJECT_OUT=str(tmp_path / "lib.co"))).stdout  # fmt: skip
     line = [ln for ln in out.splitlines() if "lm_fused_kernel" in ln]
     assert len(line) == 1, out
     vgpr, scratch = int(line[0].split()[1]), int(line[0].split()[7])
     assert vgpr <= 128 and scratch == 0, line[0]  # four wavefronts per SIMD, nothing spilled
 
 
-def test_no_kernel_of_the_library_touches_scratch(lib):
+def test_no_kernel_of_the_library_touches_scratch(lib, tmp_path):
     """the coupled step's parallel-in-time elimination at 8 joints (300 - 372 B per lane), the large-launch block kernel
     of FetchArm and the generic 7- / 8-joint chains, and the four-lanes-per-row kernel at 11 / 12 joints spilled registers to scratch
     memory.  Round 4: the elimination streams its coupling blocks instead of holding them, the other two are built for the
@@ -300,7 +305,7 @@ def test_no_kernel_of_the_library_touches_scratch(lib):
     from cppflow_amd import build
 
     out = subprocess.run([sys.executable, os.path.join(os.path.dirname(build.CSRC), "..", "scripts", "kernel_resources.py")],
-                         capture_output=True, text=True, check=True).stdout
+                         capture_output=True, text=True, check=True, env=dict(os.environ, CPPF_CODE_OBJECT_OUT=str(tmp_path / "lib.co"))).stdout
     rows = [ln.split() for ln in out.splitlines() if ln.startswith("vgpr")]
     assert len(rows) > 300, len(rows)  # every instantiation of both translation units
     spilled = [" ".join(r[:10] + r[10:14]) for r in rows if int(r[7]) != 0]

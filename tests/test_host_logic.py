@@ -16,7 +16,8 @@ from cppflow_amd.evaluation_utils import errors_are_below_threshold, seed_metric
 from cppflow_amd.lm_hyper_parameters import ALT_LOSS_V2_1_DIFF, ALT_LOSS_V2_1_POSE, OptimizationParameters
 from cppflow_amd.robots import Robot, get_robot
 
-REFERENCE = "/root/reference/cppflow"
+# the reference's own problem / path files (cppflow/problems/*.yaml, cppflow/paths/*.csv, tests/fetch_arm__s__truncated.yaml), as data
+REFERENCE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_files")
 
 
 def test_pose_preset_values():
@@ -123,20 +124,18 @@ def test_problem_loader_formats():
 
 def test_problem_listing():
     """ALL_PROBLEM_FILENAMES / get_problem_dict / get_all_problems (cppflow/data_type_utils.py:24-52, 222-241) over the
-    shipped problems directory and, when it is mounted, over the reference's own (every one of its problem files parses)."""
+    shipped problems directory and over the reference's own (tests/golden/reference_files: every one of its problem files parses)."""
     from cppflow_amd import data_type_utils as U
 
     assert U.ALL_PROBLEM_FILENAMES == ["fetch__line", "panda__line"] and set(U.ALL_OBS_PROBLEM_FILENAMES) <= set(U.ALL_PROBLEM_FILENAMES)
     problems = U.get_all_problems(device="cpu")
     assert [p.full_name for p in problems] == U.ALL_PROBLEM_FILENAMES and all(p.target_path.shape[1] == 7 for p in problems)
-    ref = "/root/reference/cppflow"
-    if os.path.isdir(os.path.join(ref, "problems")):
-        theirs = U.get_all_problems(os.path.join(ref, "problems"), os.path.join(ref, "paths"), device="cpu")
-        names = {p.full_name for p in theirs}
-        assert {"panda__2cubes", "panda__1cube", "fetch__hello", "fetch_arm__s"} <= names
-        by = {p.full_name: p for p in theirs}
-        assert by["fetch__hello"].robot is by["fetch__circle"].robot or len(by["fetch__circle"].obstacles) > 0
-        assert len(by["panda__2cubes"].obstacles) == 2
+    theirs = U.get_all_problems(os.path.join(REFERENCE, "problems"), os.path.join(REFERENCE, "paths"), device="cpu")
+    names = {p.full_name for p in theirs}
+    assert len(names) == 18 and {"panda__2cubes", "panda__1cube", "fetch__hello", "fetch_arm__s"} <= names
+    by = {p.full_name: p for p in theirs}
+    assert by["fetch__hello"].robot is by["fetch__circle"].robot or len(by["fetch__circle"].obstacles) > 0
+    assert len(by["panda__2cubes"].obstacles) == 2
 
 
 def test_offset_and_resample():
@@ -162,9 +161,8 @@ def test_offset_and_resample():
     np.testing.assert_allclose(r[0], path[0]) and np.testing.assert_allclose(r[-1], path[-1])
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="reference tree not present (GPU box)")
 def test_loader_reads_the_reference_problem_files():
-    """The loader consumes the reference's own yaml / csv files where they lie (read as data)."""
+    """The loader consumes the reference's own yaml / csv files (copies under tests/golden/reference_files, read as data)."""
     kw = dict(problems_dir=os.path.join(REFERENCE, "problems"), paths_dir=os.path.join(REFERENCE, "paths"), device="cpu")
     p = problem_from_filename(None, "panda__2cubes", **kw)
     assert p.n_timesteps == 200 and len(p.obstacles_cuboids) == 2
@@ -172,7 +170,7 @@ def test_loader_reads_the_reference_problem_files():
     np.testing.assert_allclose(p.obstacles_Tcuboids[1][:3, 3].numpy(), [-0.25, 0.3, 0.75], atol=1e-7)
     f = problem_from_filename(None, "fetch__hello", **kw)
     assert f.robot.ndof == 8 and f.n_timesteps == 553 and len(f.obstacles_cuboids) == 0
-    a = problem_from_filename(None, "", filepath_override="/root/reference/tests/fetch_arm__s__truncated.yaml", **kw)
+    a = problem_from_filename(None, "", filepath_override=os.path.join(REFERENCE, "fetch_arm__s__truncated.yaml"), **kw)
     assert a.robot.name == "fetch_arm" and a.n_timesteps == 59
     raw = load_path_csv(os.path.join(REFERENCE, "paths", "s_truncated.csv"))
     np.testing.assert_allclose(a.target_path[:, :3].numpy(), raw[:, :3] + [1.0 - 0.086875, 0.3, 0.55 + 0.37743], atol=1e-6)
