@@ -60,6 +60,27 @@ class LmParams(ctypes.Structure):
     ]
 
 
+class TrackParams(ctypes.Structure):
+    """struct cppf_track_params"""
+
+    _fields_ = [
+        ("lm_lambda", _f),
+        ("alpha_position", _f),
+        ("alpha_rotation", _f),
+        ("n_restart", _i32),
+        ("n_track", _i32),
+        ("n_random_restarts", _i32),
+        ("tol_pos_m", _f),
+        ("tol_rot_rad", _f),
+        ("max_jump_rad", _f),
+        ("max_jump_m", _f),
+        ("seed", ctypes.c_uint32),
+        ("call_index", ctypes.c_uint32),
+    ]
+
+
+TRACK_CONVERGED, TRACK_RESTARTED, TRACK_JUMP, TRACK_RECOVERED = 1, 2, 4, 8  # cppf_track_paths' status bits (CPPF_TRACK_*)
+
 SHAPE_AUTO, SHAPE_ROW, SHAPE_QUAD = 0, 1, 2
 SOLVER_AUTO, SOLVER_F64, SOLVER_F32 = 0, 1, 2  # AUTO = fp32 with the conditioning-gated double-precision redo (the default)
 
@@ -160,6 +181,10 @@ SIGNATURES = {
     ),
     "cppf_pose_error_metrics": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),
     "cppf_seed_validity": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp]),
+    "cppf_track_paths": (
+        ctypes.c_int,
+        [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(TrackParams), _vp, _vp, _vp, _vp, _vp, _vp],
+    ),
     "cppf_self_collision_distances_jacobian": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _vp, _vp]),
     "cppf_env_collision_distances_jacobian": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.POINTER(_f), ctypes.POINTER(_f),
                                                              _vp, _vp, _vp]),

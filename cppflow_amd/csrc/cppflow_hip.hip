@@ -58,6 +58,7 @@ constexpr int kBlock = CPPF_BLOCK;
 #include "kernels_chain.h"
 #include "kernels_collision.h"
 #include "kernels_fused.h"
+#include "kernels_track.h"
 #include "kernels_quad.h"
 #include "kernels_eval.h"
 #include "kernels_coupled.h"
@@ -1068,6 +1069,56 @@ int cppf_pose_error_metrics(const cppf_robot* robot, const float* x, const float
     CPPF_DISPATCH_D(robot->desc.ndof,
                     hipLaunchKernelGGL((pose_metrics_kernel<D>), dim3(grid_for(n)), dim3(kBlock), 0, st, robot->chain,
                                        robot->coll, (int)n, W, x, target, pos_err_m, rot_err_rad));
+    return check_launch(robot);
+}
+
+int cppf_track_paths(const cppf_robot* robot, const float* target, int T, int k, int S, const cppf_track_params* params,
+                     const float* q0, float* q_out, float* pos_err_m, float* rot_err_rad, uint8_t* status, void* stream) {
+    // every argument is checked before the device is selected (CPPF_ENTER), so that the checks hold for a host-only handle too
+    CPPF_REQUIRE(robot != nullptr, "robot handle is NULL");
+    CPPF_REQUIRE(!(robot->life.load(std::memory_order_acquire) & kRobotDead), "the robot handle was destroyed");
+    CPPF_REQUIRE(params, "params is NULL");
+    CPPF_REQUIRE(T >= 0 && k >= 0, "T / k < 0");
+    CPPF_REQUIRE(S >= 1, "S (segments) must be >= 1");
+    CPPF_REQUIRE(params->n_restart >= 1 && params->n_track >= 1, "n_restart / n_track must be >= 1");
+    CPPF_REQUIRE(params->n_random_restarts >= 0, "n_random_restarts must be >= 0");
+    CPPF_REQUIRE(params->max_jump_rad >= 0.f && params->max_jump_m >= 0.f, "max_jump_rad / max_jump_m must be >= 0 (0 = off)");
+    cppf_lm_params lp = {};
+    lp.lm_lambda = params->lm_lambda;
+    lp.alpha_position = params->alpha_position;
+    lp.alpha_rotation = params->alpha_rotation;
+    lp.n_steps = std::max(params->n_restart, params->n_track);
+    lp.clamp = 1;
+    lp.tol_pos_m = params->tol_pos_m;
+    lp.tol_rot_rad = params->tol_rot_rad;
+    lp.shape = CPPF_SHAPE_ROW;
+    lp.solver = CPPF_SOLVER_AUTO;
+    lp.solver_gate = 0.f;
+    LmK prm;
+    if (int rc = make_lm_kernel_params(robot, &lp, prm)) return rc;
+    prm.pace_ticks = 0;  // (a latency launch: no fair-share schedule)
+    if (T == 0 || k == 0) return CPPF_OK;
+    CPPF_REQUIRE(S <= T, "S (segments) must be <= T: every segment needs a waypoint");
+    CPPF_REQUIRE((size_t)k * (size_t)S <= 0x7fffffffu && (size_t)k * (size_t)T <= 0x7fffffffu, "k*S / k*T exceeds 2^31-1");
+    CPPF_REQUIRE(target && q_out && pos_err_m && rot_err_rad && status, "target / q_out / pos_err_m / rot_err_rad / status is NULL");
+    CPPF_ENTER(robot);
+    TrackK tk;
+    tk.target = target, tk.q0 = q0, tk.q_out = q_out, tk.pos_err = pos_err_m, tk.rot_err = rot_err_rad, tk.status = status;
+    tk.T = T, tk.k = k, tk.S = S;
+    tk.n_restart = params->n_restart, tk.n_track = params->n_track, tk.n_random = params->n_random_restarts;
+    tk.max_jump_rad = params->max_jump_rad, tk.max_jump_m = params->max_jump_m;
+    tk.seed = params->seed, tk.call_index = params->call_index;
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned grid = (unsigned)(((size_t)k * S + kTrackBlock - 1) / kTrackBlock);
+    if (use_rtc(robot)) {
+        void* args[] = {(void*)&robot->chain, (void*)&robot->coll, (void*)&prm, (void*)&tk};
+        CPPF_HIP(hipModuleLaunchKernel(robot->rtc->fn[RTC_TRACK], grid, 1, 1, (unsigned)kTrackBlock, 1, 1, 0, st, args, nullptr));
+        return CPPF_OK;
+    }
+#define CPPF_BODY \
+    hipLaunchKernelGGL((track_kernel<RB>), dim3(grid), dim3(kTrackBlock), 0, st, robot->chain, robot->coll, prm, tk)
+    CPPF_DISPATCH_RB(robot)
+#undef CPPF_BODY
     return check_launch(robot);
 }
 

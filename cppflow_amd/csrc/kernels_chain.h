@@ -553,7 +553,7 @@ constexpr unsigned long long gate_tri_pack(bool rows) {
 // The double-precision re-solve of up to kGateSlots rows of a wavefront, by the WHOLE wavefront (it is waiting for it anyway; in a
 // launch of one wavefront per SIMD a round is pure latency): (1) the 21 entries of A = J J^T + lambda S^-2 of every slot are one
 // task each -- 7 .. 12 FMAs -- spread over the 64 lanes (one lane per slot forming its own A was 21 D FMAs in a row, more than
-// half of the round); (2) lanes 0 .. cnt-1 factor and substitute, one slot each, A coming from LDS; (3) the D entries of
+// half of the round); (2) the active lanes of rank 0 .. cnt-1 factor and substitute, one slot each, A coming from LDS; (3) the D entries of
 // delta = J^T y of every slot are one task each again.  J is only ever read from LDS, by whoever needs an entry.
 // Everything stays inside one wavefront: no barrier, the LDS accesses of a wavefront complete in order (s_waitcnt lgkmcnt(0)
 // between the stages).
@@ -562,8 +562,8 @@ __device__ __forceinline__ void gate_solve_slots(float* __restrict__ w, int cnt,
     double* const wd = reinterpret_cast<double*>(w + GateLds<D>::kJe);
     constexpr unsigned long long kRow = gate_tri_pack(true), kCol = gate_tri_pack(false);
     // (1) A
-    // (the tasks go round the ACTIVE lanes: lanes 0 .. nact-1, a prefix of the wavefront -- the last wavefront of a launch may be
-    // partly empty)
+    // (the tasks go round the ACTIVE lanes, `lane` = rank among them, 0 .. nact-1: the last wavefront of a launch may be partly empty,
+    // and the tracking kernel's lanes climb its recovery ladder or walk segments of unequal length in any data-dependent pattern)
     const int n_a = cnt * 21;
 #pragma unroll 1
     for (int base = 0; base < n_a; base += nact) {
@@ -581,7 +581,7 @@ __device__ __forceinline__ void gate_solve_slots(float* __restrict__ w, int cnt,
         }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    // (2) Cholesky with the damping as pivot floor, forward and back substitution: one lane per slot
+    // (2) Cholesky with the damping as pivot floor, forward and back substitution: one active lane per slot
     if (lane < cnt) {
         double A[6][6];  // lower triangle; L overwrites it
         {
@@ -650,7 +650,7 @@ __device__ __forceinline__ void gate_solve_slots(float* __restrict__ w, int cnt,
 // the fp32 solve (y is known, so is the estimate; J^T y is still to come), so that J is not kept in registers a moment longer than
 // the fp32 solve itself needs it.  A wavefront with more flagged rows than slots comes back for another round with J recomputed
 // (lm_row_iterate) rather than parking 48 floats per row in registers meanwhile.
-// lm_gate_solve: lanes 0 .. cnt-1 solve one slot each in double precision; the flagged rows pick their delta up and clear `flag`.
+// lm_gate_solve: the first cnt active lanes solve one slot each in double precision; the flagged rows pick their delta up and clear `flag`.
 template <int D>
 __device__ __forceinline__ int lm_gate_hand_over(const float (&J)[6][D], const float (&e)[6], unsigned long long todo,
                                                  float* __restrict__ w, bool flag) {
@@ -670,11 +670,13 @@ __device__ __forceinline__ int lm_gate_hand_over(const float (&J)[6][D], const f
 template <int D>
 __device__ __forceinline__ void lm_gate_solve(double lam_r, double lam_p, unsigned long long todo, int rank,
                                               float* __restrict__ w, bool& flag, float (&delta)[D]) {
-    const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
     const int cnt = min((int)__builtin_popcountll(todo), kGateSlots);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the slots are written (one wavefront: its LDS accesses complete in order)
-    // Every lane of the wavefront works on the slots (gate_solve_slots), flagged itself or not.
-    const int nact = (int)__builtin_popcountll(__builtin_amdgcn_ballot_w64(true));
+    // Every ACTIVE lane of the wavefront works on the slots (gate_solve_slots), flagged itself or not, by its rank among the active
+    // lanes: the active lanes need not be a prefix of the wavefront (for a prefix the rank is the lane id)
+    const unsigned long long act = __builtin_amdgcn_ballot_w64(true);
+    const int lane = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(act >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)act, 0u));
+    const int nact = (int)__builtin_popcountll(act);
     gate_solve_slots<D>(w, cnt, lane, nact, lam_r, lam_p);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     if (flag && rank < kGateSlots) {

@@ -24,7 +24,7 @@
 
 namespace {
 
-enum RtcKernel { RTC_FUSED0 = 0, RTC_FUSED1, RTC_FUSED2, RTC_COLL_MASK, RTC_COLL_MIN, RTC_QUAD0, RTC_QUAD1, RTC_COUNT };
+enum RtcKernel { RTC_FUSED0 = 0, RTC_FUSED1, RTC_FUSED2, RTC_COLL_MASK, RTC_COLL_MIN, RTC_QUAD0, RTC_QUAD1, RTC_TRACK, RTC_COUNT };
 
 const char* const kRtcNameExpr[RTC_COUNT] = {
     "cppf_rtc::lm_fused_kernel<cppf::StaRobot<cppf::gen::Custom>, 0>",
@@ -34,6 +34,7 @@ const char* const kRtcNameExpr[RTC_COUNT] = {
     "cppf_rtc::collision_kernel<cppf::StaRobot<cppf::gen::Custom>, true>",
     "cppf_rtc::lm_quad_kernel<cppf::StaRobot<cppf::gen::Custom>, 0, false>",
     "cppf_rtc::lm_quad_kernel<cppf::StaRobot<cppf::gen::Custom>, 1, false>",
+    "cppf_rtc::track_kernel<cppf::StaRobot<cppf::gen::Custom>>",
 };
 
 // (the machine scheduler of fused_static.hip: the fused kernel gains 2.4 %, the quad kernels 1.5 %, the collision kernel loses 1 %)
@@ -183,7 +184,7 @@ std::string rtc_program_source(const cppf_robot& rb) {
     s += "constexpr int kBlock = " + std::to_string(kBlock) + ";\n";
     s += "#define CPPF_WAVES_LM " + std::to_string(CPPF_WAVES_LM) + "\n";
     s += "#define CPPF_WAVES_COLL " + std::to_string(CPPF_WAVES_COLL) + "\n";
-    s += "#include \"kernels_chain.h\"\n#include \"kernels_collision.h\"\n#include \"kernels_fused.h\"\n#include \"kernels_quad.h\"\n";
+    s += "#include \"kernels_chain.h\"\n#include \"kernels_collision.h\"\n#include \"kernels_fused.h\"\n#include \"kernels_track.h\"\n#include \"kernels_quad.h\"\n";
     s += "}  // namespace cppf_rtc\n";
     return s;
 }

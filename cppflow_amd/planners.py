@@ -74,6 +74,78 @@ class LmIkSeedProvider:
         return out
 
 
+class TrackingSeedProvider:
+    """k candidate joint-space paths for a problem by tracking IK in ONE launch (`Robot.track_paths`, csrc/kernels_track.h): the same
+    `(problem, k) -> [k,T,d]` contract as `LmIkSeedProvider`, without its per-waypoint loop of launches.  The path is cut into
+    segments that every candidate tracks independently (one lane each); rows that miss the tolerances or jump by more than
+    `max_jump_rad` / `max_jump_m` climb the recovery ladder (warm continuation, then `n_random_restarts` random restarts).
+
+    Every call draws new candidates: a call counter goes into the kernel's hash (a planner's rerun, DEFAULT_RERUN_NEW_K, gets other
+    candidates), and so does the rank of torch.distributed, read at call time (rank-distinct candidates under seed sharding).  With
+    `problem.initial_configuration`, candidate 0 starts its first segment exactly there and the others from uniform perturbations of
+    width `init_width` around it, clamped to the joint limits (the joint-space analogue of the reference's `_sample_latents_near`,
+    cppflow/planners.py:136-153).  `last` holds the last call's per-row `status`, `pos_err_m` and `rot_err_rad` [k,T].
+
+    Segments: `n_segments` if given, else ceil(T / `waypoints_per_segment`).  A lane runs n_restart + (T / S - 1) n_track LM
+    iterations in sequence, and one iteration of a lone lane takes 1.5 - 1.7 us on gfx950 whatever S is (profiles/track_sweep.txt), so
+    the default of 35 waypoints per segment caps that depth at 40 + 34 x 6 = 244 iterations, ~0.4 ms of fixed work for any path
+    length (fetch__hello, T = 553: S = 16), while a short path (T <= 35) stays one continuous track per candidate."""
+
+    def __init__(self, seed: int = 0, n_segments: Optional[int] = None, waypoints_per_segment: int = 35, damping: float = 1e-2, n_restart_steps: int = 40, n_track_steps: int = 6,
+                 n_random_restarts: int = 2, tol_pos_m: float = 5e-5, tol_rot_rad: float = 5e-4, max_jump_rad: float = 0.0,
+                 max_jump_m: float = 0.0, init_width: float = 0.25):  # fmt: skip
+        assert n_segments is None or int(n_segments) >= 1, "n_segments must be >= 1"
+        assert int(waypoints_per_segment) >= 1, "waypoints_per_segment must be >= 1"
+        assert float(damping) > 0.0, "damping must be > 0"
+        assert int(n_restart_steps) >= 1 and int(n_track_steps) >= 1, "n_restart_steps / n_track_steps must be >= 1"
+        assert int(n_random_restarts) >= 0, "n_random_restarts must be >= 0"
+        assert float(tol_pos_m) >= 0.0 and float(tol_rot_rad) >= 0.0, "tolerances must be >= 0"
+        assert (float(tol_pos_m) > 0.0) == (float(tol_rot_rad) > 0.0), "set both tolerances or neither"
+        assert float(max_jump_rad) >= 0.0 and float(max_jump_m) >= 0.0, "jump bars must be >= 0 (0 = off)"
+        assert float(init_width) >= 0.0, "init_width must be >= 0"
+        self.seed = int(seed)
+        self.n_segments = None if n_segments is None else int(n_segments)
+        self.waypoints_per_segment = int(waypoints_per_segment)
+        self._kw = dict(lm_lambda=float(damping), n_restart=int(n_restart_steps), n_track=int(n_track_steps),
+                        n_random_restarts=int(n_random_restarts), tol_pos_m=float(tol_pos_m), tol_rot_rad=float(tol_rot_rad),
+                        max_jump_rad=float(max_jump_rad), max_jump_m=float(max_jump_m))  # fmt: skip
+        self.init_width = float(init_width)
+        self.n_calls = 0
+        self.last: Optional[Dict[str, torch.Tensor]] = None
+
+    def _q0_near(self, problem: Problem, k: int, S: int, seed: int) -> torch.Tensor:
+        """[k*S, d] starts: segment 0 of candidate 0 at the initial configuration, of the others clamped uniform perturbations around it;
+        the later segments uniform in the joint box the kernel draws from."""
+        rb, dev = problem.robot, problem.target_path.device
+        d = rb.ndof
+        gen = torch.Generator().manual_seed(seed)
+        lo = torch.tensor([l for l, _ in rb.actuated_joints_limits], dtype=torch.float32)
+        hi = torch.tensor([u for _, u in rb.actuated_joints_limits], dtype=torch.float32)
+        q0 = (lo + (hi - lo) * (0.1 + 0.8 * torch.rand((k, S, d), generator=gen)))
+        center = problem.initial_configuration.detach().reshape(-1).to("cpu", torch.float32)
+        near = center + self.init_width * (torch.rand((k, d), generator=gen) - 0.5)
+        near[0] = center
+        q0[:, 0] = torch.minimum(torch.maximum(near, lo), hi)
+        q0[0, 0] = center  # exactly there, even outside the limits
+        return q0.reshape(k * S, d).to(dev)
+
+    def __call__(self, problem: Problem, k: int) -> torch.Tensor:
+        rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+        T = problem.n_timesteps
+        S = self.n_segments if self.n_segments is not None else -(-T // self.waypoints_per_segment)
+        S = max(1, min(S, T))
+        call = self.n_calls
+        self.n_calls += 1
+        seed = (self.seed + 0x9E3779B1 * rank) & 0xFFFFFFFF
+        q0 = None
+        if problem.initial_configuration is not None:
+            q0 = self._q0_near(problem, k, S, (seed * 1000003 + call) & 0x7FFFFFFF)
+        res = problem.robot.track_paths(problem.target_path.contiguous(), k, n_segments=S, q0=q0, seed=seed, call_index=call,
+                                        **self._kw)  # fmt: skip
+        self.last = {key: res[key] for key in ("status", "pos_err_m", "rot_err_rad")}
+        return res["x"]
+
+
 class Planner:
     def __init__(self, settings: PlannerSettings, robot, seed_provider: Optional[SeedProvider] = None, process_group=None,
                  candidate_lm_steps: int = 0):
@@ -139,7 +211,10 @@ class Planner:
         t0 = time()
         qpath_search = dp_search(self.robot, qs.contiguous(), self_viol, env_viol)
         time_dp = time() - t0
-        return qpath_search, False, TimingData(-1, time_seeds, time_coll, 0.0, time_dp, 0.0), {}, (qs, self_viol, env_viol)
+        debug_info = {}
+        if self._cfg.do_return_search_path_mjac:  # (cppflow/planners.py:283-284)
+            add_search_path_mjac(debug_info, problem, qpath_search)
+        return qpath_search, False, TimingData(-1, time_seeds, time_coll, 0.0, time_dp, 0.0), debug_info, (qs, self_viol, env_viol)
 
 
 class PlannerSearcher(Planner):

@@ -518,6 +518,45 @@ class Robot:
         )
         return pe, re
 
+    def track_paths(self, target_path: torch.Tensor, k: int, n_segments: int = 1, q0: Optional[torch.Tensor] = None,
+                    seed: int = 0, call_index: int = 0, lm_lambda: float = 1e-2, alpha_position: float = 3.5,
+                    alpha_rotation: float = 0.35, n_restart: int = 40, n_track: int = 6, n_random_restarts: int = 0,
+                    tol_pos_m: float = 0.0, tol_rot_rad: float = 0.0, max_jump_rad: float = 0.0, max_jump_m: float = 0.0,
+                    out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:  # fmt: skip
+        """k candidate joint-space paths along `target_path` [T,7] in ONE launch (cppf_track_paths, include/cppflow_hip.h): the path is
+        cut into `n_segments` contiguous segments, each candidate's segment starts fresh (from `q0` [k*n_segments, d], row
+        i*n_segments + s, or a hashed uniform draw of (seed, call_index, candidate, segment)) with `n_restart` LM iterations and tracks
+        the following waypoints warm-started with `n_track`, climbing the recovery ladder (warm continuation, then `n_random_restarts`
+        random restarts) where a row misses the tolerances or a jump bar.  Returns {"x" [k,T,d], "pos_err_m" [k,T], "rot_err_rad"
+        [k,T], "status" [k,T] uint8 (bits _hip.TRACK_*)}; `out` may hold preallocated tensors under those keys."""
+        target = _require_device_tensor(target_path, "target_path")
+        assert target.dim() == 2 and target.shape[1] == 7, tuple(target.shape)
+        T, d, dev = target.shape[0], self.ndof, target.device
+        k, S = int(k), int(n_segments)
+        assert k >= 0 and 1 <= S <= max(T, 1), (k, S, T)
+        if q0 is not None:
+            q0 = _require_device_tensor(q0, "q0")
+            assert tuple(q0.shape) == (k * S, d) and q0.device == dev, (tuple(q0.shape), (k * S, d))
+        res = {} if out is None else dict(out)
+        for name, shape, dtype in (("x", (k, T, d), torch.float32), ("pos_err_m", (k, T), torch.float32),
+                                   ("rot_err_rad", (k, T), torch.float32), ("status", (k, T), torch.uint8)):  # fmt: skip
+            if name in res:
+                res[name] = _require_output_tensor(res[name], name, dtype)
+                assert tuple(res[name].shape) == shape and res[name].device == dev, (name, tuple(res[name].shape))
+            else:
+                res[name] = torch.empty(shape, dtype=dtype, device=dev)
+        prm = _hip.TrackParams(float(lm_lambda), float(alpha_position), float(alpha_rotation), int(n_restart), int(n_track),
+                               int(n_random_restarts), float(tol_pos_m), float(tol_rot_rad), float(max_jump_rad), float(max_jump_m),
+                               int(seed) & 0xFFFFFFFF, int(call_index) & 0xFFFFFFFF)  # fmt: skip
+        _hip.check(
+            _hip.lib().cppf_track_paths(
+                self._handle(dev), target.data_ptr(), T, k, S, ctypes.byref(prm), q0.data_ptr() if q0 is not None else None,
+                res["x"].data_ptr(), res["pos_err_m"].data_ptr(), res["rot_err_rad"].data_ptr(), res["status"].data_ptr(),
+                _stream_ptr(dev),
+            )  # fmt: skip
+        )
+        return res
+
     PLAN_METRIC_FIELDS = ("max_pos_err_cm", "mean_pos_err_cm", "max_rot_err_deg", "mean_rot_err_deg", "mjac_deg", "mjac_cm",
                           "path_length_rad", "path_length_m", "n_joint_limit_violations", "n_self_colliding",
                           "n_env_colliding", "initial_q_norm_dist")  # fmt: skip

@@ -280,6 +280,46 @@ int cppf_env_collision_distances_jacobian(const cppf_robot* robot, const float* 
 int cppf_pose_error_metrics(const cppf_robot* robot, const float* x, const float* target, int S, int W, float* pos_err_m,
                             float* rot_err_rad, void* stream);
 
+/* Tracking IK in one launch: k candidate joint-space paths along ONE target path (the seed stage of a planner).
+ * The path [0, T) is split into S contiguous segments (1 <= S <= T); one lane runs candidate i on segment s and walks the segment's
+ * waypoints in order, keeping q in registers:
+ *   - first waypoint of a segment: start from q0[i*S + s] (q0 [k*S, d], may be NULL) or, without q0, from a uniform draw in
+ *     lo + (hi - lo) * [0.1, 0.9]; n_restart LM iterations;
+ *   - every later waypoint: warm start from the previous waypoint's q; n_track LM iterations.
+ * An LM block of n iterations is exactly a cppf_lm_pose_steps launch of n_steps = n with clamp = 1 and the same tolerances (row shape):
+ * with S = 1, n_random_restarts = 0, no jump bar and the same starts, the result is the chain of per-waypoint launches, in one launch.
+ * Recovery ladder: a row that is not converged (tolerances set; the early-out criterion of cppf_lm_params.tol_*) or whose change from
+ * the previous row exceeds max_jump_rad on a revolute / max_jump_m on a prismatic joint (0 = that bar off) first continues its warm start
+ * up to n_restart iterations in total, then tries up to n_random_restarts fresh random starts of n_restart iterations each, and stops at
+ * the first attempt that is converged (when tolerances are set) and within the jump bars; failing that it keeps the attempt with the lowest
+ * scaled pose error a_pos^2 |e_pos|^2 + a_rot^2 |e_rot|^2.
+ * Outputs (all required): q_out [k, T, d]; pos_err_m / rot_err_rad [k, T] (the definitions of cppf_pose_error_metrics at q_out);
+ * status [k, T], bits CPPF_TRACK_*.  Random draws hash (seed, call_index, candidate, segment, waypoint, attempt): the same arguments give
+ * bit-identical outputs, another call_index other candidates.  A non-finite q0 row poisons every row of its lane (NaN, status 0); a
+ * non-finite target waypoint is written NaN / status 0 by every lane, which carries its q on unchanged. */
+typedef struct cppf_track_params {
+    float lm_lambda;           /* damping, as cppf_lm_params */
+    float alpha_position;      /* as cppf_lm_params */
+    float alpha_rotation;      /* as cppf_lm_params */
+    int32_t n_restart;         /* >= 1: LM iterations from a fresh start (and the warm continuation's total) */
+    int32_t n_track;           /* >= 1: LM iterations from the warm start */
+    int32_t n_random_restarts; /* >= 0: R, random restarts of the recovery ladder */
+    float tol_pos_m;           /* early-out / convergence tolerances: both or neither (0 = off: no convergence test, no early-out) */
+    float tol_rot_rad;
+    float max_jump_rad;        /* >= 0: joint-change bar of revolute joints between consecutive rows (0 = off) */
+    float max_jump_m;          /* >= 0: the same for prismatic joints (0 = off) */
+    uint32_t seed;
+    uint32_t call_index;       /* a planner's rerun counter: another value, other candidates */
+} cppf_track_params;
+
+#define CPPF_TRACK_CONVERGED 1 /* the row meets tol_pos_m / tol_rot_rad */
+#define CPPF_TRACK_RESTARTED 2 /* the row's q comes from a fresh start: the first row of a segment or a random restart */
+#define CPPF_TRACK_JUMP 4      /* the row's change from the previous row exceeds a jump bar */
+#define CPPF_TRACK_RECOVERED 8 /* the row's q comes from the continued warm start of the ladder */
+
+int cppf_track_paths(const cppf_robot* robot, const float* target, int T, int k, int S, const cppf_track_params* params,
+                     const float* q0, float* q_out, float* pos_err_m, float* rot_err_rad, uint8_t* status, void* stream);
+
 /* Validity half of x_is_valid for every seed (cppflow/optimization_utils.py:845-884, evaluation_utils.py:29-75):
  * out [S,4] = max position error (cm), max rotation error (deg), max |revolute joint change| (deg),
  * max |prismatic joint change| (cm) over the seed's W waypoints. */
