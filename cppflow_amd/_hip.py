@@ -117,6 +117,50 @@ class FullParams(ctypes.Structure):
         ("differencing_scale_down", _f), ("differencing_shift_invalid_to_threshold", _i32)]  # fmt: skip
 
 
+OPT_MODE_POSE, OPT_MODE_DIFF, OPT_MODE_DONE = 0, 1, 2  # CPPF_OPT_MODE_*
+OPT_ON_POSE_VALID = {"differencing": 0, "stop": 1, "continue": 2}  # CPPF_OPT_ON_POSE_VALID_*
+
+
+class OptloopRecord(ctypes.Structure):
+    """struct cppf_optloop_record (16 words; cppf_lm_optimize_enqueue's loop-control block starts with C of these)"""
+
+    _fields_ = [("mode", _i32), ("pose_pos_valid", _i32), ("pose_rot_valid", _i32), ("converged", _i32), ("last_valid_idx", _i32),
+                ("n_steps", _i32), ("has_tl", _i32), ("last_tl", _f), ("is_valid", _i32), ("valid_seed_idx", _i32), ("i_final", _i32),
+                ("reserved", _i32 * 5)]  # fmt: skip
+
+
+class OptloopTrace(ctypes.Structure):
+    """struct cppf_optloop_trace"""
+
+    _fields_ = [("mode", _i32), ("tl", _f), ("flags", _i32), ("valid", _i32)]
+
+
+class OptloopParams(ctypes.Structure):
+    """struct cppf_optloop_params"""
+
+    _fields_ = [("pose_lm_lambda", _f), ("pose_alpha_position", _f), ("pose_alpha_rotation", _f), ("diff", FullParams),
+                ("constraints", Constraints), ("max_n_steps", _i32), ("return_if_valid_after_n_steps", _i32), ("on_pose_valid", _i32),
+                ("per_trajectory", _i32), ("trace_capacity", _i32), ("reserved", _i32), ("convergence_threshold", ctypes.c_double)]  # fmt: skip
+
+
+def optloop_initial_control(n_records: int, trace_capacity: int) -> np.ndarray:
+    """The loop-control block as the caller hands it to cppf_lm_optimize_enqueue (int32 words): every record leads with a pose step
+    (pose_pos_valid = 1, pose_rot_valid = 0, last_valid_idx = -1), the trace is zero."""
+    words = np.zeros(n_records * 16 + n_records * trace_capacity * 4, dtype=np.int32)
+    rec = words[: n_records * 16].reshape(n_records, 16)
+    rec[:, 0], rec[:, 1], rec[:, 2], rec[:, 4] = OPT_MODE_POSE, 1, 0, -1
+    return words
+
+
+def optloop_flags(word: int):
+    """cppf_optloop_trace.flags -> the six flags of x_is_valid (collision flags None / False / True), or None when the iteration ended
+    before validity was evaluated."""
+    if word < 0:
+        return None
+    tri = {0: None, 1: False, 2: True}
+    return (bool(word & 1), bool(word & 2), bool(word & 4), bool(word & 8), tri[(word >> 4) & 3], tri[(word >> 6) & 3])
+
+
 class LmOutputs(ctypes.Structure):
     """struct cppf_lm_outputs (device pointers; 0 = not requested)"""
 
@@ -197,6 +241,12 @@ SIGNATURES = {
     "cppf_lm_full_step": (
         ctypes.c_int,
         [_vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(FullParams), _vp, _vp, _vp, _vp, _vp],
+    ),
+    "cppf_lm_optimize_workspace_bytes": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
+    "cppf_lm_optimize_control_bytes": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(OptloopParams), ctypes.POINTER(ctypes.c_size_t)]),
+    "cppf_lm_optimize_enqueue": (
+        ctypes.c_int,
+        [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(OptloopParams), _vp, _vp, ctypes.c_int, _vp],
     ),
     "cppf_comm_available": (ctypes.c_int, []),
     "cppf_comm_unique_id": (ctypes.c_int, [_vp]),

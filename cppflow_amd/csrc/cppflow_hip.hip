@@ -63,6 +63,7 @@ constexpr int kBlock = CPPF_BLOCK;
 #include "kernels_eval.h"
 #include "kernels_coupled.h"
 #include "kernels_dp.h"
+#include "kernels_optloop.h"
 
 // ---- host side --------------------------------------------------------------------------------------------------------------
 
@@ -752,6 +753,59 @@ int launch_fused_rows(const cppf_robot* robot, int coll, size_t n_rows, unsigned
     return check_launch(robot);
 }
 
+// One launch of the quad-shape kernel (kernels_quad.h) over n rows; `gate` = { NULL } unless the optimiser loop on the device asks
+int launch_quad(const cppf_robot* robot, bool coll, size_t n, hipStream_t st, const LmK& prm, const float* x_in, const float* target,
+                const cppf_lm_outputs& oq, const StepGateK gate) {
+        const unsigned grid = (unsigned)((n + kQuadRows - 1) / kQuadRows);
+        const size_t lds_q = coll ? sizeof(float) * (4 * (CPPF_MAX_PAIRS + CPPF_MAX_CAPSULES) +
+                                                     (size_t)kQuadRows * quad_row_stride(robot->coll.ncaps))
+                                  : 0;
+        const uint4* tab = static_cast<const uint4*>(robot->d_quad);
+        const bool mfma = tune(robot, CPPF_TUNE_QUAD_MFMA) && robot->static_id >= 0 && !tune(robot, CPPF_TUNE_FORCE_GENERIC);
+        if (use_rtc(robot) && robot->rtc->fn[RTC_QUAD0]) {
+            void* args[] = {(void*)&robot->chain, (void*)&robot->coll, (void*)&prm, (void*)&x_in, (void*)&target, (void*)&oq, (void*)&tab, (void*)&gate};
+            if (int rc = rtc_launch(robot, coll ? RTC_QUAD1 : RTC_QUAD0, grid, lds_q, st, args)) return rc;
+        } else {
+#define CPPF_BODY                                                                                                          \
+    if constexpr (RB::D >= 6) {                                                                                            \
+        if (coll) {                                                                                                        \
+            if constexpr (RB::kStatic) {                                                                                   \
+                if (mfma)                                                                                                  \
+                    hipLaunchKernelGGL((lm_quad_kernel<RB, 1, true>), dim3(grid), dim3(kBlock), lds_q, st, robot->chain,    \
+                                       robot->coll, prm, x_in, target, oq, tab, gate);                                           \
+                else                                                                                                       \
+                    hipLaunchKernelGGL((lm_quad_kernel<RB, 1, false>), dim3(grid), dim3(kBlock), lds_q, st, robot->chain,   \
+                                       robot->coll, prm, x_in, target, oq, tab, gate);                                           \
+            } else {                                                                                                       \
+                hipLaunchKernelGGL((lm_quad_kernel<RB, 1, false>), dim3(grid), dim3(kBlock), lds_q, st, robot->chain,       \
+                                   robot->coll, prm, x_in, target, oq, tab, gate);                                               \
+            }                                                                                                              \
+        } else {                                                                                                           \
+            if constexpr (RB::kStatic) {                                                                                   \
+                if (mfma)                                                                                                  \
+                    hipLaunchKernelGGL((lm_quad_kernel<RB, 0, true>), dim3(grid), dim3(kBlock), 0, st, robot->chain,        \
+                                       robot->coll, prm, x_in, target, oq, tab, gate);                                           \
+                else                                                                                                       \
+                    hipLaunchKernelGGL((lm_quad_kernel<RB, 0, false>), dim3(grid), dim3(kBlock), 0, st, robot->chain,       \
+                                       robot->coll, prm, x_in, target, oq, tab, gate);                                           \
+            } else {                                                                                                       \
+                hipLaunchKernelGGL((lm_quad_kernel<RB, 0, false>), dim3(grid), dim3(kBlock), 0, st, robot->chain,           \
+                                   robot->coll, prm, x_in, target, oq, tab, gate);                                               \
+            }                                                                                                              \
+        }                                                                                                                  \
+    }
+        CPPF_DISPATCH_RB(robot)
+#undef CPPF_BODY
+        }
+    return CPPF_OK;
+}
+
+inline bool quad_possible(const cppf_robot* robot, const cppf_lm_outputs& out) {
+    return robot->desc.ndof >= 6 && !out.J_out && !out.e_out && !out.min_self && !out.min_env &&
+           (!out.seed_summary || (out.x_out && out.pos_err_m && out.rot_err_rad && out.self_mask && out.env_mask && out.jlim_mask &&
+                                  out.ext_cost));
+}
+
 }  // namespace
 
 // A batched fused launch (cppflow_hip.h): the item descriptors live in a device table the batch object owns.
@@ -795,10 +849,7 @@ int cppf_lm_pose_steps(const cppf_robot* robot, const float* x_in, const float* 
         outk.seed_summary = nullptr;
     }
     // kernel shape: four lanes per row for batches that cannot fill the chip (kernels_quad.h), one row per lane otherwise
-    const int d = robot->desc.ndof;
-    const bool quad_can = d >= 6 && !out->J_out && !out->e_out && !out->min_self && !out->min_env &&
-                          (!out->seed_summary || (out->x_out && out->pos_err_m && out->rot_err_rad && out->self_mask &&
-                                                  out->env_mask && out->jlim_mask && out->ext_cost));
+    const bool quad_can = quad_possible(robot, *out);
     CPPF_REQUIRE(params->shape != CPPF_SHAPE_QUAD || quad_can,
                  "CPPF_SHAPE_QUAD needs ndof >= 6, no J_out / e_out / min_self / min_env, and (with seed_summary) every per-row output");
     // AUTO: the quad shape when the batch is at most one of its wavefronts per SIMD AND no per-seed summary is asked for (in
@@ -809,47 +860,7 @@ int cppf_lm_pose_steps(const cppf_robot* robot, const float* x_in, const float* 
     if (quad) {
         cppf_lm_outputs oq = *out;
         oq.seed_summary = nullptr;  // rows of a seed span several workgroups in this shape: the reduction kernel follows
-        const unsigned grid = (unsigned)((n + kQuadRows - 1) / kQuadRows);
-        const size_t lds_q = coll ? sizeof(float) * (4 * (CPPF_MAX_PAIRS + CPPF_MAX_CAPSULES) +
-                                                     (size_t)kQuadRows * quad_row_stride(robot->coll.ncaps))
-                                  : 0;
-        const uint4* tab = static_cast<const uint4*>(robot->d_quad);
-        const bool mfma = tune(robot, CPPF_TUNE_QUAD_MFMA) && robot->static_id >= 0 && !tune(robot, CPPF_TUNE_FORCE_GENERIC);
-        if (use_rtc(robot) && robot->rtc->fn[RTC_QUAD0]) {
-            void* args[] = {(void*)&robot->chain, (void*)&robot->coll, (void*)&prm, (void*)&x_in, (void*)&target, (void*)&oq, (void*)&tab};
-            if (int rc = rtc_launch(robot, coll ? RTC_QUAD1 : RTC_QUAD0, grid, lds_q, st, args)) return rc;
-        } else {
-#define CPPF_BODY                                                                                                          \
-    if constexpr (RB::D >= 6) {                                                                                            \
-        if (coll) {                                                                                                        \
-            if constexpr (RB::kStatic) {                                                                                   \
-                if (mfma)                                                                                                  \
-                    hipLaunchKernelGGL((lm_quad_kernel<RB, 1, true>), dim3(grid), dim3(kBlock), lds_q, st, robot->chain,    \
-                                       robot->coll, prm, x_in, target, oq, tab);                                           \
-                else                                                                                                       \
-                    hipLaunchKernelGGL((lm_quad_kernel<RB, 1, false>), dim3(grid), dim3(kBlock), lds_q, st, robot->chain,   \
-                                       robot->coll, prm, x_in, target, oq, tab);                                           \
-            } else {                                                                                                       \
-                hipLaunchKernelGGL((lm_quad_kernel<RB, 1, false>), dim3(grid), dim3(kBlock), lds_q, st, robot->chain,       \
-                                   robot->coll, prm, x_in, target, oq, tab);                                               \
-            }                                                                                                              \
-        } else {                                                                                                           \
-            if constexpr (RB::kStatic) {                                                                                   \
-                if (mfma)                                                                                                  \
-                    hipLaunchKernelGGL((lm_quad_kernel<RB, 0, true>), dim3(grid), dim3(kBlock), 0, st, robot->chain,        \
-                                       robot->coll, prm, x_in, target, oq, tab);                                           \
-                else                                                                                                       \
-                    hipLaunchKernelGGL((lm_quad_kernel<RB, 0, false>), dim3(grid), dim3(kBlock), 0, st, robot->chain,       \
-                                       robot->coll, prm, x_in, target, oq, tab);                                           \
-            } else {                                                                                                       \
-                hipLaunchKernelGGL((lm_quad_kernel<RB, 0, false>), dim3(grid), dim3(kBlock), 0, st, robot->chain,           \
-                                   robot->coll, prm, x_in, target, oq, tab);                                               \
-            }                                                                                                              \
-        }                                                                                                                  \
-    }
-        CPPF_DISPATCH_RB(robot)
-#undef CPPF_BODY
-        }
+        if (int rc = launch_quad(robot, coll, n, st, prm, x_in, target, oq, StepGateK{nullptr, 0, 0u})) return rc;
         if (int rc = check_launch(robot)) return rc;
         if (summary_dst)
             return cppf_seed_summary(robot, oq.x_out, S, W, oq.ext_cost, oq.pos_err_m, oq.rot_err_rad, oq.self_mask, oq.env_mask,
@@ -953,8 +964,29 @@ void cppf_lm_batch_destroy(cppf_lm_batch* batch) {
     if (robot->life.fetch_sub(1u, std::memory_order_acq_rel) == (kRobotDead | 1u)) robot_free(robot);
 }
 
+}  // extern "C"
+
+namespace {
+int collision_masks_gated(const cppf_robot* robot, const float* q, int S, int W, uint8_t* self_mask, uint8_t* env_mask,
+                          uint8_t* jlim_mask, float* ext_cost, float* min_self, float* min_env, void* stream, const StepGateK gate);
+int lm_full_step_gated(const cppf_robot* robot, const float* x_in, const float* target, const float* virtual_configs, int S, int W,
+                       const cppf_full_params* params, float* work_blocks, float* work_G, float* work_y, float* x_out, void* stream,
+                       const StepGateK gate);
+}  // namespace
+
+extern "C" {
+
 int cppf_collision_masks(const cppf_robot* robot, const float* q, int S, int W, uint8_t* self_mask, uint8_t* env_mask,
                          uint8_t* jlim_mask, float* ext_cost, float* min_self, float* min_env, void* stream) {
+    return collision_masks_gated(robot, q, S, W, self_mask, env_mask, jlim_mask, ext_cost, min_self, min_env, stream,
+                                 StepGateK{nullptr, 0, 0u});
+}
+
+}  // extern "C"
+
+namespace {
+int collision_masks_gated(const cppf_robot* robot, const float* q, int S, int W, uint8_t* self_mask, uint8_t* env_mask,
+                          uint8_t* jlim_mask, float* ext_cost, float* min_self, float* min_env, void* stream, const StepGateK gate) {
     CPPF_ENTER(robot);
     CPPF_REQUIRE(S >= 0 && W >= 0, "S / W < 0");
     const size_t n = (size_t)S * W;
@@ -966,24 +998,27 @@ int cppf_collision_masks(const cppf_robot* robot, const float* q, int S, int W, 
     if (use_rtc(robot)) {
         int n_i = (int)n;
         void* args[] = {(void*)&robot->chain, (void*)&robot->coll, (void*)&n_i, (void*)&q, (void*)&self_mask, (void*)&env_mask,
-                        (void*)&jlim_mask, (void*)&ext_cost, (void*)&min_self, (void*)&min_env};
+                        (void*)&jlim_mask, (void*)&ext_cost, (void*)&min_self, (void*)&min_env, (void*)&gate, (void*)&W};
         return rtc_launch(robot, (min_self || min_env) ? RTC_COLL_MIN : RTC_COLL_MASK, grid_for(n), 0, st, args);
     }
     if (min_self || min_env) {
 #define CPPF_BODY                                                                                                    \
     hipLaunchKernelGGL((collision_kernel<RB, true>), dim3(grid_for(n)), dim3(kBlock), lds, st, robot->chain, robot->coll, \
-                       (int)n, q, self_mask, env_mask, jlim_mask, ext_cost, min_self, min_env)
+                       (int)n, q, self_mask, env_mask, jlim_mask, ext_cost, min_self, min_env, gate, W)
         CPPF_DISPATCH_RB(robot)
 #undef CPPF_BODY
     } else {
 #define CPPF_BODY                                                                                                     \
     hipLaunchKernelGGL((collision_kernel<RB, false>), dim3(grid_for(n)), dim3(kBlock), lds, st, robot->chain, robot->coll, \
-                       (int)n, q, self_mask, env_mask, jlim_mask, ext_cost, min_self, min_env)
+                       (int)n, q, self_mask, env_mask, jlim_mask, ext_cost, min_self, min_env, gate, W)
         CPPF_DISPATCH_RB(robot)
 #undef CPPF_BODY
     }
     return check_launch(robot);
 }
+}  // namespace
+
+extern "C" {
 
 int cppf_self_collision_distances(const cppf_robot* robot, const float* x, int n, float* dists, void* stream) {
     CPPF_ENTER(robot);
@@ -1189,6 +1224,17 @@ int cppf_plan_metrics(const cppf_robot* robot, const float* x, const float* targ
 int cppf_lm_full_step(const cppf_robot* robot, const float* x_in, const float* target, const float* virtual_configs, int S,
                       int W, const cppf_full_params* params, float* work_blocks, float* work_G, float* work_y,
                       float* x_out, void* stream) {
+    return lm_full_step_gated(robot, x_in, target, virtual_configs, S, W, params, work_blocks, work_G, work_y, x_out, stream,
+                              StepGateK{nullptr, 0, 0u});
+}
+
+}  // extern "C"
+
+namespace {
+// cppf_lm_full_step; with a gate (the optimiser loop on the device) only the trajectories it opens are stepped
+int lm_full_step_gated(const cppf_robot* robot, const float* x_in, const float* target, const float* virtual_configs, int S, int W,
+                       const cppf_full_params* params, float* work_blocks, float* work_G, float* work_y, float* x_out, void* stream,
+                       const StepGateK gate) {
     CPPF_ENTER(robot);
     CPPF_REQUIRE(params, "params is NULL");
     CPPF_REQUIRE(S >= 0 && W >= 1, "S < 0 or W < 1");
@@ -1247,14 +1293,17 @@ int cppf_lm_full_step(const cppf_robot* robot, const float* x_in, const float* t
     const bool use_rows = !var_coupling && !use_pcr && (!prm.use_pose || g_rows_pose) && g_full_rows && robot->desc.ndof >= 3 &&
                           robot->desc.ndof <= 12 && W <= (1 << 19);
     prm.fold = use_rows || var_coupling;
+    if (gate.ctl != nullptr && !use_pcr && !use_rows)
+        return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: the device-side optimiser loop gates the parallel-in-time and the row-per-lane "
+                                          "elimination only (no pose block, no individually weighted differencing rows, CPPF_TUNE_FULL_ROWS on)");
     hipStream_t st = (hipStream_t)stream;
 #define CPPF_BODY                                                                                                     \
     if (n >= 131072)                                                                                                  \
         hipLaunchKernelGGL((full_blocks_kernel<RB, full_blocks_occ<RB>()>), dim3(grid_for(n)), dim3(kBlock), robot->lds_bytes, st, \
-                           robot->chain, robot->coll, prm, x_in, target, virtual_configs, work_blocks, w2next);      \
+                           robot->chain, robot->coll, prm, x_in, target, virtual_configs, work_blocks, w2next, gate); \
     else                                                                                                              \
         hipLaunchKernelGGL((full_blocks_kernel<RB>), dim3(grid_for(n)), dim3(kBlock), robot->lds_bytes, st, robot->chain, \
-                           robot->coll, prm, x_in, target, virtual_configs, work_blocks, w2next)
+                           robot->coll, prm, x_in, target, virtual_configs, work_blocks, w2next, gate)
     CPPF_DISPATCH_RB(robot)
 #undef CPPF_BODY
     // Trajectories are eliminated one per wavefront (8 x 8 lane tile) up to 8 joints, one per lane beyond.  With the pose
@@ -1280,16 +1329,16 @@ int cppf_lm_full_step(const cppf_robot* robot, const float* x_in, const float* t
                 CPPF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&full_solve_pcr_kernel<DD, 512, true, true>), \
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kState));                \
                 hipLaunchKernelGGL((full_solve_pcr_kernel<DD, 512, true, true>), dim3((unsigned)S), dim3(512), kState, st, \
-                                   robot->chain, prm, x_in, virtual_configs, work_blocks, work_G, x_out);              \
+                                   robot->chain, prm, x_in, virtual_configs, work_blocks, work_G, x_out, gate);              \
             } else                                                                                                     \
             hipLaunchKernelGGL((full_solve_pcr_kernel<DD, 256, true>), dim3((unsigned)S), dim3(256), kState, st,        \
-                               robot->chain, prm, x_in, virtual_configs, work_blocks, work_G, x_out);                  \
+                               robot->chain, prm, x_in, virtual_configs, work_blocks, work_G, x_out, gate);                  \
         } else if (W <= 256)                                                                                           \
             hipLaunchKernelGGL((full_solve_pcr_kernel<DD, 256>), dim3((unsigned)S), dim3(256), 0, st, robot->chain, prm, \
-                               x_in, virtual_configs, work_blocks, work_G, x_out);                                     \
+                               x_in, virtual_configs, work_blocks, work_G, x_out, gate);                                     \
         else                                                                                                           \
             hipLaunchKernelGGL((full_solve_pcr_kernel<DD, 512>), dim3((unsigned)S), dim3(512), 0, st, robot->chain, prm, \
-                               x_in, virtual_configs, work_blocks, work_G, x_out);                                     \
+                               x_in, virtual_configs, work_blocks, work_G, x_out, gate);                                     \
         break;
             CPPF_PCR_CASE(3) CPPF_PCR_CASE(4) CPPF_PCR_CASE(5) CPPF_PCR_CASE(6) CPPF_PCR_CASE(7) CPPF_PCR_CASE(8)
 #undef CPPF_PCR_CASE
@@ -1315,9 +1364,9 @@ int cppf_lm_full_step(const cppf_robot* robot, const float* x_in, const float* t
                                              hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));                   \
             }                                                                                                           \
             hipLaunchKernelGGL((full_rows_eliminate_kernel<DD>), dim3(rows_wgs), dim3(64), rows_lds, st, prm,           \
-                               robot->chain.pris_mask, work_blocks, work_G, work_y);                                    \
+                               robot->chain.pris_mask, work_blocks, work_G, work_y, gate);                                    \
             hipLaunchKernelGGL((full_rows_substitute_kernel<DD>), dim3(rows_wgs), dim3(64), rows_lds, st, prm,          \
-                               robot->chain.pris_mask, x_in, work_blocks, work_G, work_y, x_out);                       \
+                               robot->chain.pris_mask, x_in, work_blocks, work_G, work_y, x_out, gate);                       \
         } else                                                                                                          \
             hipLaunchKernelGGL((full_solve_wave_kernel<DD>), dim3((unsigned)S), dim3(64), 0, st, robot->chain, prm,      \
                                x_in, virtual_configs, work_blocks, work_G, work_y, x_out);                              \
@@ -1334,9 +1383,9 @@ int cppf_lm_full_step(const cppf_robot* robot, const float* x_in, const float* t
                                              hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));                   \
             }                                                                                                           \
             hipLaunchKernelGGL((full_rows_eliminate_kernel<DD>), dim3(rows_wgs), dim3(64), rows_lds, st, prm,           \
-                               robot->chain.pris_mask, work_blocks, work_G, work_y);                                    \
+                               robot->chain.pris_mask, work_blocks, work_G, work_y, gate);                                    \
             hipLaunchKernelGGL((full_rows_substitute_kernel<DD>), dim3(rows_wgs), dim3(64), rows_lds, st, prm,          \
-                               robot->chain.pris_mask, x_in, work_blocks, work_G, work_y, x_out);                       \
+                               robot->chain.pris_mask, x_in, work_blocks, work_G, work_y, x_out, gate);                       \
         } else                                                                                                          \
             hipLaunchKernelGGL((full_solve_kernel<DD>), dim3((unsigned)((S + 63) / 64)), dim3(64), 0, st, robot->chain, \
                                prm, x_in, virtual_configs, work_blocks, work_G, work_y, x_out, nullptr);                \
@@ -1350,6 +1399,124 @@ int cppf_lm_full_step(const cppf_robot* robot, const float* x_in, const float* t
                                                x_out, nullptr));
     }
     return check_launch(robot);
+}
+
+// workspace of cppf_lm_optimize_enqueue, in floats (every section a multiple of 4 floats): snapshot | x_new | blocks | G | y |
+// metrics [S,16] | self mask | env mask (one byte per row each)
+struct OptloopLayout {
+    size_t snapshot, x_new, blocks, G, y, metrics, self_mask, env_mask, total;
+};
+OptloopLayout optloop_layout(int d, size_t S, size_t W) {
+    auto up = [](size_t v) { return (v + 3) & ~(size_t)3; };
+    const size_t n = S * W, nt = (size_t)d * (d + 1) / 2;
+    OptloopLayout L;
+    L.snapshot = 0;
+    L.x_new = L.snapshot + up(n * d);
+    L.blocks = L.x_new + up(n * d);
+    L.G = L.blocks + up(n * (nt + d));
+    L.y = L.G + up(n * d * d);
+    L.metrics = L.y + up(n * d);
+    L.self_mask = L.metrics + up(S * 16);
+    L.env_mask = L.self_mask + up((n + 3) / 4);
+    L.total = L.env_mask + up((n + 3) / 4);
+    return L;
+}
+}  // namespace
+
+extern "C" {
+
+int cppf_lm_optimize_workspace_bytes(const cppf_robot* robot, int S, int W, size_t* bytes) {
+    CPPF_REQUIRE(robot != nullptr, "robot handle is NULL");
+    CPPF_REQUIRE(!(robot->life.load(std::memory_order_acquire) & kRobotDead), "the robot handle was destroyed");
+    CPPF_REQUIRE(bytes, "bytes is NULL");
+    CPPF_REQUIRE(S >= 1 && W >= 1 && (size_t)S * W <= 0x7fffffffu, "S / W must be >= 1 and S*W at most 2^31-1");
+    *bytes = optloop_layout(robot->desc.ndof, (size_t)S, (size_t)W).total * sizeof(float);
+    return CPPF_OK;
+}
+
+int cppf_lm_optimize_control_bytes(int S, const cppf_optloop_params* params, size_t* bytes) {
+    CPPF_REQUIRE(params && bytes, "params / bytes is NULL");
+    CPPF_REQUIRE(S >= 1, "S must be >= 1");
+    CPPF_REQUIRE(params->trace_capacity >= 0, "trace_capacity must be >= 0");
+    *bytes = optloop_control_words(S, *params) * 4;
+    return CPPF_OK;
+}
+
+int cppf_lm_optimize_enqueue(const cppf_robot* robot, float* x, const float* target, int S, int W,
+                             const cppf_optloop_params* params, void* workspace, int32_t* control, int n_iterations,
+                             void* stream) {
+    // every argument is checked before the device is selected (CPPF_ENTER), so that the checks hold for a host-only handle too
+    CPPF_REQUIRE(robot != nullptr, "robot handle is NULL");
+    CPPF_REQUIRE(!(robot->life.load(std::memory_order_acquire) & kRobotDead), "the robot handle was destroyed");
+    CPPF_REQUIRE(params, "params is NULL");
+    CPPF_REQUIRE(S >= 1 && W >= 1, "S / W must be >= 1");
+    CPPF_REQUIRE((size_t)S * W <= 0x7fffffffu, "S*W exceeds 2^31-1 rows");
+    CPPF_REQUIRE(n_iterations >= 0, "n_iterations < 0");
+    CPPF_REQUIRE(params->max_n_steps >= 1, "max_n_steps must be >= 1");
+    CPPF_REQUIRE(params->return_if_valid_after_n_steps >= -1, "return_if_valid_after_n_steps must be >= 0, or -1 for none");
+    CPPF_REQUIRE(params->on_pose_valid >= 0 && params->on_pose_valid <= 2, "on_pose_valid must be one of CPPF_OPT_ON_POSE_VALID_*");
+    CPPF_REQUIRE(params->per_trajectory == 0 || params->per_trajectory == 1, "per_trajectory must be 0 or 1");
+    CPPF_REQUIRE(params->trace_capacity >= 0, "trace_capacity must be >= 0");
+    CPPF_REQUIRE(params->convergence_threshold >= 0.0, "convergence_threshold must be >= 0");
+    CPPF_REQUIRE(params->diff.lm_lambda > 0.f, "diff.lm_lambda must be > 0");
+    CPPF_REQUIRE(!params->diff.use_virtual_configs || (params->diff.n_virtual_configs > 0 && 2 * params->diff.n_virtual_configs < W),
+                 "2 * n_virtual_configs must be < number of waypoints (optimization_utils.py:449-451)");
+    cppf_lm_params lp = {};
+    lp.lm_lambda = params->pose_lm_lambda;
+    lp.alpha_position = params->pose_alpha_position;
+    lp.alpha_rotation = params->pose_alpha_rotation;
+    lp.n_steps = 1;
+    lp.clamp = 0;
+    lp.shape = CPPF_SHAPE_AUTO;
+    lp.solver = CPPF_SOLVER_AUTO;
+    LmK prm;
+    if (int rc = make_lm_kernel_params(robot, &lp, prm)) return rc;
+    CPPF_REQUIRE(x && target && workspace && control, "x / target / workspace / control is NULL");
+    CPPF_REQUIRE(((uintptr_t)workspace & 15u) == 0 && ((uintptr_t)control & 3u) == 0, "workspace must be 16-byte, control 4-byte aligned");
+    const int d = robot->desc.ndof;
+    const size_t n = (size_t)S * W;
+    // the gated steps are the kernels the host loop's launches resolve to at these sizes (same instructions, same bits)
+    if (use_rtc(robot))
+        return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: the device-side optimiser loop runs the compiled-in kernels; this handle was specialised at run time");
+    if (d < 6 || n > (size_t)tune(robot, CPPF_TUNE_QUAD_MAX_ROWS))
+        return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: the device-side optimiser loop needs the quad-shape pose step (ndof >= 6, S*W within its row limit)");
+    if (params->diff.use_pose || params->diff.differencing_mode != 0)
+        return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: the device-side optimiser loop takes a coupled step without pose block and without weighted differencing rows");
+    if (n_iterations == 0) return CPPF_OK;
+    CPPF_ENTER(robot);
+    prm.n = (int)n;
+    prm.W = W;
+    hipStream_t st = (hipStream_t)stream;
+    const OptloopLayout L = optloop_layout(d, (size_t)S, (size_t)W);
+    float* const ws = static_cast<float*>(workspace);
+    float* const x_new = ws + L.x_new;
+    float* const metrics = ws + L.metrics;
+    const bool want_masks = !(params->constraints.self_collisions_ignored && params->constraints.env_collisions_ignored);
+    uint8_t* const self_m = reinterpret_cast<uint8_t*>(ws + L.self_mask);
+    uint8_t* const env_m = reinterpret_cast<uint8_t*>(ws + L.env_mask);
+    const StepGateK g_pose{control, params->per_trajectory, 1u << CPPF_OPT_MODE_POSE};
+    const StepGateK g_diff{control, params->per_trajectory, 1u << CPPF_OPT_MODE_DIFF};
+    const StepGateK g_live{control, params->per_trajectory, (1u << CPPF_OPT_MODE_POSE) | (1u << CPPF_OPT_MODE_DIFF)};
+    cppf_lm_outputs oq;
+    std::memset(&oq, 0, sizeof oq);
+    oq.x_out = x_new;
+    const int C = params->per_trajectory ? S : 1;
+    const size_t total = n * (size_t)d;
+    for (int it = 0; it < n_iterations; ++it) {
+        if (int rc = launch_quad(robot, false, n, st, prm, x, target, oq, g_pose)) return rc;
+        if (int rc = lm_full_step_gated(robot, x, target, x, S, W, &params->diff, ws + L.blocks, ws + L.G, ws + L.y, x_new, stream, g_diff))
+            return rc;
+        hipLaunchKernelGGL(optloop_clamp_kernel, dim3(grid_for(total)), dim3(kBlock), 0, st, robot->chain, total, W, x_new, x, g_live);
+        if (want_masks)
+            if (int rc = collision_masks_gated(robot, x, S, W, self_m, env_m, nullptr, nullptr, nullptr, nullptr, stream, g_live)) return rc;
+        const uint8_t* const sm = params->constraints.self_collisions_ignored ? nullptr : self_m;
+        const uint8_t* const em = params->constraints.env_collisions_ignored ? nullptr : env_m;
+        CPPF_DISPATCH_D(d, hipLaunchKernelGGL((optloop_metrics_kernel<D>), dim3(S), dim3(64), 0, st, robot->chain, robot->coll, S, W, x,
+                                              target, sm, em, metrics, g_live));
+        hipLaunchKernelGGL(optloop_decide_kernel, dim3(C), dim3(64), 0, st, *params, S, W, d, metrics, x, ws + L.snapshot, control);
+        if (int rc = check_launch(robot)) return rc;
+    }
+    return CPPF_OK;
 }
 
 int cppf_mjacs(const cppf_robot* robot, const float* q, int k, int T, float prismatic_scaling, float* mjacs, void* stream) {

@@ -280,7 +280,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(OCC ? OC
                                                              const float* __restrict__ x,
                                                              const float* __restrict__ target,
                                                              const float* __restrict__ xv, float* __restrict__ blocks,
-                                                             float* __restrict__ w2next) {
+                                                             float* __restrict__ w2next, const StepGateK gate) {
     extern __shared__ float lds[];
     constexpr int D = RB::D;
     constexpr int NT = D * (D + 1) / 2;
@@ -289,6 +289,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(OCC ? OC
     const size_t row = (size_t)blockIdx.x * kBlock + tid;
     const size_t n = (size_t)prm.S * prm.W;
     if (row >= n) return;
+    if (gate.ctl != nullptr && !step_open(gate, (int)(row / (size_t)prm.W))) return;  // like the tail rows: before any wavefront-wide vote
     float q[D];
     load_x<D>(x, row, q);
     unsigned long long near_self = ~0ull, near_env = ~0ull;  // wavefront-uniform
@@ -870,6 +871,18 @@ __device__ __forceinline__ RowsLane<D> rows_lane(const FullK& prm, uint32_t pris
     return L;
 }
 
+// Gated launch (the optimiser loop on the device): the lanes of a trajectory whose mode does not ask for the coupled step become
+// idle ones (they work on whatever the workspace holds and store nothing); true if the wavefront has no open trajectory at all --
+// the caller returns then, all 64 lanes together.
+template <int D>
+__device__ __forceinline__ bool rows_gate(const StepGateK& gate, const FullK& prm, int wave, int lane, RowsLane<D>& L) {
+    if (gate.ctl == nullptr) return false;
+    constexpr int GW = kRowsGW<D>, TPW = 64 / GW;
+    const int s_raw = wave * TPW + lane / GW;
+    L.live = L.live && step_open(gate, s_raw < prm.S ? s_raw : prm.S - 1);
+    return __builtin_amdgcn_ballot_w64(L.live) == 0ull;
+}
+
 // A -= E G E (this lane's row) and the return value  (G v)_r  for the vector v held one component per lane
 template <int D>
 __device__ __forceinline__ float rows_couple(const RowsLane<D>& L, const float (&G)[D], float v, float (&A)[kRowsGW<D>]) {
@@ -889,14 +902,15 @@ __device__ __forceinline__ float rows_couple(const RowsLane<D>& L, const float (
 template <int D>
 __global__ __launch_bounds__(64) void full_rows_eliminate_kernel(const FullK prm, const uint32_t pris_mask,
                                                                  const float* __restrict__ blocks, float* __restrict__ workG,
-                                                                 float* __restrict__ worky) {
+                                                                 float* __restrict__ worky, const StepGateK gate) {
     static_assert(D <= 16, "one row of the padded block per lane: 8 or 16 lanes per trajectory");
     constexpr int NT = D * (D + 1) / 2, STRIDE = NT + D;
     const int wave = blockIdx.x >> 1, dir = blockIdx.x & 1;
     const int T = prm.W, m = T / 2;
     const int start = dir ? T - 1 : 0, sgn = dir ? -1 : 1, len = dir ? T - 1 - m : m;  // waypoint of step tau: start + sgn tau
     if (len <= 0) return;
-    const RowsLane<D> L = rows_lane<D>(prm, pris_mask, wave, threadIdx.x);
+    RowsLane<D> L = rows_lane<D>(prm, pris_mask, wave, threadIdx.x);
+    if (rows_gate<D>(gate, prm, wave, threadIdx.x, L)) return;
     const float* blk = blocks + L.ubase * STRIDE;
     float* gw = workG + L.ubase * (D * D);
     float* yw = worky + L.ubase * D;
@@ -964,12 +978,14 @@ template <int D>
 __global__ __launch_bounds__(64) void full_rows_substitute_kernel(const FullK prm, const uint32_t pris_mask,
                                                                   const float* __restrict__ x, const float* __restrict__ blocks,
                                                                   const float* __restrict__ workG,
-                                                                  const float* __restrict__ worky, float* __restrict__ x_out) {
+                                                                  const float* __restrict__ worky, float* __restrict__ x_out,
+                                                                  const StepGateK gate) {
     constexpr int NT = D * (D + 1) / 2, STRIDE = NT + D;
     const int wave = blockIdx.x >> 1, dir = blockIdx.x & 1;
     const int T = prm.W, m = T / 2;
     const int start = dir ? T - 1 : 0, sgn = dir ? -1 : 1, len = dir ? T - 1 - m : m;
-    const RowsLane<D> L = rows_lane<D>(prm, pris_mask, wave, threadIdx.x);
+    RowsLane<D> L = rows_lane<D>(prm, pris_mask, wave, threadIdx.x);
+    if (rows_gate<D>(gate, prm, wave, threadIdx.x, L)) return;
     const float* blk = blocks + L.ubase * STRIDE;
     const float* gw = workG + L.ubase * (D * D);
     const float* yw = worky + L.ubase * D;
@@ -1109,10 +1125,12 @@ __device__ __forceinline__ const float* opaque(const float* p) {
 template <int D, int BS, bool kLds = false, bool kSplit = false>
 __global__ __launch_bounds__(BS) void full_solve_pcr_kernel(const ChainK ch, const FullK prm, const float* __restrict__ x,
                                                             const float* __restrict__ xv, float* blocks, float* workL,
-                                                            float* __restrict__ x_out) {
+                                                            float* __restrict__ x_out, const StepGateK gate) {
     constexpr int NT = D * (D + 1) / 2, SB = NT + D, DD = D * D;
     constexpr int STR = (SB + DD) | 1;  // odd stride: lanes t, t + 1, ... of a wavefront hit distinct banks
     extern __shared__ float pcr_state[];
+    // gated launch: the workgroup IS one trajectory, so every lane of it takes this exit or none does (no barrier is left waiting)
+    if (gate.ctl != nullptr && !step_open(gate, (int)blockIdx.x)) return;
     static_assert(!kSplit || (kLds && BS == 512), "the split form keeps its state in LDS and runs 512 lanes");
     constexpr int TW = kSplit ? BS / 2 : BS;  // waypoints per workgroup
     constexpr bool kLean = CPPF_PCR_LEAN(D, BS, kLds, kSplit);  // which form of the general level (below)

@@ -5,16 +5,14 @@
 // ---- Plan metrics for every seed at once (cppflow/data_types.py:140-264) ------------------------------------------------------
 // One wavefront per seed; lanes stride over the W waypoints (FK + pose metrics per waypoint, joint changes to the next
 // waypoint), then a 64-lane butterfly.  out[S,16] -- field order documented at cppf_plan_metrics in the header.
+// (the body is a function of its own so that the gated entry point of kernels_optloop.h runs the very same code)
 template <int D>
-__global__ __launch_bounds__(64) void plan_metrics_kernel(const ChainK ch, const CollK co, int S, int W,
-                                                          const float* __restrict__ x, const float* __restrict__ target,
-                                                          const uint8_t* __restrict__ self_mask,
-                                                          const uint8_t* __restrict__ env_mask,
-                                                          const float* __restrict__ q_init, float* __restrict__ out) {
+__device__ __forceinline__ void plan_metrics_seed(const ChainK& ch, const CollK& co, int s, int W, const float* __restrict__ x,
+                                                  const float* __restrict__ target, const uint8_t* __restrict__ self_mask,
+                                                  const uint8_t* __restrict__ env_mask, const float* __restrict__ q_init,
+                                                  float* __restrict__ out) {
     using RB = DynRobot<D>;
     const RB rb{ch, co};
-    const int s = blockIdx.x;
-    if (s >= S) return;
     const float rad2deg = 57.29577951308232087680f;
     float mx[4] = {0.f, 0.f, 0.f, 0.f};              // max pos (cm), max rot (deg), mjac revolute (deg), mjac prismatic (cm)
     float sm[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // sum pos, sum rot, length rad, length m, # limit violations, # self, # env
@@ -72,6 +70,17 @@ __global__ __launch_bounds__(64) void plan_metrics_kernel(const ChainK ch, const
         o[6] = sm[2], o[7] = sm[3], o[8] = sm[4], o[9] = sm[5], o[10] = sm[6], o[11] = qd;
         o[12] = o[13] = o[14] = o[15] = 0.f;
     }
+}
+
+template <int D>
+__global__ __launch_bounds__(64) void plan_metrics_kernel(const ChainK ch, const CollK co, int S, int W,
+                                                          const float* __restrict__ x, const float* __restrict__ target,
+                                                          const uint8_t* __restrict__ self_mask,
+                                                          const uint8_t* __restrict__ env_mask,
+                                                          const float* __restrict__ q_init, float* __restrict__ out) {
+    const int s = blockIdx.x;
+    if (s >= S) return;
+    plan_metrics_seed<D>(ch, co, s, W, x, target, self_mask, env_mask, q_init, out);
 }
 
 // ---- per-seed summary of a fused launch's per-row outputs ---------------------------------------------------------------------

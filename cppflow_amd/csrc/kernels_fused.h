@@ -497,13 +497,14 @@ template <class RB, bool WANT_MIN>
 __global__ __launch_bounds__(kBlock, CPPF_WAVES_COLL) void collision_kernel(const ChainK ch, const CollK co, int n,
                                                            const float* __restrict__ x, uint8_t* self_mask,
                                                            uint8_t* env_mask, uint8_t* jlim_mask, float* ext_cost,
-                                                           float* min_self, float* min_env) {
+                                                           float* min_self, float* min_env, const StepGateK gate, int gate_W) {
     extern __shared__ float lds[];
     constexpr int D = RB::D;
     const RB rb{ch, co};
     const int tid = threadIdx.x;
     const size_t row = (size_t)blockIdx.x * kBlock + tid;
     if (row >= (size_t)n) return;
+    if (gate.ctl != nullptr && !step_open(gate, (int)(row / (size_t)gate_W))) return;  // (rows are lane-private here: no barrier follows)
     float q[D], R[9], p[3];
     load_x<D>(x, row, q);
     // wave-uniform: which halves of the work the caller asked for (jlim-only calls skip FK altogether)
@@ -627,12 +628,15 @@ __global__ __launch_bounds__(kBlock) void pose_metrics_kernel(const ChainK ch, c
     if (rot_err) rot_err[row] = re;
 }
 
+__device__ __forceinline__ float clamp_joint(const ChainK& ch, int j, float v) {
+    return v != v ? v : fminf(fmaxf(v, ch.lo[j]), ch.hi[j]);  // torch.clamp keeps a NaN (fminf / fmaxf would drop it)
+}
+
 __global__ __launch_bounds__(kBlock) void clamp_kernel(const ChainK ch, size_t total, float* __restrict__ x) {
     const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= total) return;
     const int j = (int)(i % (size_t)ch.ndof);
-    const float v = x[i];
-    x[i] = v != v ? v : fminf(fmaxf(v, ch.lo[j]), ch.hi[j]);  // torch.clamp keeps a NaN (fminf / fmaxf would drop it)
+    x[i] = clamp_joint(ch, j, x[i]);
 }
 
 // one wavefront per seed: lanes stride over the seed's W waypoints, then a 64-lane butterfly max

@@ -365,14 +365,21 @@ constexpr int quad_min_waves() {
 template <class RB, int COLL, bool MFMA>
 __global__ __launch_bounds__(kBlock, quad_min_waves<RB>()) void lm_quad_kernel(const ChainK ch, const CollK co, const LmK prm,
                                                             const float* __restrict__ x_in, const float* __restrict__ target,
-                                                            const cppf_lm_outputs out, const uint4* __restrict__ tables) {
+                                                            const cppf_lm_outputs out, const uint4* __restrict__ tables,
+                                                            const StepGateK gate) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int D = RB::D;
     const RB rb{ch, co};
     const int tid = threadIdx.x, kk = tid & 3, slot = tid >> 2;
     const QuadLane k(kk);
     const size_t row_raw = (size_t)blockIdx.x * kQuadRows + slot;
-    const bool active = row_raw < (size_t)prm.n;
+    bool active = row_raw < (size_t)prm.n;
+    if (gate.ctl != nullptr) {
+        // gated launch (the optimiser loop on the device; never with the collision stage, so no barrier lies ahead): quads of a
+        // trajectory whose mode does not ask for this step store nothing, and a wavefront without a single open quad leaves here
+        active = active && step_open(gate, (int)(row_raw / (size_t)prm.W));
+        if (__builtin_amdgcn_ballot_w64(active) == 0ull) return;
+    }
     const size_t row = active ? row_raw : (size_t)prm.n - 1;  // idle quads shadow the last row: no divergence, stores predicated
     // the collision stage's pair / capsule records: fetched now, parked in registers across the LM loop, written to LDS at the
     // end (a load issued there would put a trip to L2 on the critical path of a launch that is all latency)

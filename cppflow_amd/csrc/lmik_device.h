@@ -70,6 +70,20 @@ struct LmK {
                                // s_memrealtime per LM iteration (kernels_fused.h: lm_pace; CPPF_TUNE_LM_PACE, the host decides)
 };
 
+// Per-trajectory launch gate of the device-side optimiser loop (kernels_optloop.h, cppf_lm_optimize_enqueue): a kernel that takes
+// one works on trajectory s only if the `mode` word of s's loop-control record is one of the modes in `mask`.  ctl == NULL (every
+// entry point but that one) opens every trajectory.  `per_traj` is 1 when every trajectory has a record of its own, 0 when record 0
+// speaks for all of them.  The record's first word is its mode (cppf_optloop_record in cppflow_hip.h, 16 words per record).
+struct StepGateK {
+    const int32_t* ctl;
+    int32_t per_traj;
+    uint32_t mask;
+};
+__device__ __forceinline__ bool step_open(const StepGateK& g, int s) {
+    if (g.ctl == nullptr) return true;
+    return ((g.mask >> (uint32_t)g.ctl[(size_t)(s * g.per_traj) * 16]) & 1u) != 0u;
+}
+
 // One problem of a fused launch: what cppf_lm_pose_steps takes as (x_in, target, S * W, W, outputs).  The same layout sits in the
 // kernel-argument segment (FusedArgs::single, the plain launch) and, for a batched launch (cppf_lm_batch_*), in a device table of
 // these behind a BatchHeadK -- the kernel picks one or the other base address and reads the fields with scalar loads either way.

@@ -58,6 +58,10 @@ class OptimizationResult:
     n_steps_taken: int
     is_valid: bool
     parallel_seed_idx: int
+    # device_loop=True only: per loop-control record, one (step taken "pose" / "diff", TL, the six x_is_valid flags or None, valid or
+    # None) per iteration decided -- what the device wrote down, for comparing decision by decision; and the records themselves
+    trace: Optional[list] = None
+    records: Optional[list] = None
 
 
 def _unstacked_target(opt_problem: OptimizationProblem) -> torch.Tensor:
@@ -133,20 +137,37 @@ def run_lm_alternating_loss(
     save_images: bool = False,
     results_df: Optional[Dict] = None,
     on_pose_valid: str = "differencing",
+    device_loop: bool = False,
+    sync_every: Optional[int] = None,
+    per_trajectory: bool = False,
 ):
     """The alternating loop of cppflow/optimization.py:147-373 with its bookkeeping and termination rules.
 
     Per iteration: if both pose flags are valid take the coupled differencing step (virtual configs := current x, :253),
     else a pose-only step; clamp; evaluate `x_is_valid`; TL-convergence (:275-297) and termination (:326-358) as in the
-    reference.  `on_pose_valid` = "stop" / "continue" replace the differencing branch by stopping / more pose steps."""
+    reference.  `on_pose_valid` = "stop" / "continue" replace the differencing branch by stopping / more pose steps.
+
+    `device_loop=True`: the same loop with the decision taken on the device (`cppf_lm_optimize_enqueue`): `sync_every` iterations
+    are enqueued at a time (default: all `max_n_steps` without a time limit, DEVICE_LOOP_TIMED_CHUNK with one) and the loop-control
+    block is copied back once per chunk -- ONE device-to-host copy per chunk instead of one per iteration.  Iterations enqueued
+    after the loop has ended are gated off on the device.  `tmax_sec` is checked between chunks only: the time limit has chunk
+    granularity in this mode (the last valid trajectory is still what comes back).  `per_trajectory=True` (device loop only): every
+    one of the `parallel_count` trajectories alternates and terminates by its OWN flags (a finished one is gated off) instead of
+    all following one decision; the result is the lowest-index valid trajectory (`parallel_seed_idx`), `x_opt` holds every
+    trajectory's own result."""
     assert not return_residuals and not save_images and results_df is None, "debug outputs are not supported"
     assert on_pose_valid in ("differencing", "stop", "continue")
+    assert device_loop or (sync_every is None and not per_trajectory), "sync_every / per_trajectory belong to device_loop=True"
+    assert sync_every is None or (isinstance(sync_every, int) and sync_every >= 1), "sync_every must be a positive int"
     if tmax_sec is None:
         assert (max_n_steps is not None) and (return_if_valid_after_n_steps is not None)
         assert return_if_valid_after_n_steps <= max_n_steps
     if max_n_steps is None:
         assert tmax_sec is not None
         max_n_steps = 10**6
+    if device_loop:
+        return _run_device_loop(opt_problem, opt_state, params_diff, params_pose, tmax_sec, max_n_steps,
+                                return_if_valid_after_n_steps, convergence_threshold, on_pose_valid, sync_every, per_trajectory)
     robot = opt_problem.robot
     target = _unstacked_target(opt_problem)
     printc = print if verbosity > 1 else (lambda *a, **k: None)
@@ -217,6 +238,79 @@ def run_lm_alternating_loss(
     )
 
 
+DEVICE_LOOP_TIMED_CHUNK = 4  # iterations enqueued between two looks at the clock when the device loop runs under a time limit
+DEVICE_LOOP_TRACE_CAPACITY = 4096  # iterations whose decision the device writes down (an anytime run may take more; those are not traced)
+
+
+def _run_device_loop(opt_problem, opt_state, params_diff, params_pose, tmax_sec, max_n_steps, return_if_valid_after_n_steps,
+                     convergence_threshold, on_pose_valid, sync_every, per_trajectory) -> OptimizationResult:
+    """`run_lm_alternating_loss(device_loop=True)`: enqueue chunks of gated iterations, copy the loop-control block back once per
+    chunk, assemble the result the host loop would return."""
+    import numpy as np
+
+    from cppflow_amd import _hip
+
+    robot, problem = opt_problem.robot, opt_problem.problem
+    target = _unstacked_target(opt_problem)
+    W, S = opt_problem.n_timesteps, opt_problem.parallel_count
+    x = opt_state.x
+    assert x.shape == (S * W, robot.ndof) and x.is_contiguous(), tuple(x.shape)
+    if max_n_steps == 0:
+        return OptimizationResult(x_opt=x, n_steps_taken=0, is_valid=False, parallel_seed_idx=0, trace=[], records=[])
+    problem.bind_obstacles()
+    c = opt_problem.constraints
+    prm = _hip.OptloopParams()
+    prm.pose_lm_lambda, prm.pose_alpha_position = float(params_pose.lm_lambda), float(params_pose.alpha_position)
+    prm.pose_alpha_rotation = float(params_pose.alpha_rotation)
+    prm.diff = robot.full_params(params_diff)
+    prm.constraints = _hip.Constraints(c.max_allowed_position_error_cm, c.max_allowed_rotation_error_deg, c.max_allowed_mjac_deg,
+                                       c.max_allowed_mjac_cm, int(bool(SELF_COLLISIONS_IGNORED)), int(bool(ENV_COLLISIONS_IGNORED)))  # fmt: skip
+    prm.max_n_steps = int(max_n_steps)
+    prm.return_if_valid_after_n_steps = -1 if return_if_valid_after_n_steps is None else min(int(return_if_valid_after_n_steps), 2**31 - 1)
+    prm.on_pose_valid = _hip.OPT_ON_POSE_VALID[on_pose_valid]
+    prm.per_trajectory = int(bool(per_trajectory))
+    prm.trace_capacity = min(int(max_n_steps), DEVICE_LOOP_TRACE_CAPACITY)
+    prm.convergence_threshold = float(convergence_threshold)
+    C = S if per_trajectory else 1
+    workspace, control = robot.lm_optimize_buffers(S, W, prm, x.device)
+    chunk = sync_every if sync_every is not None else (max_n_steps if tmax_sec is None else DEVICE_LOOP_TIMED_CHUNK)
+    t0 = time()
+    enqueued = 0
+    while True:
+        k = min(chunk, max_n_steps - enqueued)
+        robot.lm_optimize_enqueue(x, target, prm, workspace, control, k)
+        enqueued += k
+        host = control.cpu().numpy()  # the one device-to-host copy of this chunk
+        rec = host[: C * 16].reshape(C, 16)
+        if bool((rec[:, 0] == _hip.OPT_MODE_DONE).all()) or enqueued >= max_n_steps:
+            break
+        if tmax_sec is not None and time() - t0 > tmax_sec:
+            break  # (optimization.py: the last valid trajectory comes back, as below)
+    opt_state.n_steps += int(rec[:, 5].max())
+    done = rec[:, 0] == _hip.OPT_MODE_DONE
+    i_final = np.where(done, rec[:, 10], rec[:, 5] - 1)
+    valid = rec[:, 8] != 0
+    snapshot = workspace[: S * W * robot.ndof].view(S * W, robot.ndof)
+    if not per_trajectory:
+        x_opt = snapshot.clone() if valid[0] else x
+        seed_idx = int(rec[0, 9])
+    else:
+        x_opt = x.clone()
+        for s in np.nonzero(valid)[0]:
+            x_opt[s * W : (s + 1) * W] = snapshot[s * W : (s + 1) * W]
+        seed_idx = int(np.nonzero(valid)[0][0]) if valid.any() else 0
+    tr = host[C * 16 :].reshape(C, prm.trace_capacity, 4)
+    names = {_hip.OPT_MODE_POSE: "pose", _hip.OPT_MODE_DIFF: "diff"}
+    trace = [
+        [(names[int(r[0])], float(r[1:2].view(np.float32)[0]), _hip.optloop_flags(int(r[2])), None if r[3] < 0 else bool(r[3]))
+         for r in tr[ci, : min(int(rec[ci, 5]), prm.trace_capacity)]]
+        for ci in range(C)
+    ]  # fmt: skip
+    records = [_hip.OptloopRecord.from_buffer_copy(rec[ci].tobytes()) for ci in range(C)]
+    return OptimizationResult(x_opt=x_opt, n_steps_taken=max(int(i_final.max()), 0), is_valid=bool(valid.any()),
+                              parallel_seed_idx=seed_idx, trace=trace, records=records)  # fmt: skip
+
+
 def run_lm_optimization(
     problem: Problem,
     x_seed: torch.Tensor,
@@ -228,9 +322,13 @@ def run_lm_optimization(
     results_df: Optional[Dict] = None,
     verbosity: int = 1,
     on_pose_valid: str = "differencing",
+    device_loop: bool = False,
+    sync_every: Optional[int] = None,
+    per_trajectory: bool = False,
 ) -> OptimizationResult:
     """Optimise a trajectory (or `parallel_count` seeds at once): x_seed is [parallel_count * W, ndof]
-    (cppflow/optimization.py:376-426).  The target path is NOT stacked: rows index it modulo W."""
+    (cppflow/optimization.py:376-426).  The target path is NOT stacked: rows index it modulo W.
+    `device_loop` / `sync_every` / `per_trajectory`: see `run_lm_alternating_loss`."""
     if SELF_COLLISIONS_IGNORED:
         warnings.warn("robot-robot are collisions will be ignored during LM optimization")
     if ENV_COLLISIONS_IGNORED:
@@ -247,6 +345,7 @@ def run_lm_optimization(
         opt_problem, opt_state, ALT_LOSS_V2_1_DIFF, ALT_LOSS_V2_1_POSE, return_residuals=False, verbosity=verbosity,
         tmax_sec=tmax_sec, max_n_steps=max_n_steps, return_if_valid_after_n_steps=return_if_valid_after_n_steps,
         convergence_threshold=convergence_threshold, save_images=False, results_df=results_df, on_pose_valid=on_pose_valid,
+        device_loop=device_loop, sync_every=sync_every, per_trajectory=per_trajectory,
     )  # fmt: skip
 
 

@@ -148,9 +148,11 @@ class TrackingSeedProvider:
 
 class Planner:
     def __init__(self, settings: PlannerSettings, robot, seed_provider: Optional[SeedProvider] = None, process_group=None,
-                 candidate_lm_steps: int = 0):
+                 candidate_lm_steps: int = 0, device_optimizer: bool = False):
         """`process_group` / `candidate_lm_steps`: the sharded candidate stage (module docstring); with `candidate_lm_steps` > 0 every
-        (candidate, waypoint) row takes that many fused pose-only LM iterations before the masks are evaluated (one launch)."""
+        (candidate, waypoint) row takes that many fused pose-only LM iterations before the masks are evaluated (one launch).
+        `device_optimizer`: the LM optimiser's loop is decided on the device (`run_lm_optimization(device_loop=True)`); same plan."""
+        self._device_optimizer = bool(device_optimizer)
         self._cfg = settings
         self._robot = robot
         self._seed_provider = seed_provider if seed_provider is not None else LmIkSeedProvider()
@@ -270,7 +272,7 @@ class CppFlowPlanner(Planner):
                       convergence_threshold=OPTIMIZATION_CONVERGENCE_THRESHOLD) if self._cfg.anytime_mode_enabled else dict(
             max_n_steps=20, return_if_valid_after_n_steps=0, convergence_threshold=1e6)  # fmt: skip  (planners.py:402-422)
         opt = run_lm_optimization(problem, search_qpath.contiguous(), tmax_sec=self._cfg.tmax_sec - (time() - t0),
-                                  verbosity=self._cfg.verbosity, **budget)  # fmt: skip
+                                  verbosity=self._cfg.verbosity, device_loop=self._device_optimizer, **budget)  # fmt: skip
         td.optimizer = time() - t0_opt
         debug_info["n_optimization_steps"] = opt.n_steps_taken
         x_opt = opt.x_opt.detach()

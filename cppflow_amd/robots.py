@@ -591,29 +591,11 @@ class Robot:
         n, W = x.shape[0], target.shape[0]
         assert target.dim() == 2 and target.shape[1] == 7 and W > 0 and n % W == 0
         p = opt_params
-        assert not (p.differencing_do_scale_satisfied and p.differencing_do_ignore_satisfied), "use one or the other, not both"
-        from cppflow_amd.optimization_utils import satisfied_thresholds
-
-        thr = satisfied_thresholds(p, constraints)
         xv = None
         if virtual_configs is not None and p.use_virtual_configs and virtual_configs.numel() > 0:
             xv = self._x2d(virtual_configs, "virtual_configs")
             assert xv.shape == x.shape, "virtual_configs must have the shape of x (optimization_utils.py:433)"
-
-        def f(v):
-            return 0.0 if v is None else float(v)
-
-        prm = _hip.FullParams(f(p.lm_lambda), f(p.alpha_position), f(p.alpha_rotation), f(p.alpha_differencing),
-                              f(p.alpha_differencing_prismatic_scaling), f(p.alpha_virtual_configs),
-                              f(p.alpha_self_collision), f(p.alpha_env_collision), int(bool(p.use_pose)),
-                              int(bool(p.use_differencing)), int(bool(p.use_virtual_configs)), int(p.n_virtual_configs or 0),
-                              int(bool(p.use_self_collisions)), int(bool(p.use_env_collisions)),
-                              int(bool(p.pose_do_scale_down_satisfied)), thr["pose_threshold_m"], thr["pose_threshold_rad"],
-                              f(p.pose_ignore_satisfied_scale_down),
-                              1 if p.differencing_do_ignore_satisfied else (2 if p.differencing_do_scale_satisfied else 0),
-                              thr["differencing_threshold_rad"], thr["differencing_threshold_m"],
-                              f(p.differencing_scale_down_satisfied_scale),
-                              int(bool(p.differencing_scale_down_satisfied_shift_invalid_to_threshold)))  # fmt: skip
+        prm = self.full_params(p, constraints)
         d = self.ndof
         nt = d * (d + 1) // 2
         dev = x.device
@@ -629,6 +611,64 @@ class Robot:
             )  # fmt: skip
         )
         return x_out
+
+    @staticmethod
+    def full_params(opt_params, constraints=None) -> "_hip.FullParams":
+        """An OptimizationParameters record as the coupled step's `cppf_full_params` (thresholds of the "satisfied" row options from
+        `constraints`, see `lm_full_step`)."""
+        p = opt_params
+        assert not (p.differencing_do_scale_satisfied and p.differencing_do_ignore_satisfied), "use one or the other, not both"
+        from cppflow_amd.optimization_utils import satisfied_thresholds
+
+        thr = satisfied_thresholds(p, constraints)
+
+        def f(v):
+            return 0.0 if v is None else float(v)
+
+        return _hip.FullParams(f(p.lm_lambda), f(p.alpha_position), f(p.alpha_rotation), f(p.alpha_differencing),
+                              f(p.alpha_differencing_prismatic_scaling), f(p.alpha_virtual_configs),
+                              f(p.alpha_self_collision), f(p.alpha_env_collision), int(bool(p.use_pose)),
+                              int(bool(p.use_differencing)), int(bool(p.use_virtual_configs)), int(p.n_virtual_configs or 0),
+                              int(bool(p.use_self_collisions)), int(bool(p.use_env_collisions)),
+                              int(bool(p.pose_do_scale_down_satisfied)), thr["pose_threshold_m"], thr["pose_threshold_rad"],
+                              f(p.pose_ignore_satisfied_scale_down),
+                              1 if p.differencing_do_ignore_satisfied else (2 if p.differencing_do_scale_satisfied else 0),
+                              thr["differencing_threshold_rad"], thr["differencing_threshold_m"],
+                              f(p.differencing_scale_down_satisfied_scale),
+                              int(bool(p.differencing_scale_down_satisfied_shift_invalid_to_threshold)))  # fmt: skip
+
+    # ---- the optimiser loop on the device (cppf_lm_optimize_enqueue) ---------------------------------------------------------------
+    def lm_optimize_buffers(self, S: int, W: int, prm: "_hip.OptloopParams", device) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(workspace, control) for `lm_optimize_enqueue`: the workspace (fp32; its first S*W*ndof floats are the snapshot of the last
+        valid x) and the loop-control block (int32: records then trace), initialised so that every record leads with a pose step."""
+        dev = torch.device(device)
+        nb = ctypes.c_size_t(0)
+        _hip.check(_hip.lib().cppf_lm_optimize_workspace_bytes(self._handle(dev), S, W, ctypes.byref(nb)))
+        workspace = torch.empty(nb.value // 4, dtype=torch.float32, device=dev)
+        _hip.check(_hip.lib().cppf_lm_optimize_control_bytes(S, ctypes.byref(prm), ctypes.byref(nb)))
+        n_records = S if prm.per_trajectory else 1
+        init = _hip.optloop_initial_control(n_records, prm.trace_capacity)
+        assert init.nbytes == nb.value
+        control = torch.from_numpy(init).to(dev)
+        return workspace, control
+
+    def lm_optimize_enqueue(self, x: torch.Tensor, target: torch.Tensor, prm: "_hip.OptloopParams", workspace: torch.Tensor,
+                            control: torch.Tensor, n_iterations: int) -> None:
+        """Enqueue `n_iterations` gated iterations of the alternating loop on x [S*W, d] (in place) and return without
+        synchronising; copy `control` back to see what was decided (`_hip.OptloopRecord` per record, then the trace)."""
+        xc = self._x2d(x)
+        assert xc.data_ptr() == x.data_ptr(), "lm_optimize_enqueue works on x in place: x must be contiguous"
+        target = _require_device_tensor(target, "target_path")
+        n, W = x.shape[0], target.shape[0]
+        assert target.dim() == 2 and target.shape[1] == 7 and W > 0 and n % W == 0
+        assert workspace.is_cuda and workspace.dtype == torch.float32 and workspace.is_contiguous()
+        assert control.is_cuda and control.dtype == torch.int32 and control.is_contiguous()
+        _hip.check(
+            _hip.lib().cppf_lm_optimize_enqueue(
+                self._handle(x.device), x.data_ptr(), target.data_ptr(), n // W, W, ctypes.byref(prm), workspace.data_ptr(),
+                control.data_ptr(), int(n_iterations), _stream_ptr(x.device),
+            )  # fmt: skip
+        )
 
     def dp_search(self, q: torch.Tensor, ext_cost: torch.Tensor, prismatic_joint_scaling: float = 5.0, method: str = "auto",
                   return_memo: bool = False, return_method: bool = False):

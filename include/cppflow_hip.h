@@ -409,6 +409,79 @@ int cppf_lm_full_step(const cppf_robot* robot, const float* x_in, const float* t
                       int W, const cppf_full_params* params, float* work_blocks, float* work_G, float* work_y,
                       float* x_out, void* stream);
 
+/* ---- the alternating LM optimiser loop on the device (run_lm_alternating_loss, cppflow/optimization.py:147-373) -------------------
+ * cppf_lm_optimize_enqueue() enqueues `n_iterations` iterations of  { pose step | coupled step ; clamp ; capsule masks ; plan
+ * metrics ; decide }  on `stream` and returns without synchronising.  Which step an iteration takes, whether the trajectory is
+ * valid, converged or finished is decided ON THE DEVICE by the last kernel of the iteration, from the [S,16] metrics the one before
+ * it wrote, with the rules of the reference's loop; the decision lives in a loop-control block in device memory, and every kernel
+ * of an iteration returns at once for a trajectory whose record does not ask for it (an iteration enqueued after `done` costs its
+ * launches and nothing else).  The caller copies the control block back ONCE, whenever it wants to know.
+ *
+ * Control block (device, int32 words; the caller initialises it, see below):
+ *     cppf_optloop_record  record[C]                   C = S if per_trajectory else 1
+ *     cppf_optloop_trace   trace[C][trace_capacity]    one row per iteration the record has decided (those beyond the capacity
+ *                                                      are not recorded)
+ * per_trajectory = 0: ONE record speaks for all S trajectories, as the reference's loop does (TL = the sum over the trajectories,
+ * flags of the last trajectory x_is_valid examined, the snapshot is the whole x).  per_trajectory = 1: every trajectory alternates
+ * and terminates on its own.
+ * Initial record: mode = CPPF_OPT_MODE_POSE, pose_pos_valid = 1, pose_rot_valid = 0 (the reference leads with a pose step,
+ * optimization.py:218-219), last_valid_idx = -1, everything else 0.  A record with mode = CPPF_OPT_MODE_DONE is never touched again. */
+#define CPPF_OPT_MODE_POSE 0 /* the next step is the pose-only step (K = 1, no clamp inside) */
+#define CPPF_OPT_MODE_DIFF 1 /* the next step is the coupled differencing step (virtual configs := current x) */
+#define CPPF_OPT_MODE_DONE 2 /* finished: is_valid, valid_seed_idx, i_final hold the result */
+
+#define CPPF_OPT_ON_POSE_VALID_DIFFERENCING 0
+#define CPPF_OPT_ON_POSE_VALID_STOP 1
+#define CPPF_OPT_ON_POSE_VALID_CONTINUE 2
+
+typedef struct cppf_optloop_record { /* 16 words */
+    int32_t mode;                           /* CPPF_OPT_MODE_*: the step the NEXT iteration takes */
+    int32_t pose_pos_valid, pose_rot_valid; /* of the last trajectory x_is_valid examined */
+    int32_t converged;                      /* TL change between two consecutive differencing steps fell below the threshold */
+    int32_t last_valid_idx;                 /* iteration of the last snapshot, -1 = none */
+    int32_t n_steps;                        /* iterations decided so far */
+    int32_t has_tl;                         /* last_tl holds the TL after the last differencing step */
+    float last_tl;
+    int32_t is_valid;       /* a snapshot exists (workspace, see below) */
+    int32_t valid_seed_idx; /* first valid trajectory at the last snapshot (0 with per_trajectory) */
+    int32_t i_final;        /* valid once mode = DONE: the loop index the reference's loop ends with (its n_steps_taken) */
+    int32_t reserved[5];
+} cppf_optloop_record;
+
+/* flags: bit 0 pose_pos_valid, 1 pose_rot_valid, 2 mjac_rev_valid, 3 mjac_pris_valid; bits 4-5 is_a_self_collision and bits 6-7
+ * is_a_env_collision as 0 = not looked at (the reference's None), 1 = no, 2 = yes.  flags = valid = -1: the iteration ended on the
+ * TL rule before validity was evaluated (optimization.py:294-297). */
+typedef struct cppf_optloop_trace {
+    int32_t mode; /* the step this iteration took */
+    float tl;
+    int32_t flags;
+    int32_t valid;
+} cppf_optloop_trace;
+
+typedef struct cppf_optloop_params {
+    float pose_lm_lambda, pose_alpha_position, pose_alpha_rotation; /* ALT_LOSS_V2_1_POSE: 1e-6, 3.5, 0.35 */
+    cppf_full_params diff;                                          /* ALT_LOSS_V2_1_DIFF (use_pose = 0, differencing_mode = 0) */
+    cppf_constraints constraints;                                   /* thresholds (strict <, fp32) and the two collisions-ignored switches */
+    int32_t max_n_steps;                   /* >= 1 */
+    int32_t return_if_valid_after_n_steps; /* -1 = no such rule */
+    int32_t on_pose_valid;                 /* CPPF_OPT_ON_POSE_VALID_* */
+    int32_t per_trajectory;
+    int32_t trace_capacity; /* >= 0 */
+    int32_t reserved;
+    double convergence_threshold; /* |TL - previous TL| is formed and compared in double, as the Python loop does */
+} cppf_optloop_params;
+
+/* Workspace (device, 16-byte aligned) for S trajectories of W waypoints.  Its first S*W*d floats are the SNAPSHOT: the x of the
+ * last valid iteration (per record), what the caller returns when is_valid; the rest is scratch. */
+int cppf_lm_optimize_workspace_bytes(const cppf_robot* robot, int S, int W, size_t* bytes);
+int cppf_lm_optimize_control_bytes(int S, const cppf_optloop_params* params, size_t* bytes);
+/* x [S*W, d] is read and written in place; target [W,7].  Obstacles / limits: those of the handle.  CPPF_ERR_UNSUPPORTED where a
+ * step has no gated kernel: fewer than 6 joints or more rows than the quad-shape pose kernel serves, a handle specialised at run
+ * time, a coupled step that is not eliminated by the parallel-in-time or the row-per-lane kernels. */
+int cppf_lm_optimize_enqueue(const cppf_robot* robot, float* x, const float* target, int S, int W,
+                             const cppf_optloop_params* params, void* workspace, int32_t* control, int n_iterations,
+                             void* stream);
+
 /* _get_mjacs (cppflow/search.py:100-125): q [k,T,d] -> mjacs [k,k,T-1], mjacs[i,j,t] = max over joints of
  * |wrap(s (q[i,t+1] - q[j,t]))| with s = prismatic_scaling on prismatic joints.  cppf_dp_search does not need it (it never
  * materialises the tensor); provided for callers of the reference helper. */

@@ -14,6 +14,6 @@ constexpr int kBlock = 256;
 #include "kernels_coupled.h"
 }
 using namespace dev;
-#define PCR(D, BS, L, S) template __global__ void dev::full_solve_pcr_kernel<D, BS, L, S>(const ChainK, const FullK, const float*, const float*, float*, float*, float*);
+#define PCR(D, BS, L, S) template __global__ void dev::full_solve_pcr_kernel<D, BS, L, S>(const ChainK, const FullK, const float*, const float*, float*, float*, float*, const StepGateK);
 PCR(7, 256, true, false) PCR(7, 512, true, true) PCR(7, 512, false, false) PCR(7, 256, false, false)
 PCR(8, 256, true, false) PCR(8, 512, true, true) PCR(8, 512, false, false) PCR(8, 256, false, false)

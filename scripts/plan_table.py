@@ -2,12 +2,18 @@
 """Planning record on the reference's own problems: CppFlowPlanner.generate_plan with both seed providers.
 
     python scripts/plan_table.py [--out profiles/plan_table.txt] [--problems a,b,...] [--k 175] [--tmax 5]
+    python scripts/plan_table.py --device-loop [--out profiles/plan_table_device_loop.txt] [--repeats 5]
 
 The 13 problems of the reference's README plus the `_mini` / truncated fixtures, loaded from tests/golden/reference_files with
 problem_from_filename, k = 175, tmax_sec = 5 and the constraints of the reference's scripts/evaluate.py:51-56 (0.01 cm, 0.1 deg, 7 deg,
 2 cm).  Per problem and provider: valid or not, the constraints that failed, the LM optimisation steps, ms per stage (seeds / masks /
 dp_search / optimiser), the searched path's mjac (deg / cm) and the seed stage's own ms measured around the provider call after a
-synchronize (TimingData.ikflow is host time up to the provider's return, which for a one-launch provider is mostly enqueue)."""
+synchronize (TimingData.ikflow is host time up to the provider's return, which for a one-launch provider is mostly enqueue).
+
+`--device-loop` writes a second table instead: per problem (LmIk provider) the optimiser stage with the host loop and with the loop
+decided on the device (`CppFlowPlanner(device_optimizer=True)`), same process, alternating, median of `--repeats` plans each after one
+warm-up plan of either kind; and the cost of enqueuing gated-off iterations behind a finished loop (host time per iteration to
+enqueue, device time per iteration to drain), which is what enqueuing ahead pays for."""
 
 import argparse
 import os
@@ -59,12 +65,12 @@ def providers():
     return {"LmIk": lambda: LmIkSeedProvider(seed=0), "Tracking": lambda: TrackingSeedProvider(seed=0)}
 
 
-def run(name: str, prov_name: str, k: int, tmax: float, device: str) -> dict:
+def run(name: str, prov_name: str, k: int, tmax: float, device: str, device_optimizer: bool = False) -> dict:
     problem = load(name, device)
     prov = Timed(providers()[prov_name]())
     settings = PlannerSettings(k=k, tmax_sec=tmax, anytime_mode_enabled=False, do_rerun_if_large_dp_search_mjac=True,
                                do_rerun_if_optimization_fails=False, do_return_search_path_mjac=True, verbosity=0)  # fmt: skip
-    planner = CppFlowPlanner(settings, problem.robot, seed_provider=prov)
+    planner = CppFlowPlanner(settings, problem.robot, seed_provider=prov, device_optimizer=device_optimizer)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     res = planner.generate_plan(problem)
@@ -81,9 +87,81 @@ def run(name: str, prov_name: str, k: int, tmax: float, device: str) -> dict:
                 plan_mjac_deg=res.plan.mjac_deg, plan_mjac_cm=res.plan.mjac_cm)  # fmt: skip
 
 
+def noop_iteration_cost(name: str, device: str, n_iterations: int = 20, repeats: int = 20):
+    """(host us per iteration to enqueue, device us per iteration to drain) for iterations enqueued behind a loop that is done"""
+    import statistics
+
+    from cppflow_amd import _hip
+    from cppflow_amd.lm_hyper_parameters import ALT_LOSS_V2_1_DIFF
+
+    problem = load(name, device)
+    rb, W = problem.robot, problem.n_timesteps
+    problem.bind_obstacles()
+    prm = _hip.OptloopParams()
+    prm.pose_lm_lambda, prm.pose_alpha_position, prm.pose_alpha_rotation = 1e-6, 3.5, 0.35
+    prm.diff = rb.full_params(ALT_LOSS_V2_1_DIFF)
+    prm.constraints = _hip.Constraints(0.01, 0.1, 7.0, 2.0, 0, 0)
+    prm.max_n_steps, prm.return_if_valid_after_n_steps, prm.trace_capacity, prm.convergence_threshold = 20, 0, 20, 1e6
+    workspace, control = rb.lm_optimize_buffers(1, W, prm, device)
+    control[0] = _hip.OPT_MODE_DONE
+    x = torch.zeros((W, rb.ndof), dtype=torch.float32, device=device)
+    host, dev = [], []
+    for r in range(repeats + 3):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        rb.lm_optimize_enqueue(x, problem.target_path, prm, workspace, control, n_iterations)
+        t1 = time.perf_counter()
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        if r >= 3:
+            host.append(1e6 * (t1 - t0) / n_iterations)
+            dev.append(1e6 * (t2 - t0) / n_iterations)
+    return statistics.median(host), statistics.median(dev), W
+
+
+def main_device_loop(a, names):
+    import statistics
+
+    device = "cuda:0"
+    for dl in (False, True):
+        run("panda__1cube_mini", "LmIk", a.k, a.tmax, device, device_optimizer=dl)
+    lines = [f"# scripts/plan_table.py --device-loop: the optimiser stage of CppFlowPlanner.generate_plan (LmIk provider, k = {a.k}, "
+             f"tmax_sec = {a.tmax}), host loop vs the loop decided on the device; ms, median of {a.repeats} plans each, alternating, "
+             f"same process, after one warm-up plan of either kind per problem",
+             f"# torch {torch.__version__}, device {torch.cuda.get_device_name(0)}",
+             f"{'problem':26s} {'T':>4s} {'lm':>3s} {'opt_host':>9s} {'opt_dev':>9s} {'min_host':>9s} {'min_dev':>9s} {'same':>5s}"]  # fmt: skip
+    print("\n".join(lines), flush=True)
+    for name in names:
+        res = {False: [], True: []}
+        for rep in range(a.repeats + 1):
+            for dl in (False, True):
+                r = run(name, "LmIk", a.k, a.tmax, device, device_optimizer=dl)
+                if rep > 0:
+                    res[dl].append(r)
+        h, d = [r["opt_ms"] for r in res[False]], [r["opt_ms"] for r in res[True]]
+        same = all(x["lm_steps"] == y["lm_steps"] and x["valid"] == y["valid"] for x, y in zip(res[False], res[True]))
+        ln = (f"{name:26s} {res[False][0]['T']:4d} {res[False][0]['lm_steps']:3d} {statistics.median(h):9.3f} {statistics.median(d):9.3f} "
+              f"{min(h):9.3f} {min(d):9.3f} {str(same):>5s}")  # fmt: skip
+        print(ln, flush=True)
+        lines.append(ln)
+    lines.append("# gated-off iterations enqueued behind a finished loop (7 or 8 launches each): host us per iteration to enqueue, us per "
+                 "iteration until the device has drained them (median of 20 x 20 iterations)")
+    for name in ("panda__1cube_mini", "fetch__hello"):
+        if name in names or name == "panda__1cube_mini":
+            hu, du, W = noop_iteration_cost(name, device)
+            ln = f"# noop {name:24s} T {W:4d}  enqueue {hu:7.2f} us/iteration  drained {du:7.2f} us/iteration"
+            print(ln, flush=True)
+            lines.append(ln)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "plan_table.txt"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--device-loop", action="store_true", help="the optimiser stage, host loop vs device loop (a table of its own)")
+    ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--problems", default=",".join(README_PROBLEMS + FIXTURES))
     ap.add_argument("--k", type=int, default=175)
     ap.add_argument("--tmax", type=float, default=5.0)
@@ -91,6 +169,10 @@ def main():
     device = "cuda:0"
     assert torch.cuda.is_available(), "plan_table.py runs the planner on the MI355X"
     names = [n for n in a.problems.split(",") if n]
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "plan_table_device_loop.txt" if a.device_loop else "plan_table.txt")
+    if a.device_loop:
+        return main_device_loop(a, names)
     # warm-up: the first planning call of a process pays for allocator growth and library loading
     for pn in providers():
         run("panda__1cube_mini", pn, a.k, a.tmax, device)

@@ -17,11 +17,11 @@ constexpr int kBlock = 256;
 }  // namespace dev
 using namespace dev;
 
-template __global__ void dev::lm_quad_kernel<StaRobot<gen::Panda>, 1, false>(const ChainK, const CollK, const LmK, const float*, const float*, const cppf_lm_outputs, const uint4*);
-template __global__ void dev::lm_quad_kernel<StaRobot<gen::Chain12>, 1, true>(const ChainK, const CollK, const LmK, const float*, const float*, const cppf_lm_outputs, const uint4*);
-template __global__ void dev::lm_quad_kernel<StaRobot<gen::Chain12>, 1, false>(const ChainK, const CollK, const LmK, const float*, const float*, const cppf_lm_outputs, const uint4*);
-template __global__ void dev::lm_quad_kernel<StaRobot<gen::Chain12>, 0, false>(const ChainK, const CollK, const LmK, const float*, const float*, const cppf_lm_outputs, const uint4*);
-template __global__ void dev::lm_quad_kernel<DynRobot<11>, 1, false>(const ChainK, const CollK, const LmK, const float*, const float*, const cppf_lm_outputs, const uint4*);
-template __global__ void dev::lm_quad_kernel<DynRobot<12>, 1, false>(const ChainK, const CollK, const LmK, const float*, const float*, const cppf_lm_outputs, const uint4*);
-template __global__ void dev::lm_quad_kernel<DynRobot<12>, 0, false>(const ChainK, const CollK, const LmK, const float*, const float*, const cppf_lm_outputs, const uint4*);
-template __global__ void dev::lm_quad_kernel<DynRobot<10>, 1, false>(const ChainK, const CollK, const LmK, const float*, const float*, const cppf_lm_outputs, const uint4*);
+template __global__ void dev::lm_quad_kernel<StaRobot<gen::Panda>, 1, false>(const ChainK, const CollK, const LmK, const float*, const float*, const cppf_lm_outputs, const uint4*, const StepGateK);
+template __global__ void dev::lm_quad_kernel<StaRobot<gen::Chain12>, 1, true>(const ChainK, const CollK, const LmK, const float*, const float*, const cppf_lm_outputs, const uint4*, const StepGateK);
+template __global__ void dev::lm_quad_kernel<StaRobot<gen::Chain12>, 1, false>(const ChainK, const CollK, const LmK, const float*, const float*, const cppf_lm_outputs, const uint4*, const StepGateK);
+template __global__ void dev::lm_quad_kernel<StaRobot<gen::Chain12>, 0, false>(const ChainK, const CollK, const LmK, const float*, const float*, const cppf_lm_outputs, const uint4*, const StepGateK);
+template __global__ void dev::lm_quad_kernel<DynRobot<11>, 1, false>(const ChainK, const CollK, const LmK, const float*, const float*, const cppf_lm_outputs, const uint4*, const StepGateK);
+template __global__ void dev::lm_quad_kernel<DynRobot<12>, 1, false>(const ChainK, const CollK, const LmK, const float*, const float*, const cppf_lm_outputs, const uint4*, const StepGateK);
+template __global__ void dev::lm_quad_kernel<DynRobot<12>, 0, false>(const ChainK, const CollK, const LmK, const float*, const float*, const cppf_lm_outputs, const uint4*, const StepGateK);
+template __global__ void dev::lm_quad_kernel<DynRobot<10>, 1, false>(const ChainK, const CollK, const LmK, const float*, const float*, const cppf_lm_outputs, const uint4*, const StepGateK);

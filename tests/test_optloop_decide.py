@@ -1,0 +1,325 @@
+"""The decision function of the device-side optimiser loop (`optloop_decide`, cppflow_amd/csrc/kernels_optloop.h) against the Python
+loop it restates (run_lm_alternating_loss, cppflow_amd/optimization.py).  CPU only: the function is `__host__ __device__` without a
+HIP intrinsic, so the host C++ compiler builds it here (into pytest's tmp_path, behind a ten-line extern "C" shim) and ctypes drives
+it -- no GPU, no hipcc.
+
+Yardstick: the existing Python loop with its step functions stubbed the way tests/test_loop_control.py stubs them (pose step: x + 1,
+differencing step: x + 100, clamp: identity, evaluate_seeds: the scripted [S,16] metrics); `x_is_valid` is the real one, fed those
+metrics.  Everything compared is an integer, a boolean or an exactly representable float and must be EQUAL: the sequence of steps,
+n_steps_taken, is_valid, parallel_seed_idx and the x that is returned (which says which iteration's x it is).
+
+Thresholds are compared in fp32 on both sides.  So that no comparison sits on a rounding edge the scripted metrics, the thresholds,
+the TL values and the convergence threshold are all small multiples of 1/8: exactly representable, their sums and differences
+exact in fp32 in any order (a value equal to its threshold is then "not below" on both sides, deterministically)."""
+
+import ctypes
+import os
+import shutil
+import subprocess
+import types
+
+import numpy as np
+import pytest
+import torch
+
+from cppflow_amd import _hip
+from cppflow_amd import optimization as opt
+from cppflow_amd import optimization_utils as opt_utils
+from cppflow_amd.data_types import Constraints
+from cppflow_amd.lm_hyper_parameters import ALT_LOSS_V2_1_DIFF, ALT_LOSS_V2_1_POSE
+
+CSRC = os.path.join(os.path.dirname(os.path.abspath(opt.__file__)), "csrc")
+W, D = 4, 3
+CONSTRAINTS = Constraints(max_allowed_position_error_cm=0.5, max_allowed_rotation_error_deg=0.5, max_allowed_mjac_deg=2.0,
+                          max_allowed_mjac_cm=1.0)  # fmt: skip
+
+SHIM = """
+#include "kernels_optloop.h"
+extern "C" int shim_decide(const cppf_optloop_params* P, cppf_optloop_record* rec, const float* metrics, int G,
+                           cppf_optloop_trace* tr) {
+    return optloop_decide(*P, *rec, metrics, G, *tr);
+}
+extern "C" unsigned long shim_control_words(int S, const cppf_optloop_params* P) { return (unsigned long)optloop_control_words(S, *P); }
+extern "C" int shim_sizeof(int which) {
+    return which == 0 ? (int)sizeof(cppf_optloop_params) : which == 1 ? (int)sizeof(cppf_optloop_record) : (int)sizeof(cppf_optloop_trace);
+}
+"""
+
+
+@pytest.fixture(scope="module")
+def decide(tmp_path_factory):
+    cxx = shutil.which(os.environ.get("CXX", "c++")) or shutil.which("g++") or shutil.which("clang++")
+    assert cxx, "a host C++ compiler is needed (the one oracle/Makefile builds the C oracle with)"
+    d = tmp_path_factory.mktemp("optloop")
+    src, so = d / "shim.cpp", d / "liboptloop_shim.so"
+    src.write_text(SHIM)
+    subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-shared", "-fPIC", "-I", CSRC, "-o", str(so), str(src)], check=True)
+    lib = ctypes.CDLL(str(so))
+    lib.shim_decide.restype = ctypes.c_int
+    lib.shim_decide.argtypes = [ctypes.POINTER(_hip.OptloopParams), ctypes.POINTER(_hip.OptloopRecord), ctypes.c_void_p, ctypes.c_int,
+                                ctypes.POINTER(_hip.OptloopTrace)]  # fmt: skip
+    lib.shim_control_words.restype = ctypes.c_ulong
+    lib.shim_control_words.argtypes = [ctypes.c_int, ctypes.POINTER(_hip.OptloopParams)]
+    return lib
+
+
+def metrics_row(pos=0.25, rot=0.25, mjac_deg=1.0, mjac_cm=0.0, n_self=0, n_env=0, tl=0.0):
+    m = np.zeros(16, dtype=np.float32)
+    m[0], m[2], m[4], m[5], m[9], m[10], m[6] = pos, rot, mjac_deg, mjac_cm, n_self, n_env, tl
+    return m
+
+
+OK = dict()  # every threshold met, no collision
+POSE_BAD = dict(pos=1.0)  # position error above its threshold: pose flag false, the next step is a pose step
+ROT_BAD = dict(rot=1.0)
+MJAC_BAD = dict(mjac_deg=4.0)  # both pose flags hold (-> differencing next) but the trajectory is not valid
+
+
+def seq(*steps):
+    """steps: (tl, kind) for S = 1, or (tl, [kind per trajectory]); TL is split evenly over the trajectories"""
+    out = []
+    for tl, kinds in steps:
+        kinds = kinds if isinstance(kinds, list) else [kinds]
+        out.append(np.stack([metrics_row(tl=tl / len(kinds), **k) for k in kinds]))
+    return out
+
+
+def run_python(mp, metrics_seq, S, **kw):
+    """the Python loop, stubbed as tests/test_loop_control.py stubs it (x_is_valid real)"""
+    calls, it = [], [0]
+
+    def pose(problem, state, params, return_residual=False):
+        calls.append("pose")
+        return state.x + 1.0
+
+    def full(problem, state, params, return_residual=False):
+        assert torch.equal(params.virtual_configs, state.x)
+        calls.append("diff")
+        return state.x + 100.0
+
+    def evaluate(problem, target, x, parallel_count):
+        m = torch.from_numpy(metrics_seq[it[0]].copy())
+        it[0] += 1
+        return m
+
+    mp.setattr(opt, "levenberg_marquardt_only_pose", pose)
+    mp.setattr(opt, "levenberg_marquardt_full", full)
+    mp.setattr(opt, "clamp_to_joint_limits", lambda robot, x, verbosity=0: x)
+    mp.setattr(opt, "evaluate_seeds", evaluate)
+    robot = types.SimpleNamespace(ndof=D)
+    problem = types.SimpleNamespace(robot=robot, n_timesteps=W, target_path=torch.zeros((W, 7)), constraints=CONSTRAINTS)
+    x0 = torch.zeros((S * W, D))
+    p = opt.OptimizationProblem(problem, CONSTRAINTS, x0.clone(), problem.target_path, 0, S, None)
+    st = opt.OptimizationState(x0.clone(), 0, 0.0)
+    args = dict(return_residuals=False, tmax_sec=None, max_n_steps=len(metrics_seq), return_if_valid_after_n_steps=len(metrics_seq),
+                convergence_threshold=0.25)  # fmt: skip
+    args.update(kw)
+    r = opt.run_lm_alternating_loss(p, st, ALT_LOSS_V2_1_DIFF, ALT_LOSS_V2_1_POSE, **args)
+    return calls, r
+
+
+def make_params(max_n_steps, return_if_valid_after_n_steps, convergence_threshold=0.25, on_pose_valid="differencing", per_trajectory=False,
+                self_ignored=False, env_ignored=False):  # fmt: skip
+    P = _hip.OptloopParams()
+    P.constraints = _hip.Constraints(CONSTRAINTS.max_allowed_position_error_cm, CONSTRAINTS.max_allowed_rotation_error_deg,
+                                     CONSTRAINTS.max_allowed_mjac_deg, CONSTRAINTS.max_allowed_mjac_cm, int(self_ignored), int(env_ignored))  # fmt: skip
+    P.max_n_steps, P.return_if_valid_after_n_steps = max_n_steps, -1 if return_if_valid_after_n_steps is None else return_if_valid_after_n_steps
+    P.on_pose_valid, P.per_trajectory = _hip.OPT_ON_POSE_VALID[on_pose_valid], int(per_trajectory)
+    P.trace_capacity, P.convergence_threshold = max_n_steps, convergence_threshold
+    return P
+
+
+def run_c(lib, metrics_seq, S, per_trajectory=False, **kw):
+    """what cppf_lm_optimize_enqueue's kernels do per iteration, with the same fake steps: a record's trajectories take the step its
+    mode names, the decision function sees the scripted metrics, a valid iteration snapshots x"""
+    max_n_steps = kw.pop("max_n_steps", len(metrics_seq))
+    riv = kw.pop("return_if_valid_after_n_steps", len(metrics_seq))
+    P = make_params(max_n_steps, riv, per_trajectory=per_trajectory, **kw)
+    C, G = (S, 1) if per_trajectory else (1, S)
+    words = _hip.optloop_initial_control(C, P.trace_capacity)
+    assert lib.shim_control_words(S, ctypes.byref(P)) == words.size
+    recs = [_hip.OptloopRecord.from_buffer_copy(words[c * 16 : (c + 1) * 16].tobytes()) for c in range(C)]
+    x, snapshot = torch.zeros((S * W, D)), torch.full((S * W, D), float("nan"))
+    calls = [[] for _ in range(C)]
+    traces = [[] for _ in range(C)]
+    for i in range(max_n_steps):
+        if all(r.mode == _hip.OPT_MODE_DONE for r in recs):
+            break
+        for c, rec in enumerate(recs):
+            if rec.mode == _hip.OPT_MODE_DONE:
+                continue
+            rows = slice(c * G * W, (c + 1) * G * W)
+            x[rows] += 1.0 if rec.mode == _hip.OPT_MODE_POSE else 100.0
+            calls[c].append("pose" if rec.mode == _hip.OPT_MODE_POSE else "diff")
+            m = np.ascontiguousarray(metrics_seq[i][c * G : (c + 1) * G], dtype=np.float32)
+            tr = _hip.OptloopTrace()
+            assert rec.n_steps == i
+            if lib.shim_decide(ctypes.byref(P), ctypes.byref(rec), m.ctypes.data, G, ctypes.byref(tr)):
+                snapshot[rows] = x[rows]
+            traces[c].append((tr.mode, tr.tl, tr.flags, tr.valid))
+    assert all(r.mode == _hip.OPT_MODE_DONE for r in recs), "max_n_steps iterations always end every record"
+    valid = [bool(r.is_valid) for r in recs]
+    if per_trajectory:
+        x_ret = x.clone()
+        for s in range(S):
+            if valid[s]:
+                x_ret[s * W : (s + 1) * W] = snapshot[s * W : (s + 1) * W]
+        seed = valid.index(True) if any(valid) else 0
+    else:
+        x_ret, seed = (snapshot if valid[0] else x), recs[0].valid_seed_idx
+    return calls, types.SimpleNamespace(x_opt=x_ret, n_steps_taken=max(r.i_final for r in recs), is_valid=any(valid),
+                                        parallel_seed_idx=seed, records=recs, traces=traces)  # fmt: skip
+
+
+def assert_same(py, c):
+    (calls_p, rp), (calls_c, rc) = py, c
+    assert calls_c[0] == calls_p
+    assert rc.n_steps_taken == rp.n_steps_taken and rc.is_valid == rp.is_valid and rc.parallel_seed_idx == rp.parallel_seed_idx
+    assert torch.equal(rc.x_opt, rp.x_opt)
+
+
+# ---- the scenarios of tests/test_loop_control.py ----------------------------------------------------------------------------------
+def test_leads_with_pose_and_switches_to_differencing_when_both_pose_flags_hold(decide, monkeypatch):
+    s = seq((10.0, POSE_BAD), (10.0, ROT_BAD), (10.0, MJAC_BAD), (9.0, POSE_BAD), (9.0, OK), (8.0, OK))
+    py, c = run_python(monkeypatch, s, 1), run_c(decide, s, 1)
+    assert py[0] == ["pose", "pose", "pose", "diff", "pose", "diff"] and py[1].n_steps_taken == 5 and py[1].is_valid
+    assert_same(py, c)
+    assert torch.equal(c[1].x_opt, torch.full((W, D), 4 * 1.0 + 2 * 100.0))
+    # the trace: step taken, TL, flags (position, rotation, mjac revolute, mjac prismatic, self, env), valid
+    assert [_hip.optloop_flags(t[2]) for t in c[1].traces[0]][:3] == [
+        (False, True, True, True, None, None), (True, False, True, True, None, None), (True, True, False, True, None, None)]  # fmt: skip
+    assert [t[3] for t in c[1].traces[0]] == [0, 0, 0, 0, 1, 1] and [t[1] for t in c[1].traces[0]] == [10.0, 10.0, 10.0, 9.0, 9.0, 8.0]
+
+
+def test_tl_convergence_stops_at_once_if_the_previous_step_was_valid(decide, monkeypatch):
+    s = seq((10.0, MJAC_BAD), (10.0, OK), (9.875, OK), (0.0, OK))
+    py, c = run_python(monkeypatch, s, 1), run_c(decide, s, 1)
+    assert py[0] == ["pose", "diff", "diff"] and py[1].n_steps_taken == 2
+    assert_same(py, c)
+    assert torch.equal(c[1].x_opt, torch.full((W, D), 1.0 + 100.0))  # the state after step 1, not after the converging step
+    assert c[1].traces[0][2][2:] == (-1, -1)  # validity was not evaluated in the converging iteration
+
+
+def test_converged_but_not_valid_keeps_going_until_a_valid_trajectory_shows_up(decide, monkeypatch):
+    s = seq((10.0, MJAC_BAD), (10.0, MJAC_BAD), (9.875, MJAC_BAD), (9.75, POSE_BAD), (9.75, OK), (1.0, OK))
+    py, c = run_python(monkeypatch, s, 1), run_c(decide, s, 1)
+    assert py[0] == ["pose", "diff", "diff", "diff", "pose"] and py[1].n_steps_taken == 4 and py[1].is_valid
+    assert_same(py, c)
+
+
+def test_a_tl_change_at_or_above_the_threshold_is_not_convergence(decide, monkeypatch):
+    s = seq((10.0, OK), (9.0, OK), (8.75, OK), (7.0, OK))  # 0.25 is AT the threshold: not below it
+    py, c = run_python(monkeypatch, s, 1), run_c(decide, s, 1)
+    assert py[0] == ["pose", "diff", "diff", "diff"] and py[1].n_steps_taken == 3
+    assert_same(py, c)
+
+
+def test_return_if_valid_after_n_steps(decide, monkeypatch):
+    s = seq((10.0, OK), *[(10.0 - k, POSE_BAD) for k in range(1, 8)])
+    kw = dict(return_if_valid_after_n_steps=2, on_pose_valid="continue")
+    py, c = run_python(monkeypatch, s, 1, **kw), run_c(decide, s, 1, **kw)
+    assert len(py[0]) == 4 and py[1].n_steps_taken == 3 and py[1].is_valid
+    assert_same(py, c)
+    assert torch.equal(c[1].x_opt, torch.full((W, D), 1.0))
+
+
+def test_never_valid_returns_the_current_x_after_max_n_steps(decide, monkeypatch):
+    s = seq(*[(10.0, POSE_BAD)] * 5)
+    py, c = run_python(monkeypatch, s, 1), run_c(decide, s, 1)
+    assert py[0] == ["pose"] * 5 and not py[1].is_valid and py[1].n_steps_taken == 4
+    assert_same(py, c)
+    assert torch.equal(c[1].x_opt, torch.full((W, D), 5.0))
+
+
+def test_on_pose_valid_stop_and_continue(decide, monkeypatch):
+    s = seq((10.0, POSE_BAD), (10.0, MJAC_BAD), (9.0, MJAC_BAD), (8.0, OK))
+    for mode in ("stop", "continue"):
+        py, c = run_python(monkeypatch, s, 1, on_pose_valid=mode), run_c(decide, s, 1, on_pose_valid=mode)
+        assert_same(py, c)
+    assert run_python(monkeypatch, s, 1, on_pose_valid="stop")[0] == ["pose", "pose"]
+
+
+def test_first_valid_trajectory_and_the_flags_of_the_last_one_examined(decide, monkeypatch):
+    """parallel_count = 3, one decision for all: the first trajectory in order that passes everything; the step that follows goes by the
+    flags of the LAST trajectory examined"""
+    s = seq((12.0, [POSE_BAD, dict(n_self=2), OK]), (12.0, [OK, OK, POSE_BAD]), (9.0, [MJAC_BAD, dict(n_env=1), ROT_BAD]), (6.0, [OK] * 3))
+    py, c = run_python(monkeypatch, s, 3), run_c(decide, s, 3)
+    assert py[1].parallel_seed_idx == 0 and py[0] == ["pose", "diff", "diff", "pose"]
+    assert_same(py, c)
+    assert _hip.optloop_flags(c[1].traces[0][0][2]) == (True, True, True, True, False, False)
+    assert _hip.optloop_flags(c[1].traces[0][2][2]) == (True, False, True, True, False, True)
+
+
+def test_argument_contract_of_the_device_loop_switches():
+    """sync_every / per_trajectory belong to device_loop=True; the reference's asserts come first either way"""
+    robot = types.SimpleNamespace(ndof=D)
+    problem = types.SimpleNamespace(robot=robot, n_timesteps=W, target_path=torch.zeros((W, 7)), constraints=CONSTRAINTS)
+    p = opt.OptimizationProblem(problem, CONSTRAINTS, torch.zeros((W, D)), problem.target_path, 0, 1, None)
+    st = opt.OptimizationState(torch.zeros((W, D)), 0, 0.0)
+    for kw in (dict(sync_every=2), dict(per_trajectory=True), dict(device_loop=True, sync_every=0)):
+        with pytest.raises(AssertionError):
+            opt.run_lm_alternating_loss(p, st, ALT_LOSS_V2_1_DIFF, ALT_LOSS_V2_1_POSE, False, None, 5, 5, 0.3, **kw)
+    with pytest.raises(AssertionError):
+        opt.run_lm_alternating_loss(p, st, ALT_LOSS_V2_1_DIFF, ALT_LOSS_V2_1_POSE, False, None, 5, 6, 0.3, device_loop=True)
+
+
+# ---- randomised sequences ---------------------------------------------------------------------------------------------------------
+def random_sequence(rng, S, n):
+    vals = dict(pos=(0.25, 0.25, 0.25, 0.5, 1.0), rot=(0.25, 0.25, 0.25, 0.5, 1.0), mjac_deg=(1.0, 1.0, 1.0, 2.0, 4.0),
+                mjac_cm=(0.0, 0.0, 0.5, 1.0, 2.0), n_self=(0, 0, 0, 0, 1, 3), n_env=(0, 0, 0, 0, 2))  # fmt: skip
+    out = []
+    tl = float(rng.randint(40, 120)) / 8
+    for _ in range(n):
+        tl = max(0.0, tl + float(rng.choice([-16, -4, -2, -1, -1, 0, 0, 1, 2])) / 8)
+        rows = [metrics_row(tl=float(rng.randint(0, 24)) / 8 if S > 1 else tl, **{k: v[rng.randint(len(v))] for k, v in vals.items()})
+                for _ in range(S)]  # fmt: skip
+        out.append(np.stack(rows))
+    return out
+
+
+@pytest.mark.parametrize("S", [1, 3])
+def test_randomised_sequences_take_the_same_decisions(decide, monkeypatch, S):
+    rng = np.random.RandomState(1234 + S)
+    n_valid = n_diff = n_stopped_early = 0
+    for case in range(2000):
+        n = int(rng.randint(1, 13))
+        s = random_sequence(rng, S, n)
+        kw = dict(return_if_valid_after_n_steps=int(rng.randint(0, n + 1)), convergence_threshold=float(rng.choice([0.125, 0.25, 1.0, 1e6])),
+                  on_pose_valid=str(rng.choice(["differencing", "differencing", "differencing", "stop", "continue"])))  # fmt: skip
+        py, c = run_python(monkeypatch, s, S, **kw), run_c(decide, s, S, **kw)
+        assert_same(py, c)
+        n_valid += py[1].is_valid
+        n_diff += "diff" in py[0]
+        n_stopped_early += len(py[0]) < n
+    # the generator reaches every branch often enough to mean something
+    assert n_valid > 300 and n_diff > 300 and n_stopped_early > 300, (n_valid, n_diff, n_stopped_early)
+
+
+def test_collisions_ignored_switches(decide, monkeypatch):
+    rng = np.random.RandomState(7)
+    for self_ignored, env_ignored in ((True, False), (False, True), (True, True)):
+        monkeypatch.setattr(opt_utils, "SELF_COLLISIONS_IGNORED", self_ignored)
+        monkeypatch.setattr(opt_utils, "ENV_COLLISIONS_IGNORED", env_ignored)
+        for case in range(200):
+            s = random_sequence(rng, 3, 8)
+            py = run_python(monkeypatch, s, 3)
+            assert_same(py, run_c(decide, s, 3, self_ignored=self_ignored, env_ignored=env_ignored))
+
+
+def test_per_trajectory_records_decide_like_separate_single_trajectory_loops(decide, monkeypatch):
+    """per_trajectory: every trajectory alternates and ends by its own flags -- record s of an S = 3 run takes exactly the decisions of
+    an S = 1 run on trajectory s's metrics, and the result is the lowest-index valid trajectory"""
+    rng = np.random.RandomState(99)
+    for case in range(300):
+        n = int(rng.randint(2, 11))
+        s = random_sequence(rng, 3, n)
+        kw = dict(return_if_valid_after_n_steps=int(rng.randint(0, n + 1)), convergence_threshold=float(rng.choice([0.25, 1.0])))
+        calls, r = run_c(decide, s, 3, per_trajectory=True, **kw)
+        singles = [run_python(monkeypatch, [m[t : t + 1] for m in s], 1, **kw) for t in range(3)]
+        for t in range(3):
+            assert calls[t] == singles[t][0]
+            assert r.records[t].i_final == singles[t][1].n_steps_taken and bool(r.records[t].is_valid) == singles[t][1].is_valid
+            assert torch.equal(r.x_opt[t * W : (t + 1) * W], singles[t][1].x_opt)
+        ok = [x[1].is_valid for x in singles]
+        assert r.is_valid == any(ok) and r.parallel_seed_idx == (ok.index(True) if any(ok) else 0)
+        assert r.n_steps_taken == max(x[1].n_steps_taken for x in singles)
