@@ -1231,6 +1231,28 @@ int cppf_lm_full_step(const cppf_robot* robot, const float* x_in, const float* t
 }  // extern "C"
 
 namespace {
+// Which elimination a coupled step of S trajectories of W waypoints resolves to on this handle (see the comments at the launches
+// in lm_full_step_gated): the parallel-in-time form, the row-per-lane form, or neither (the one-wavefront / one-lane kernels).
+// Depends on the sizes, the parameters and the handle's tuning only, so a caller can know it before it launches anything.
+struct FullStepForm {
+    bool use_pcr, use_rows;
+};
+FullStepForm full_step_form(const cppf_robot* robot, size_t n, int W, bool use_pose, bool var_coupling) {
+    const int t_pcr_rows = tune(robot, CPPF_TUNE_PCR_MAX_ROWS);
+    const bool g_pcr_lds = tune(robot, CPPF_TUNE_PCR_LDS) != 0;
+    const bool g_rows_pose = tune(robot, CPPF_TUNE_ROWS_POSE) != 0, g_full_rows = tune(robot, CPPF_TUNE_FULL_ROWS) != 0;
+    const size_t pcr_rows = t_pcr_rows >= 0 ? (size_t)t_pcr_rows : (size_t)((W <= 256 && g_pcr_lds) ? kPcrMaxRowsLds : kPcrMaxRowsGlobal);
+    const size_t pcr_limit = pcr_rows * (robot->desc.ndof <= 7 ? 100 : 50) / 100;
+    FullStepForm f;
+    f.use_pcr = !var_coupling && !use_pose && W <= 512 && n <= pcr_limit && robot->desc.ndof >= 3 && robot->desc.ndof <= 8;
+    f.use_rows = !var_coupling && !f.use_pcr && (!use_pose || g_rows_pose) && g_full_rows && robot->desc.ndof >= 3 &&
+                 robot->desc.ndof <= 12 && W <= (1 << 19);
+    return f;
+}
+const char* const kGatedFormRefusal =
+    "cppflow_hip: the device-side optimiser loop gates the parallel-in-time and the row-per-lane "
+    "elimination only (no pose block, no individually weighted differencing rows, CPPF_TUNE_FULL_ROWS on)";
+
 // cppf_lm_full_step; with a gate (the optimiser loop on the device) only the trajectories it opens are stepped
 int lm_full_step_gated(const cppf_robot* robot, const float* x_in, const float* target, const float* virtual_configs, int S, int W,
                        const cppf_full_params* params, float* work_blocks, float* work_G, float* work_y, float* x_out, void* stream,
@@ -1284,18 +1306,12 @@ int lm_full_step_gated(const cppf_robot* robot, const float* x_in, const float* 
     const bool var_coupling = prm.diff_mode != 0;
     float* const w2next = work_G + n * (size_t)(robot->desc.ndof * (robot->desc.ndof + 1) / 2);
     // which elimination kernel: see the comments at the launches below
-    const int t_pcr_rows = tune(robot, CPPF_TUNE_PCR_MAX_ROWS), t_pcr_lds = tune(robot, CPPF_TUNE_PCR_LDS);
+    const int t_pcr_lds = tune(robot, CPPF_TUNE_PCR_LDS);
     const bool g_pcr_lds = t_pcr_lds != 0, g_pcr_split = t_pcr_lds != 1;
-    const bool g_rows_pose = tune(robot, CPPF_TUNE_ROWS_POSE) != 0, g_full_rows = tune(robot, CPPF_TUNE_FULL_ROWS) != 0;
-    const size_t pcr_rows = t_pcr_rows >= 0 ? (size_t)t_pcr_rows : (size_t)((W <= 256 && g_pcr_lds) ? kPcrMaxRowsLds : kPcrMaxRowsGlobal);
-    const size_t pcr_limit = pcr_rows * (robot->desc.ndof <= 7 ? 100 : 50) / 100;
-    const bool use_pcr = !var_coupling && !prm.use_pose && W <= 512 && n <= pcr_limit && robot->desc.ndof >= 3 && robot->desc.ndof <= 8;
-    const bool use_rows = !var_coupling && !use_pcr && (!prm.use_pose || g_rows_pose) && g_full_rows && robot->desc.ndof >= 3 &&
-                          robot->desc.ndof <= 12 && W <= (1 << 19);
+    const FullStepForm form = full_step_form(robot, n, W, prm.use_pose != 0, var_coupling);
+    const bool use_pcr = form.use_pcr, use_rows = form.use_rows;
     prm.fold = use_rows || var_coupling;
-    if (gate.ctl != nullptr && !use_pcr && !use_rows)
-        return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: the device-side optimiser loop gates the parallel-in-time and the row-per-lane "
-                                          "elimination only (no pose block, no individually weighted differencing rows, CPPF_TUNE_FULL_ROWS on)");
+    if (gate.ctl != nullptr && !use_pcr && !use_rows) return fail(CPPF_ERR_UNSUPPORTED, kGatedFormRefusal);
     hipStream_t st = (hipStream_t)stream;
 #define CPPF_BODY                                                                                                     \
     if (n >= 131072)                                                                                                  \
@@ -1482,6 +1498,9 @@ int cppf_lm_optimize_enqueue(const cppf_robot* robot, float* x, const float* tar
         return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: the device-side optimiser loop needs the quad-shape pose step (ndof >= 6, S*W within its row limit)");
     if (params->diff.use_pose || params->diff.differencing_mode != 0)
         return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: the device-side optimiser loop takes a coupled step without pose block and without weighted differencing rows");
+    // ... and so is the elimination of the coupled step: decided here, before the pose step's launch writes x_new
+    const FullStepForm form = full_step_form(robot, n, W, false, false);
+    if (!form.use_pcr && !form.use_rows) return fail(CPPF_ERR_UNSUPPORTED, kGatedFormRefusal);
     if (n_iterations == 0) return CPPF_OK;
     CPPF_ENTER(robot);
     prm.n = (int)n;

@@ -184,6 +184,81 @@ def test_per_trajectory_mode_and_the_reference_rule_for_parallel_seeds(monkeypat
     problem.robot.set_obstacles([], [])
 
 
+@pytest.mark.parametrize("on_pose_valid", ["stop", "continue"])
+@pytest.mark.parametrize("name", ["panda__line", "fetch_arm__s__truncated"])
+def test_on_pose_valid_stop_and_continue_match_the_host_loop(name, on_pose_valid, monkeypatch):
+    """the two branches that replace the differencing step (stop once the pose is valid / keep taking pose steps), from a start near
+    an optimised path and from one far from it: same steps, same end, same bits as the host loop"""
+    problem, x_base = _base(name)
+    for k, width in enumerate((1e-3, 0.5)):
+        x0 = _starts(x_base, 1, 200 + k, (width,))
+        calls, h = _host(problem, x0, monkeypatch=monkeypatch, on_pose_valid=on_pose_valid)
+        d = _device(problem, x0, on_pose_valid=on_pose_valid)
+        print(f"{name} {on_pose_valid} width {width}: host n_steps_taken {h.n_steps_taken} valid {h.is_valid} steps {''.join(c[0] for c in calls)} | "
+              f"device n_steps_taken {d.n_steps_taken} valid {d.is_valid} steps {''.join(c[0] for c in _steps(d.trace[0]))}")
+        assert "diff" not in calls
+        assert _steps(d.trace[0]) == calls
+        assert d.n_steps_taken == h.n_steps_taken and d.is_valid == h.is_valid and d.parallel_seed_idx == h.parallel_seed_idx
+        assert torch.equal(d.x_opt, h.x_opt)
+    problem.robot.set_obstacles([], [])
+
+
+def _smooth_fetch_553():
+    """(problem, path): Fetch (8 joints), 553 waypoints -- beyond the parallel-in-time limit, so the coupled step is eliminated row per
+    lane by default -- with the target = FK of a smooth joint path that is free of self-collisions (checked here on the host) and
+    without obstacles: the path itself is a valid trajectory, starts near it end early, starts far from it do not"""
+    if "fetch__553" not in _cache:
+        import numpy as np
+
+        from cppflow_amd.data_type_utils import problem_from_arrays
+        from cppflow_amd.robots import get_robot
+        from tests import helpers as H
+
+        ch, W = H.chain("fetch"), 553
+        rng = np.random.RandomState(500)
+        q0 = rng.uniform(ch.lo + 0.3 * (ch.hi - ch.lo), ch.hi - 0.3 * (ch.hi - ch.lo))
+        step = 0.004 * rng.randn(W, ch.ndof)
+        step[:, ch.jtype == 1] *= 0.1
+        path = H.f32(np.clip(q0[None] + np.cumsum(step, axis=0), ch.lo + 0.01, ch.hi - 0.01))
+        assert not H.oracle32("fetch").masks(path, None, None, None, None)["self_mask"].any()
+        problem = problem_from_arrays(get_robot("fetch"), H.f32(H.oracle64("fetch").fk(path)), [], name="fetch__553", device=DEV)
+        _cache["fetch__553"] = (problem, torch.tensor(path, dtype=torch.float32, device=DEV))
+    return _cache["fetch__553"]
+
+
+@pytest.mark.parametrize("name,S,switches", [("fetch_arm__s__truncated", 8, {}), ("fetch_arm__s__truncated", 8, {"pcr_max_rows": 0}),
+                                             ("fetch__553", 3, {})])  # fmt: skip
+def test_per_trajectory_at_an_unaligned_width_and_on_the_row_per_lane_path(name, S, switches, monkeypatch):
+    """per_trajectory=True where a trajectory boundary falls inside a wavefront (W is not a multiple of 16) and where the coupled step
+    is eliminated one trajectory per lane group (pcr_max_rows = 0; W > 512): every trajectory takes the steps, ends at the iteration
+    and returns the bits of a separate HOST loop of the same start under the same tuning.
+    The W > 512 case is Fetch at the 553 waypoints of fetch__hello with a reachable target (`_smooth_fetch_553`), not fetch__hello's own
+    target: from the search path of fetch__hello (24 or 175 candidates) every start of width 0, 1e-3 and 0.3 alike takes 20 pose steps
+    and is never valid (host n_steps_taken 19, valid False, steps pppppppppppppppppppp), so no coupled step would run and no two
+    trajectories would differ in what they need."""
+    problem, x_base = _smooth_fetch_553() if name == "fetch__553" else _base(name)
+    W, rb = problem.n_timesteps, problem.robot
+    assert W % 16 != 0
+    widths = (0.0, 0.3, 1e-3, 0.0, 0.6, 2e-2, 1e-3, 0.3)[:S]
+    x0 = _starts(x_base, S, 5, widths)
+    try:
+        for key, value in switches.items():
+            rb.debug_set(key, value)
+        per = _device(problem, x0, S=S, per_trajectory=True)
+        for s in range(S):
+            calls, h = _host(problem, x0[s * W : (s + 1) * W].contiguous(), monkeypatch=monkeypatch)
+            print(f"trajectory {s} width {widths[s]}: host n_steps_taken {h.n_steps_taken} valid {h.is_valid} steps {''.join(c[0] for c in calls)}")
+            assert _steps(per.trace[s]) == calls
+            assert max(per.records[s].i_final, 0) == h.n_steps_taken and bool(per.records[s].is_valid) == h.is_valid
+            assert torch.equal(per.x_opt[s * W : (s + 1) * W], h.x_opt)
+        assert len({len(t) for t in per.trace}) > 1, "the starts were meant to need different numbers of iterations"
+        assert any("diff" in _steps(t) for t in per.trace), "no trajectory took a coupled step"
+    finally:
+        for key in switches:
+            rb.debug_set(key, None)
+        rb.set_obstacles([], [])
+
+
 def test_planner_with_the_device_optimizer_returns_the_same_plan():
     from cppflow_amd.data_types import PlannerSettings
     from cppflow_amd.planners import CppFlowPlanner, LmIkSeedProvider

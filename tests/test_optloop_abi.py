@@ -139,6 +139,24 @@ def test_bad_arguments_are_refused_before_any_launch_and_sizes_are_as_documented
             P = _params(**pkw)
             rc = lib.cppf_lm_optimize_enqueue(h, buf, buf, a["S"], a["W"], ctypes.byref(P), buf, buf, 1, None)
             assert rc == _hip.CPPF_ERR_UNSUPPORTED, (pkw, akw, rc, lib.cppf_last_error().decode())
+        # ... and so is a coupled step that would resolve to an elimination without a gate (neither the parallel-in-time nor the
+        # row-per-lane form): the choice depends on S, W, ndof and the handle's tuning only, so it is refused up front as well --
+        # on this host-only handle, i.e. before the device is selected, let alone the pose step launched
+        keys = _hip.TUNE_KEYS
+        try:
+            assert lib.cppf_debug_set(h, keys["full_rows"], 0) == _hip.CPPF_OK
+            for tune, a in (({"pcr_max_rows": 0}, dict(S=1, W=16)), ({"pcr_max_rows": 0}, dict(S=3, W=200)), ({}, dict(S=1, W=600)),
+                            ({"pcr_max_rows": 100}, dict(S=2, W=64))):  # fmt: skip
+                for k, v in tune.items():
+                    assert lib.cppf_debug_set(h, keys[k], v) == _hip.CPPF_OK
+                P = _params()
+                rc = lib.cppf_lm_optimize_enqueue(h, buf, buf, a["S"], a["W"], ctypes.byref(P), buf, buf, 1, None)
+                assert rc == _hip.CPPF_ERR_UNSUPPORTED, (tune, a, rc, lib.cppf_last_error().decode())
+                assert "elimination" in lib.cppf_last_error().decode()
+                assert lib.cppf_debug_set(h, keys["pcr_max_rows"], _hip.TUNE_DEFAULT) == _hip.CPPF_OK
+        finally:
+            for k in ("full_rows", "pcr_max_rows"):
+                assert lib.cppf_debug_set(h, keys[k], _hip.TUNE_DEFAULT) == _hip.CPPF_OK
         # zero iterations: nothing to do, nothing touched
         P = _params()
         assert lib.cppf_lm_optimize_enqueue(h, buf, buf, 1, 16, ctypes.byref(P), buf, buf, 0, None) == _hip.CPPF_OK

@@ -1,7 +1,7 @@
 """The decision function of the device-side optimiser loop (`optloop_decide`, cppflow_amd/csrc/kernels_optloop.h) against the Python
 loop it restates (run_lm_alternating_loss, cppflow_amd/optimization.py).  CPU only: the function is `__host__ __device__` without a
-HIP intrinsic, so the host C++ compiler builds it here (into pytest's tmp_path, behind a ten-line extern "C" shim) and ctypes drives
-it -- no GPU, no hipcc.
+HIP intrinsic, so the host C++ compiler builds it here (into pytest's tmp_path, behind a ten-line extern "C" shim,
+tests/optloop_shim.py) and ctypes drives it -- no GPU, no hipcc.
 
 Yardstick: the existing Python loop with its step functions stubbed the way tests/test_loop_control.py stubs them (pose step: x + 1,
 differencing step: x + 100, clamp: identity, evaluate_seeds: the scripted [S,16] metrics); `x_is_valid` is the real one, fed those
@@ -13,9 +13,6 @@ the TL values and the convergence threshold are all small multiples of 1/8: exac
 exact in fp32 in any order (a value equal to its threshold is then "not below" on both sides, deterministically)."""
 
 import ctypes
-import os
-import shutil
-import subprocess
 import types
 
 import numpy as np
@@ -27,40 +24,16 @@ from cppflow_amd import optimization as opt
 from cppflow_amd import optimization_utils as opt_utils
 from cppflow_amd.data_types import Constraints
 from cppflow_amd.lm_hyper_parameters import ALT_LOSS_V2_1_DIFF, ALT_LOSS_V2_1_POSE
+from tests.optloop_shim import build_shim
 
-CSRC = os.path.join(os.path.dirname(os.path.abspath(opt.__file__)), "csrc")
 W, D = 4, 3
 CONSTRAINTS = Constraints(max_allowed_position_error_cm=0.5, max_allowed_rotation_error_deg=0.5, max_allowed_mjac_deg=2.0,
                           max_allowed_mjac_cm=1.0)  # fmt: skip
 
-SHIM = """
-#include "kernels_optloop.h"
-extern "C" int shim_decide(const cppf_optloop_params* P, cppf_optloop_record* rec, const float* metrics, int G,
-                           cppf_optloop_trace* tr) {
-    return optloop_decide(*P, *rec, metrics, G, *tr);
-}
-extern "C" unsigned long shim_control_words(int S, const cppf_optloop_params* P) { return (unsigned long)optloop_control_words(S, *P); }
-extern "C" int shim_sizeof(int which) {
-    return which == 0 ? (int)sizeof(cppf_optloop_params) : which == 1 ? (int)sizeof(cppf_optloop_record) : (int)sizeof(cppf_optloop_trace);
-}
-"""
-
 
 @pytest.fixture(scope="module")
 def decide(tmp_path_factory):
-    cxx = shutil.which(os.environ.get("CXX", "c++")) or shutil.which("g++") or shutil.which("clang++")
-    assert cxx, "a host C++ compiler is needed (the one oracle/Makefile builds the C oracle with)"
-    d = tmp_path_factory.mktemp("optloop")
-    src, so = d / "shim.cpp", d / "liboptloop_shim.so"
-    src.write_text(SHIM)
-    subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-shared", "-fPIC", "-I", CSRC, "-o", str(so), str(src)], check=True)
-    lib = ctypes.CDLL(str(so))
-    lib.shim_decide.restype = ctypes.c_int
-    lib.shim_decide.argtypes = [ctypes.POINTER(_hip.OptloopParams), ctypes.POINTER(_hip.OptloopRecord), ctypes.c_void_p, ctypes.c_int,
-                                ctypes.POINTER(_hip.OptloopTrace)]  # fmt: skip
-    lib.shim_control_words.restype = ctypes.c_ulong
-    lib.shim_control_words.argtypes = [ctypes.c_int, ctypes.POINTER(_hip.OptloopParams)]
-    return lib
+    return build_shim(tmp_path_factory.mktemp("optloop"))  # (the shim and its build: tests/optloop_shim.py)
 
 
 def metrics_row(pos=0.25, rot=0.25, mjac_deg=1.0, mjac_cm=0.0, n_self=0, n_env=0, tl=0.0):
