@@ -23,6 +23,7 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/cppflow_hip_debug.h"
@@ -88,11 +89,9 @@ int fail(int code, const std::string& msg) {
 
 inline unsigned grid_for(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
-}  // namespace
-
-namespace {
 struct RtcModule;  // rtc_specialize.h
-}
+
+}  // namespace
 
 struct cppf_robot {
     cppf_robot_desc desc;
@@ -219,48 +218,57 @@ int find_static_robot(const cppf_robot_desc& d) {
     return -1;
 }
 
-// dispatch of the heavy kernels on the robot: a generated table if the description matched one, else the generic
-// instantiation for its ndof.  Inside __VA_ARGS__ the accessor type is `RB`.
-#define CPPF_STATIC_CASE(idx, Type)       \
-    case idx: {                           \
-        using RB = StaRobot<Type>;        \
-        CPPF_BODY;                        \
-    } break;
+// ---- dispatch: which instantiation a launch takes ---------------------------------------------------------------------------
+// Each dispatcher calls a generic lambda with a tag VALUE; the lambda names what the tag carries (`constexpr int D =
+// decltype(dof)::D;`, `using RB = typename decltype(tag)::type;`) and returns a CPPF_* code, which the dispatcher hands on.
+template <int N>
+struct Dof {
+    static constexpr int D = N;
+};
+template <class T>
+struct RobotTag {
+    using type = T;  // the kernels' accessor type: DynRobot<D> or StaRobot<generated table>
+};
 
-#define CPPF_DISPATCH_RB(robot)                                                                                       \
-    if ((robot)->static_id >= 0 && !tune((robot), CPPF_TUNE_FORCE_GENERIC)) {                                                                \
-        switch ((robot)->static_id) { CPPF_FOR_EACH_STATIC_ROBOT(CPPF_STATIC_CASE) default: break; }                  \
-    } else {                                                                                                          \
-        switch ((robot)->desc.ndof) {                                                                                 \
-            case 3: { using RB = DynRobot<3>; CPPF_BODY; } break;                                                     \
-            case 4: { using RB = DynRobot<4>; CPPF_BODY; } break;                                                     \
-            case 5: { using RB = DynRobot<5>; CPPF_BODY; } break;                                                     \
-            case 6: { using RB = DynRobot<6>; CPPF_BODY; } break;                                                     \
-            case 7: { using RB = DynRobot<7>; CPPF_BODY; } break;                                                     \
-            case 8: { using RB = DynRobot<8>; CPPF_BODY; } break;                                                     \
-            case 9: { using RB = DynRobot<9>; CPPF_BODY; } break;                                                     \
-            case 10: { using RB = DynRobot<10>; CPPF_BODY; } break;                                                   \
-            case 11: { using RB = DynRobot<11>; CPPF_BODY; } break;                                                   \
-            case 12: { using RB = DynRobot<12>; CPPF_BODY; } break;                                                   \
-            default: return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: kernels are built for ndof in 3..12");     \
-        }                                                                                                             \
+// on ndof: the light kernels are instantiated for the degrees of freedom of the shipped robots
+template <class F>
+int for_ndof(int d, F&& f) {
+    switch (d) {
+        case 3: return f(Dof<3>{});
+        case 4: return f(Dof<4>{});
+        case 5: return f(Dof<5>{});
+        case 6: return f(Dof<6>{});
+        case 7: return f(Dof<7>{});
+        case 8: return f(Dof<8>{});
+        case 9: return f(Dof<9>{});
+        case 10: return f(Dof<10>{});
+        case 11: return f(Dof<11>{});
+        case 12: return f(Dof<12>{});
+        default: return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: kernels are built for ndof in 3..12");
     }
+}
 
-// the generic instantiations only (the caller has dealt with the generated tables)
-#define CPPF_DISPATCH_DYN(robot)                                                                                      \
-    switch ((robot)->desc.ndof) {                                                                                     \
-        case 3: { using RB = DynRobot<3>; CPPF_BODY; } break;                                                         \
-        case 4: { using RB = DynRobot<4>; CPPF_BODY; } break;                                                         \
-        case 5: { using RB = DynRobot<5>; CPPF_BODY; } break;                                                         \
-        case 6: { using RB = DynRobot<6>; CPPF_BODY; } break;                                                         \
-        case 7: { using RB = DynRobot<7>; CPPF_BODY; } break;                                                         \
-        case 8: { using RB = DynRobot<8>; CPPF_BODY; } break;                                                         \
-        case 9: { using RB = DynRobot<9>; CPPF_BODY; } break;                                                         \
-        case 10: { using RB = DynRobot<10>; CPPF_BODY; } break;                                                       \
-        case 11: { using RB = DynRobot<11>; CPPF_BODY; } break;                                                       \
-        case 12: { using RB = DynRobot<12>; CPPF_BODY; } break;                                                       \
-        default: return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: kernels are built for ndof in 3..12");         \
+// the generic instantiations of the heavy kernels only (the caller has dealt with the generated tables)
+template <class F>
+int for_dyn_robot(const cppf_robot* rb, F&& f) {
+    return for_ndof(rb->desc.ndof, [&](auto dof) { return f(RobotTag<DynRobot<decltype(dof)::D>>{}); });
+}
+
+// does a launch on this handle take the kernels of a generated table?
+inline bool use_table(const cppf_robot* rb) { return rb->static_id >= 0 && !tune(rb, CPPF_TUNE_FORCE_GENERIC); }
+
+// the heavy kernels on the robot: a generated table if the description matched one, else the generic instantiation for its ndof
+template <class F>
+int for_robot(const cppf_robot* rb, F&& f) {
+    if (!use_table(rb)) return for_dyn_robot(rb, f);
+    switch (rb->static_id) {
+#define CPPF_TABLE_CASE(idx, Type) \
+    case idx: return f(RobotTag<StaRobot<Type>>{});
+        CPPF_FOR_EACH_STATIC_ROBOT(CPPF_TABLE_CASE)
+#undef CPPF_TABLE_CASE
+        default: return CPPF_OK;  // (a matched table without a case here: nothing is launched)
     }
+}
 
 constexpr int kNoDevice = -12345;  // cppf_robot_create's host-only mode (no HIP call), for cppf_debug_rtc_compile
 // coupled step: parallel-in-time elimination up to this many (trajectory, waypoint) rows -- the measured crossovers with the
@@ -272,30 +280,18 @@ constexpr int kPcrMaxRowsLds = 131072, kPcrMaxRowsGlobal = 49152;
 // per lane there and lost 9 %; profiles/r4_pcr_ab.txt
 constexpr int kPcrSplitMaxD = 8;
 
-// dispatch on ndof: the light kernels are instantiated for the degrees of freedom of the shipped robots
-#define CPPF_DISPATCH_D(d, ...)                                                                               \
-    switch (d) {                                                                                              \
-        case 3: { constexpr int D = 3; __VA_ARGS__; } break;                                                  \
-        case 4: { constexpr int D = 4; __VA_ARGS__; } break;                                                  \
-        case 5: { constexpr int D = 5; __VA_ARGS__; } break;                                                  \
-        case 6: { constexpr int D = 6; __VA_ARGS__; } break;                                                  \
-        case 7: { constexpr int D = 7; __VA_ARGS__; } break;                                                  \
-        case 8: { constexpr int D = 8; __VA_ARGS__; } break;                                                  \
-        case 9: { constexpr int D = 9; __VA_ARGS__; } break;                                                  \
-        case 10: { constexpr int D = 10; __VA_ARGS__; } break;                                                \
-        case 11: { constexpr int D = 11; __VA_ARGS__; } break;                                                \
-        case 12: { constexpr int D = 12; __VA_ARGS__; } break;                                                \
-        default: return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: kernels are built for ndof in 3..12");  \
-    }
-
 // launch one of the run-time-specialised kernels of a handle (same argument lists as the compiled-in instantiations)
-int rtc_launch(const cppf_robot* rb, RtcKernel which, unsigned grid, size_t lds, hipStream_t st, void** args);
+int rtc_launch(const cppf_robot* rb, RtcKernel which, unsigned grid, size_t lds, hipStream_t st, void** args) {
+    hipFunction_t f = rb->rtc->fn[which];
+    if (!f) return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: this kernel is not part of the handle's specialised module");
+    CPPF_HIP(hipModuleLaunchKernel(f, grid, 1, 1, (unsigned)kBlock, 1, 1, (unsigned)lds, st, args, nullptr));
+    return CPPF_OK;
+}
 
 inline bool use_rtc(const cppf_robot* rb) { return rb->rtc != nullptr && !tune(rb, CPPF_TUNE_FORCE_GENERIC); }
 
-int check_launch(const cppf_robot* rb) {
+int check_launch() {
     CPPF_HIP(hipGetLastError());
-    (void)rb;
     return CPPF_OK;
 }
 
@@ -328,15 +324,6 @@ struct DeviceGuard {
         return fail(CPPF_ERR_HIP, std::string("cppflow_hip: selecting the robot's device failed: ") +               \
                                       hipGetErrorString(device_guard__.err))
 
-}  // namespace
-
-namespace {
-int rtc_launch(const cppf_robot* rb, RtcKernel which, unsigned grid, size_t lds, hipStream_t st, void** args) {
-    hipFunction_t f = rb->rtc->fn[which];
-    if (!f) return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: this kernel is not part of the handle's specialised module");
-    CPPF_HIP(hipModuleLaunchKernel(f, grid, 1, 1, (unsigned)kBlock, 1, 1, (unsigned)lds, st, args, nullptr));
-    return CPPF_OK;
-}
 }  // namespace
 
 extern "C" {
@@ -606,9 +593,10 @@ int cppf_forward_kinematics(const cppf_robot* robot, const float* x, int n, floa
     if (n == 0) return CPPF_OK;
     CPPF_REQUIRE(x && poses, "x / poses is NULL");
     hipStream_t st = (hipStream_t)stream;
-    CPPF_DISPATCH_D(robot->desc.ndof, hipLaunchKernelGGL((fk_kernel<D>), dim3(grid_for(n)), dim3(kBlock), 0, st,
-                                                        robot->chain, robot->coll, n, x, poses));
-    return check_launch(robot);
+    return for_ndof(robot->desc.ndof, [&](auto dof) {
+        hipLaunchKernelGGL((fk_kernel<decltype(dof)::D>), dim3(grid_for(n)), dim3(kBlock), 0, st, robot->chain, robot->coll, n, x, poses);
+        return check_launch();
+    });
 }
 
 int cppf_jacobian(const cppf_robot* robot, const float* x, int n, float* J, void* stream) {
@@ -617,9 +605,10 @@ int cppf_jacobian(const cppf_robot* robot, const float* x, int n, float* J, void
     if (n == 0) return CPPF_OK;
     CPPF_REQUIRE(x && J, "x / J is NULL");
     hipStream_t st = (hipStream_t)stream;
-    CPPF_DISPATCH_D(robot->desc.ndof, hipLaunchKernelGGL((jacobian_kernel<D>), dim3(grid_for(n)), dim3(kBlock), 0, st,
-                                                        robot->chain, robot->coll, n, x, J));
-    return check_launch(robot);
+    return for_ndof(robot->desc.ndof, [&](auto dof) {
+        hipLaunchKernelGGL((jacobian_kernel<decltype(dof)::D>), dim3(grid_for(n)), dim3(kBlock), 0, st, robot->chain, robot->coll, n, x, J);
+        return check_launch();
+    });
 }
 
 int cppf_pose_errors(const cppf_robot* robot, const float* x, const float* target, int S, int W, float* e,
@@ -631,9 +620,11 @@ int cppf_pose_errors(const cppf_robot* robot, const float* x, const float* targe
     CPPF_REQUIRE(n <= 0x7fffffffu, "S*W exceeds 2^31-1 rows");
     CPPF_REQUIRE(x && target, "x / target is NULL");
     hipStream_t st = (hipStream_t)stream;
-    CPPF_DISPATCH_D(robot->desc.ndof, hipLaunchKernelGGL((pose_errors_kernel<D>), dim3(grid_for(n)), dim3(kBlock), 0, st,
-                                                        robot->chain, robot->coll, (int)n, W, x, target, e, current_poses));
-    return check_launch(robot);
+    return for_ndof(robot->desc.ndof, [&](auto dof) {
+        hipLaunchKernelGGL((pose_errors_kernel<decltype(dof)::D>), dim3(grid_for(n)), dim3(kBlock), 0, st, robot->chain, robot->coll,
+                           (int)n, W, x, target, e, current_poses);
+        return check_launch();
+    });
 }
 
 int cppf_clamp_to_joint_limits(const cppf_robot* robot, float* x, int n, void* stream) {
@@ -643,7 +634,7 @@ int cppf_clamp_to_joint_limits(const cppf_robot* robot, float* x, int n, void* s
     CPPF_REQUIRE(x, "x is NULL");
     const size_t total = (size_t)n * robot->desc.ndof;
     hipLaunchKernelGGL(clamp_kernel, dim3(grid_for(total)), dim3(kBlock), 0, (hipStream_t)stream, robot->chain, total, x);
-    return check_launch(robot);
+    return check_launch();
 }
 
 }  // extern "C"
@@ -709,7 +700,7 @@ int launch_fused_rows(const cppf_robot* robot, int coll, size_t n_rows, unsigned
     // Dynamic LDS: what the generic kernels stage their capsules in, or -- for a launch of at most two workgroups per compute
     // unit -- a claim sized so that only two workgroups FIT on one (fused_spread_lds): several such launches in flight then
     // spread over the whole chip instead of stacking four deep on the compute units the dispatcher tries first.
-    const bool generic = !use_rtc(robot) && !(robot->static_id >= 0 && !tune(robot, CPPF_TUNE_FORCE_GENERIC));
+    const bool generic = !use_rtc(robot) && !use_table(robot);
     const size_t spread = fused_spread_lds(robot, n_rows);
     const size_t lds_need = (generic && coll) ? robot->lds_bytes : 0;
     // the generic kernels stage 6 floats per capsule per lane: with the gate's slots beside them, 12 joints x 24 capsules no longer
@@ -726,7 +717,7 @@ int launch_fused_rows(const cppf_robot* robot, int coll, size_t n_rows, unsigned
     {
         const unsigned long long slots = (unsigned long long)(robot->cu_count > 0 ? robot->cu_count : 256) * 4ull;  // workgroups of 256 rows at four wavefronts per SIMD
         const int d = robot->desc.ndof;
-        const bool four = (use_rtc(robot) || (robot->static_id >= 0 && !tune(robot, CPPF_TUNE_FORCE_GENERIC))) ? d <= 7 : d <= 6;
+        const bool four = (use_rtc(robot) || use_table(robot)) ? d <= 7 : d <= 6;
         if (!four || (unsigned long long)grid * 4ull < 3ull * slots || (unsigned long long)grid > slots) fa.prm.pace_ticks = 0;
     }
     fa.single = single;
@@ -740,70 +731,255 @@ int launch_fused_rows(const cppf_robot* robot, int coll, size_t n_rows, unsigned
             return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: no fused kernel for this generated table");
     } else {
         const size_t lds = std::max(lds_need, spread);
-#define CPPF_BODY                                                                                          \
-    if (coll == 2)                                                                                         \
-        hipLaunchKernelGGL((lm_fused_kernel<RB, 2>), dim3(grid), dim3(kBlock), lds, st, fa.ch, fa.co, fa.prm, fa.single, fa.table);               \
-    else if (coll == 1)                                                                                    \
-        hipLaunchKernelGGL((lm_fused_kernel<RB, 1>), dim3(grid), dim3(kBlock), lds, st, fa.ch, fa.co, fa.prm, fa.single, fa.table);               \
-    else                                                                                                   \
-        hipLaunchKernelGGL((lm_fused_kernel<RB, 0>), dim3(grid), dim3(kBlock), lds, st, fa.ch, fa.co, fa.prm, fa.single, fa.table)
-        CPPF_DISPATCH_DYN(robot)
-#undef CPPF_BODY
+        const int rc = for_dyn_robot(robot, [&](auto tag) {
+            using RB = typename decltype(tag)::type;
+            if (coll == 2)
+                hipLaunchKernelGGL((lm_fused_kernel<RB, 2>), dim3(grid), dim3(kBlock), lds, st, fa.ch, fa.co, fa.prm, fa.single, fa.table);
+            else if (coll == 1)
+                hipLaunchKernelGGL((lm_fused_kernel<RB, 1>), dim3(grid), dim3(kBlock), lds, st, fa.ch, fa.co, fa.prm, fa.single, fa.table);
+            else
+                hipLaunchKernelGGL((lm_fused_kernel<RB, 0>), dim3(grid), dim3(kBlock), lds, st, fa.ch, fa.co, fa.prm, fa.single, fa.table);
+            return CPPF_OK;
+        });
+        if (rc) return rc;
     }
-    return check_launch(robot);
+    return check_launch();
 }
 
-// One launch of the quad-shape kernel (kernels_quad.h) over n rows; `gate` = { NULL } unless the optimiser loop on the device asks
+// the one spelling of the quad-shape kernel's launch (kernels_quad.h); launch_quad picks the instantiation
+template <class RB, int COLL, bool MFMA>
+void launch_quad_kernel(const cppf_robot* robot, unsigned grid, size_t lds, hipStream_t st, const LmK& prm, const float* x_in,
+                        const float* target, const cppf_lm_outputs& oq, const uint4* tab, const StepGateK gate) {
+    hipLaunchKernelGGL((lm_quad_kernel<RB, COLL, MFMA>), dim3(grid), dim3(kBlock), lds, st, robot->chain, robot->coll, prm, x_in, target,
+                       oq, tab, gate);
+}
+
+// One launch of the quad-shape kernel over n rows; `gate` = { NULL } unless the optimiser loop on the device asks
 int launch_quad(const cppf_robot* robot, bool coll, size_t n, hipStream_t st, const LmK& prm, const float* x_in, const float* target,
                 const cppf_lm_outputs& oq, const StepGateK gate) {
-        const unsigned grid = (unsigned)((n + kQuadRows - 1) / kQuadRows);
-        const size_t lds_q = coll ? sizeof(float) * (4 * (CPPF_MAX_PAIRS + CPPF_MAX_CAPSULES) +
-                                                     (size_t)kQuadRows * quad_row_stride(robot->coll.ncaps))
-                                  : 0;
-        const uint4* tab = static_cast<const uint4*>(robot->d_quad);
-        const bool mfma = tune(robot, CPPF_TUNE_QUAD_MFMA) && robot->static_id >= 0 && !tune(robot, CPPF_TUNE_FORCE_GENERIC);
-        if (use_rtc(robot) && robot->rtc->fn[RTC_QUAD0]) {
-            void* args[] = {(void*)&robot->chain, (void*)&robot->coll, (void*)&prm, (void*)&x_in, (void*)&target, (void*)&oq, (void*)&tab, (void*)&gate};
-            if (int rc = rtc_launch(robot, coll ? RTC_QUAD1 : RTC_QUAD0, grid, lds_q, st, args)) return rc;
-        } else {
-#define CPPF_BODY                                                                                                          \
-    if constexpr (RB::D >= 6) {                                                                                            \
-        if (coll) {                                                                                                        \
-            if constexpr (RB::kStatic) {                                                                                   \
-                if (mfma)                                                                                                  \
-                    hipLaunchKernelGGL((lm_quad_kernel<RB, 1, true>), dim3(grid), dim3(kBlock), lds_q, st, robot->chain,    \
-                                       robot->coll, prm, x_in, target, oq, tab, gate);                                           \
-                else                                                                                                       \
-                    hipLaunchKernelGGL((lm_quad_kernel<RB, 1, false>), dim3(grid), dim3(kBlock), lds_q, st, robot->chain,   \
-                                       robot->coll, prm, x_in, target, oq, tab, gate);                                           \
-            } else {                                                                                                       \
-                hipLaunchKernelGGL((lm_quad_kernel<RB, 1, false>), dim3(grid), dim3(kBlock), lds_q, st, robot->chain,       \
-                                   robot->coll, prm, x_in, target, oq, tab, gate);                                               \
-            }                                                                                                              \
-        } else {                                                                                                           \
-            if constexpr (RB::kStatic) {                                                                                   \
-                if (mfma)                                                                                                  \
-                    hipLaunchKernelGGL((lm_quad_kernel<RB, 0, true>), dim3(grid), dim3(kBlock), 0, st, robot->chain,        \
-                                       robot->coll, prm, x_in, target, oq, tab, gate);                                           \
-                else                                                                                                       \
-                    hipLaunchKernelGGL((lm_quad_kernel<RB, 0, false>), dim3(grid), dim3(kBlock), 0, st, robot->chain,       \
-                                       robot->coll, prm, x_in, target, oq, tab, gate);                                           \
-            } else {                                                                                                       \
-                hipLaunchKernelGGL((lm_quad_kernel<RB, 0, false>), dim3(grid), dim3(kBlock), 0, st, robot->chain,           \
-                                   robot->coll, prm, x_in, target, oq, tab, gate);                                               \
-            }                                                                                                              \
-        }                                                                                                                  \
+    const unsigned grid = (unsigned)((n + kQuadRows - 1) / kQuadRows);
+    const size_t lds_q = coll ? sizeof(float) * (4 * (CPPF_MAX_PAIRS + CPPF_MAX_CAPSULES) +
+                                                 (size_t)kQuadRows * quad_row_stride(robot->coll.ncaps))
+                              : 0;
+    const uint4* tab = static_cast<const uint4*>(robot->d_quad);
+    const bool mfma = tune(robot, CPPF_TUNE_QUAD_MFMA) && use_table(robot);
+    if (use_rtc(robot) && robot->rtc->fn[RTC_QUAD0]) {
+        void* args[] = {(void*)&robot->chain, (void*)&robot->coll, (void*)&prm, (void*)&x_in, (void*)&target, (void*)&oq, (void*)&tab, (void*)&gate};
+        return rtc_launch(robot, coll ? RTC_QUAD1 : RTC_QUAD0, grid, lds_q, st, args);
     }
-        CPPF_DISPATCH_RB(robot)
-#undef CPPF_BODY
+    return for_robot(robot, [&](auto tag) {
+        using RB = typename decltype(tag)::type;
+        if constexpr (RB::D >= 6) {  // (the quad shape solves the dual 6x6 system)
+            constexpr bool kTable = RB::kStatic;  // the MFMA form is instantiated for the generated tables only
+            const auto launch = coll ? (mfma ? launch_quad_kernel<RB, 1, kTable> : launch_quad_kernel<RB, 1, false>)
+                                     : (mfma ? launch_quad_kernel<RB, 0, kTable> : launch_quad_kernel<RB, 0, false>);
+            launch(robot, grid, lds_q, st, prm, x_in, target, oq, tab, gate);
         }
-    return CPPF_OK;
+        return CPPF_OK;
+    });
 }
 
 inline bool quad_possible(const cppf_robot* robot, const cppf_lm_outputs& out) {
     return robot->desc.ndof >= 6 && !out.J_out && !out.e_out && !out.min_self && !out.min_env &&
            (!out.seed_summary || (out.x_out && out.pos_err_m && out.rot_err_rad && out.self_mask && out.env_mask && out.jlim_mask &&
                                   out.ext_cost));
+}
+
+// cppf_collision_masks; with a gate (the optimiser loop on the device) only the trajectories it opens are evaluated
+int collision_masks_gated(const cppf_robot* robot, const float* q, int S, int W, uint8_t* self_mask, uint8_t* env_mask,
+                          uint8_t* jlim_mask, float* ext_cost, float* min_self, float* min_env, void* stream, const StepGateK gate) {
+    CPPF_ENTER(robot);
+    CPPF_REQUIRE(S >= 0 && W >= 0, "S / W < 0");
+    const size_t n = (size_t)S * W;
+    if (n == 0) return CPPF_OK;
+    CPPF_REQUIRE(n <= 0x7fffffffu, "S*W exceeds 2^31-1 rows");
+    CPPF_REQUIRE(q, "q is NULL");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t lds = use_table(robot) ? 0 : robot->lds_bytes;
+    if (use_rtc(robot)) {
+        int n_i = (int)n;
+        void* args[] = {(void*)&robot->chain, (void*)&robot->coll, (void*)&n_i, (void*)&q, (void*)&self_mask, (void*)&env_mask,
+                        (void*)&jlim_mask, (void*)&ext_cost, (void*)&min_self, (void*)&min_env, (void*)&gate, (void*)&W};
+        return rtc_launch(robot, (min_self || min_env) ? RTC_COLL_MIN : RTC_COLL_MASK, grid_for(n), 0, st, args);
+    }
+    const int rc = for_robot(robot, [&](auto tag) {
+        using RB = typename decltype(tag)::type;
+        if (min_self || min_env)
+            hipLaunchKernelGGL((collision_kernel<RB, true>), dim3(grid_for(n)), dim3(kBlock), lds, st, robot->chain, robot->coll, (int)n,
+                               q, self_mask, env_mask, jlim_mask, ext_cost, min_self, min_env, gate, W);
+        else
+            hipLaunchKernelGGL((collision_kernel<RB, false>), dim3(grid_for(n)), dim3(kBlock), lds, st, robot->chain, robot->coll, (int)n,
+                               q, self_mask, env_mask, jlim_mask, ext_cost, min_self, min_env, gate, W);
+        return CPPF_OK;
+    });
+    return rc ? rc : check_launch();
+}
+
+// Which elimination a coupled step of S trajectories of W waypoints resolves to on this handle (see the comments at the launches
+// in lm_full_step_gated): the parallel-in-time form, the row-per-lane form, or neither (the one-wavefront / one-lane kernels).
+// Depends on the sizes, the parameters and the handle's tuning only, so a caller can know it before it launches anything.
+struct FullStepForm {
+    bool use_pcr, use_rows;
+};
+FullStepForm full_step_form(const cppf_robot* robot, size_t n, int W, bool use_pose, bool var_coupling) {
+    const int t_pcr_rows = tune(robot, CPPF_TUNE_PCR_MAX_ROWS);
+    const bool g_pcr_lds = tune(robot, CPPF_TUNE_PCR_LDS) != 0;
+    const bool g_rows_pose = tune(robot, CPPF_TUNE_ROWS_POSE) != 0, g_full_rows = tune(robot, CPPF_TUNE_FULL_ROWS) != 0;
+    const size_t pcr_rows = t_pcr_rows >= 0 ? (size_t)t_pcr_rows : (size_t)((W <= 256 && g_pcr_lds) ? kPcrMaxRowsLds : kPcrMaxRowsGlobal);
+    const size_t pcr_limit = pcr_rows * (robot->desc.ndof <= 7 ? 100 : 50) / 100;
+    FullStepForm f;
+    f.use_pcr = !var_coupling && !use_pose && W <= 512 && n <= pcr_limit && robot->desc.ndof >= 3 && robot->desc.ndof <= 8;
+    f.use_rows = !var_coupling && !f.use_pcr && (!use_pose || g_rows_pose) && g_full_rows && robot->desc.ndof >= 3 &&
+                 robot->desc.ndof <= 12 && W <= (1 << 19);
+    return f;
+}
+const char* const kGatedFormRefusal =
+    "cppflow_hip: the device-side optimiser loop gates the parallel-in-time and the row-per-lane "
+    "elimination only (no pose block, no individually weighted differencing rows, CPPF_TUNE_FULL_ROWS on)";
+
+// cppf_lm_full_step; with a gate (the optimiser loop on the device) only the trajectories it opens are stepped
+int lm_full_step_gated(const cppf_robot* robot, const float* x_in, const float* target, const float* virtual_configs, int S, int W,
+                       const cppf_full_params* params, float* work_blocks, float* work_G, float* work_y, float* x_out, void* stream,
+                       const StepGateK gate) {
+    CPPF_ENTER(robot);
+    CPPF_REQUIRE(params, "params is NULL");
+    CPPF_REQUIRE(S >= 0 && W >= 1, "S < 0 or W < 1");
+    CPPF_REQUIRE(params->lm_lambda > 0.f, "lm_lambda must be > 0");
+    CPPF_REQUIRE(!params->use_virtual_configs || (params->n_virtual_configs > 0 && 2 * params->n_virtual_configs < W),
+                 "2 * n_virtual_configs must be < number of waypoints (optimization_utils.py:449-451)");
+    CPPF_REQUIRE(x_out != x_in, "x_out must not alias x_in (the back substitution reads x_in)");
+    if (S == 0) return CPPF_OK;
+    CPPF_REQUIRE(x_in && target && work_blocks && work_G && work_y && x_out, "NULL pointer");
+    const size_t n = (size_t)S * W;
+    CPPF_REQUIRE(n <= 0x7fffffffu, "S*W exceeds 2^31-1 rows");
+    FullK prm;
+    prm.lm_lambda = params->lm_lambda;
+    prm.a_pos = params->alpha_position;
+    prm.a_rot = params->alpha_rotation;
+    prm.a_diff = params->alpha_differencing;
+    prm.a_diff_pris = params->alpha_differencing_prismatic_scaling;
+    prm.a_vq = params->alpha_virtual_configs;
+    prm.a_self = params->alpha_self_collision;
+    prm.a_env = params->alpha_env_collision;
+    prm.use_pose = params->use_pose;
+    prm.use_diff = params->use_differencing;
+    prm.use_vq = params->use_virtual_configs;
+    prm.n_vq = params->n_virtual_configs;
+    prm.use_self = params->use_self_collisions;
+    prm.use_env = params->use_env_collisions;
+    prm.S = S;
+    prm.W = W;
+    // the "satisfied" row options (cppflow/optimization_utils.py:514-533, 548-606)
+    CPPF_REQUIRE(params->differencing_mode >= 0 && params->differencing_mode <= 2, "differencing_mode must be 0, 1 or 2");
+    CPPF_REQUIRE(!params->pose_do_scale_down_satisfied || (params->pose_scale_down >= 0.f && params->pose_scale_down < 1.f),
+                 "pose scale-down must be in [0, 1) (optimization_utils.py:305)");
+    CPPF_REQUIRE(params->differencing_mode != 2 || (params->differencing_scale_down >= 0.f && params->differencing_scale_down < 1.f),
+                 "differencing scale-down must be in [0, 1) (optimization_utils.py:367)");
+    prm.pose_scale_satisfied = params->use_pose && params->pose_do_scale_down_satisfied;
+    prm.pose_thr_m = params->pose_threshold_m;
+    prm.pose_thr_rad = params->pose_threshold_rad;
+    prm.pose_scale = params->pose_scale_down;
+    prm.diff_mode = params->use_differencing ? params->differencing_mode : 0;
+    prm.diff_thr_rad = params->differencing_threshold_rad;
+    prm.diff_thr_m = params->differencing_threshold_m;
+    prm.diff_scale = params->differencing_scale_down;
+    prm.diff_shift_invalid = params->differencing_shift_invalid_to_threshold;
+    // Individually weighted differencing rows: the coupling between waypoints t and t + 1 is no longer the same constant for
+    // every t, which the tuned elimination kernels assume; such a step goes through the one-lane-per-trajectory kernel with the
+    // couplings read from memory (w2next: the spare tail of work_G -- that kernel keeps d(d+1)/2 of the d*d floats per row).
+    const bool var_coupling = prm.diff_mode != 0;
+    float* const w2next = work_G + n * (size_t)(robot->desc.ndof * (robot->desc.ndof + 1) / 2);
+    // which elimination kernel: see the comments at the launches below
+    const int t_pcr_lds = tune(robot, CPPF_TUNE_PCR_LDS);
+    const bool g_pcr_lds = t_pcr_lds != 0, g_pcr_split = t_pcr_lds != 1;
+    const FullStepForm form = full_step_form(robot, n, W, prm.use_pose != 0, var_coupling);
+    const bool use_pcr = form.use_pcr, use_rows = form.use_rows;
+    prm.fold = use_rows || var_coupling;
+    if (gate.ctl != nullptr && !use_pcr && !use_rows) return fail(CPPF_ERR_UNSUPPORTED, kGatedFormRefusal);
+    hipStream_t st = (hipStream_t)stream;
+    const int rc = for_robot(robot, [&](auto tag) {
+        using RB = typename decltype(tag)::type;
+        if (n >= 131072)
+            hipLaunchKernelGGL((full_blocks_kernel<RB, full_blocks_occ<RB>()>), dim3(grid_for(n)), dim3(kBlock), robot->lds_bytes, st,
+                               robot->chain, robot->coll, prm, x_in, target, virtual_configs, work_blocks, w2next, gate);
+        else
+            hipLaunchKernelGGL((full_blocks_kernel<RB>), dim3(grid_for(n)), dim3(kBlock), robot->lds_bytes, st, robot->chain,
+                               robot->coll, prm, x_in, target, virtual_configs, work_blocks, w2next, gate);
+        return CPPF_OK;
+    });
+    if (rc) return rc;
+    // Trajectories are eliminated one per wavefront (8 x 8 lane tile) up to 8 joints, one per lane beyond.  With the pose
+    // block the d x d blocks are J^T J + a small diagonal (rank 6 of 7, cond ~1e7): the per-lane kernel's Cholesky with
+    // floored pivots copes with that better than the explicit Gauss-Jordan inverse, so it keeps that case.
+    // Up to ~128k rows (the planner's cadence is one trajectory): parallel cyclic reduction, one workgroup per trajectory, one
+    // lane per waypoint; beyond that its O(T log T) work and traffic lose against the waypoint-after-waypoint kernels
+    if (var_coupling) {
+        return for_ndof(robot->desc.ndof, [&](auto dof) {
+            hipLaunchKernelGGL((full_solve_kernel<decltype(dof)::D, true>), dim3((unsigned)((S + 63) / 64)), dim3(64), 0, st, robot->chain,
+                               prm, x_in, virtual_configs, work_blocks, work_G, work_y, x_out, w2next);
+            return check_launch();
+        });
+    }
+    if (use_pcr) {
+        return for_ndof(robot->desc.ndof, [&](auto dof) {
+            constexpr int D = decltype(dof)::D;
+            if constexpr (D <= 8) {  // (full_step_form: the parallel-in-time form exists for 3 .. 8 joints)
+                if (W <= 256 && g_pcr_lds) {  // the state in LDS: 256 x ((d(d+1)/2 + d + d^2) | 1) floats
+                    constexpr size_t kState = 256 * (size_t)((D * (D + 1) / 2 + D + D * D) | 1) * sizeof(float);
+                    CPPF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&full_solve_pcr_kernel<D, 256, true>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)kState));
+                    if (g_pcr_split && (D <= kPcrSplitMaxD || t_pcr_lds == 3)) {  // see kPcrSplitMaxD; 3 forces the split form
+                        CPPF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&full_solve_pcr_kernel<D, 512, true, true>),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)kState));
+                        hipLaunchKernelGGL((full_solve_pcr_kernel<D, 512, true, true>), dim3((unsigned)S), dim3(512), kState, st,
+                                           robot->chain, prm, x_in, virtual_configs, work_blocks, work_G, x_out, gate);
+                    } else
+                        hipLaunchKernelGGL((full_solve_pcr_kernel<D, 256, true>), dim3((unsigned)S), dim3(256), kState, st,
+                                           robot->chain, prm, x_in, virtual_configs, work_blocks, work_G, x_out, gate);
+                } else if (W <= 256)
+                    hipLaunchKernelGGL((full_solve_pcr_kernel<D, 256>), dim3((unsigned)S), dim3(256), 0, st, robot->chain, prm, x_in,
+                                       virtual_configs, work_blocks, work_G, x_out, gate);
+                else
+                    hipLaunchKernelGGL((full_solve_pcr_kernel<D, 512>), dim3((unsigned)S), dim3(512), 0, st, robot->chain, prm, x_in,
+                                       virtual_configs, work_blocks, work_G, x_out, gate);
+            }
+            return check_launch();
+        });
+    }
+    // row-per-lane kernels: 8 trajectories per one-wavefront workgroup and two workgroups (the two ends of the path) per 8
+    // trajectories; the LDS reservation caps the workgroups per compute unit at ceil(#workgroups / 256) (160 KB per compute
+    // unit), which spreads a small launch over distinct compute units
+    const int rows_tpw = robot->desc.ndof <= 8 ? 8 : 4;  // trajectories per wavefront: 8 or 16 lanes each
+    const unsigned rows_wgs = 2u * (unsigned)((S + rows_tpw - 1) / rows_tpw);
+    const unsigned rows_per_cu = (rows_wgs + 255) / 256;
+    const size_t rows_lds = rows_per_cu == 1 ? 96 * 1024 : rows_per_cu == 2 ? 64 * 1024 : rows_per_cu == 3 ? 48 * 1024 : 0;
+    return for_ndof(robot->desc.ndof, [&](auto dof) {
+        constexpr int D = decltype(dof)::D;
+        if (use_rows) {  // (every ndof; sixteen lanes per trajectory at 9 .. 12 joints, see rows_tpw)
+            if (rows_lds > 64 * 1024) {  // per device: set whenever it is needed, a host-side table update
+                CPPF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&full_rows_eliminate_kernel<D>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+                CPPF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&full_rows_substitute_kernel<D>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+            }
+            hipLaunchKernelGGL((full_rows_eliminate_kernel<D>), dim3(rows_wgs), dim3(64), rows_lds, st, prm, robot->chain.pris_mask,
+                               work_blocks, work_G, work_y, gate);
+            hipLaunchKernelGGL((full_rows_substitute_kernel<D>), dim3(rows_wgs), dim3(64), rows_lds, st, prm, robot->chain.pris_mask,
+                               x_in, work_blocks, work_G, work_y, x_out, gate);
+            return check_launch();
+        }
+        if constexpr (D <= 8) {  // one trajectory per wavefront; with the pose block the one-lane kernel keeps the case (see above)
+            if (!prm.use_pose) {
+                hipLaunchKernelGGL((full_solve_wave_kernel<D>), dim3((unsigned)S), dim3(64), 0, st, robot->chain, prm, x_in,
+                                   virtual_configs, work_blocks, work_G, work_y, x_out);
+                return check_launch();
+            }
+        }
+        // (9 .. 12 joints have no one-wavefront-per-trajectory form)
+        hipLaunchKernelGGL((full_solve_kernel<D>), dim3((unsigned)((S + 63) / 64)), dim3(64), 0, st, robot->chain, prm, x_in,
+                           virtual_configs, work_blocks, work_G, work_y, x_out, nullptr);
+        return check_launch();
+    });
 }
 
 }  // namespace
@@ -861,7 +1037,7 @@ int cppf_lm_pose_steps(const cppf_robot* robot, const float* x_in, const float* 
         cppf_lm_outputs oq = *out;
         oq.seed_summary = nullptr;  // rows of a seed span several workgroups in this shape: the reduction kernel follows
         if (int rc = launch_quad(robot, coll, n, st, prm, x_in, target, oq, StepGateK{nullptr, 0, 0u})) return rc;
-        if (int rc = check_launch(robot)) return rc;
+        if (int rc = check_launch()) return rc;
         if (summary_dst)
             return cppf_seed_summary(robot, oq.x_out, S, W, oq.ext_cost, oq.pos_err_m, oq.rot_err_rad, oq.self_mask, oq.env_mask,
                                      oq.jlim_mask, summary_dst, stream);
@@ -964,61 +1140,11 @@ void cppf_lm_batch_destroy(cppf_lm_batch* batch) {
     if (robot->life.fetch_sub(1u, std::memory_order_acq_rel) == (kRobotDead | 1u)) robot_free(robot);
 }
 
-}  // extern "C"
-
-namespace {
-int collision_masks_gated(const cppf_robot* robot, const float* q, int S, int W, uint8_t* self_mask, uint8_t* env_mask,
-                          uint8_t* jlim_mask, float* ext_cost, float* min_self, float* min_env, void* stream, const StepGateK gate);
-int lm_full_step_gated(const cppf_robot* robot, const float* x_in, const float* target, const float* virtual_configs, int S, int W,
-                       const cppf_full_params* params, float* work_blocks, float* work_G, float* work_y, float* x_out, void* stream,
-                       const StepGateK gate);
-}  // namespace
-
-extern "C" {
-
 int cppf_collision_masks(const cppf_robot* robot, const float* q, int S, int W, uint8_t* self_mask, uint8_t* env_mask,
                          uint8_t* jlim_mask, float* ext_cost, float* min_self, float* min_env, void* stream) {
     return collision_masks_gated(robot, q, S, W, self_mask, env_mask, jlim_mask, ext_cost, min_self, min_env, stream,
                                  StepGateK{nullptr, 0, 0u});
 }
-
-}  // extern "C"
-
-namespace {
-int collision_masks_gated(const cppf_robot* robot, const float* q, int S, int W, uint8_t* self_mask, uint8_t* env_mask,
-                          uint8_t* jlim_mask, float* ext_cost, float* min_self, float* min_env, void* stream, const StepGateK gate) {
-    CPPF_ENTER(robot);
-    CPPF_REQUIRE(S >= 0 && W >= 0, "S / W < 0");
-    const size_t n = (size_t)S * W;
-    if (n == 0) return CPPF_OK;
-    CPPF_REQUIRE(n <= 0x7fffffffu, "S*W exceeds 2^31-1 rows");
-    CPPF_REQUIRE(q, "q is NULL");
-    hipStream_t st = (hipStream_t)stream;
-    const size_t lds = (robot->static_id >= 0 && !tune(robot, CPPF_TUNE_FORCE_GENERIC)) ? 0 : robot->lds_bytes;
-    if (use_rtc(robot)) {
-        int n_i = (int)n;
-        void* args[] = {(void*)&robot->chain, (void*)&robot->coll, (void*)&n_i, (void*)&q, (void*)&self_mask, (void*)&env_mask,
-                        (void*)&jlim_mask, (void*)&ext_cost, (void*)&min_self, (void*)&min_env, (void*)&gate, (void*)&W};
-        return rtc_launch(robot, (min_self || min_env) ? RTC_COLL_MIN : RTC_COLL_MASK, grid_for(n), 0, st, args);
-    }
-    if (min_self || min_env) {
-#define CPPF_BODY                                                                                                    \
-    hipLaunchKernelGGL((collision_kernel<RB, true>), dim3(grid_for(n)), dim3(kBlock), lds, st, robot->chain, robot->coll, \
-                       (int)n, q, self_mask, env_mask, jlim_mask, ext_cost, min_self, min_env, gate, W)
-        CPPF_DISPATCH_RB(robot)
-#undef CPPF_BODY
-    } else {
-#define CPPF_BODY                                                                                                     \
-    hipLaunchKernelGGL((collision_kernel<RB, false>), dim3(grid_for(n)), dim3(kBlock), lds, st, robot->chain, robot->coll, \
-                       (int)n, q, self_mask, env_mask, jlim_mask, ext_cost, min_self, min_env, gate, W)
-        CPPF_DISPATCH_RB(robot)
-#undef CPPF_BODY
-    }
-    return check_launch(robot);
-}
-}  // namespace
-
-extern "C" {
 
 int cppf_self_collision_distances(const cppf_robot* robot, const float* x, int n, float* dists, void* stream) {
     CPPF_ENTER(robot);
@@ -1026,10 +1152,11 @@ int cppf_self_collision_distances(const cppf_robot* robot, const float* x, int n
     if (n == 0 || robot->coll.npairs == 0) return CPPF_OK;
     CPPF_REQUIRE(x && dists, "x / dists is NULL");
     hipStream_t st = (hipStream_t)stream;
-    CPPF_DISPATCH_D(robot->desc.ndof,
-                    hipLaunchKernelGGL((distances_kernel<D, false>), dim3(grid_for(n)), dim3(kBlock), robot->lds_bytes,
-                                       st, robot->chain, robot->coll, n, x, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, dists));
-    return check_launch(robot);
+    return for_ndof(robot->desc.ndof, [&](auto dof) {
+        hipLaunchKernelGGL((distances_kernel<decltype(dof)::D, false>), dim3(grid_for(n)), dim3(kBlock), robot->lds_bytes, st,
+                           robot->chain, robot->coll, n, x, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, dists);
+        return check_launch();
+    });
 }
 
 int cppf_env_collision_distances(const cppf_robot* robot, const float* x, int n, const float* cuboid, const float* Rt,
@@ -1048,11 +1175,11 @@ int cppf_env_collision_distances(const cppf_robot* robot, const float* x, int n,
         hi[k] = Rt[9 + k] + cuboid[3 + k];
     }
     hipStream_t st = (hipStream_t)stream;
-    CPPF_DISPATCH_D(robot->desc.ndof,
-                    hipLaunchKernelGGL((distances_kernel<D, true>), dim3(grid_for(n)), dim3(kBlock), robot->lds_bytes,
-                                       st, robot->chain, robot->coll, n, x, lo[0], lo[1], lo[2], hi[0], hi[1], hi[2],
-                                       dists));
-    return check_launch(robot);
+    return for_ndof(robot->desc.ndof, [&](auto dof) {
+        hipLaunchKernelGGL((distances_kernel<decltype(dof)::D, true>), dim3(grid_for(n)), dim3(kBlock), robot->lds_bytes, st,
+                           robot->chain, robot->coll, n, x, lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], dists);
+        return check_launch();
+    });
 }
 
 int cppf_self_collision_distances_jacobian(const cppf_robot* robot, const float* x, int n, float* jac, float* dists,
@@ -1062,11 +1189,11 @@ int cppf_self_collision_distances_jacobian(const cppf_robot* robot, const float*
     if (n == 0 || robot->coll.npairs == 0) return CPPF_OK;
     CPPF_REQUIRE(x && jac, "x / jac is NULL");
     hipStream_t st = (hipStream_t)stream;
-    CPPF_DISPATCH_D(robot->desc.ndof,
-                    hipLaunchKernelGGL((distance_jacobians_kernel<D, false>), dim3(grid_for(n)), dim3(kBlock),
-                                       robot->lds_bytes, st, robot->chain, robot->coll, n, x, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, jac,
-                                       dists));
-    return check_launch(robot);
+    return for_ndof(robot->desc.ndof, [&](auto dof) {
+        hipLaunchKernelGGL((distance_jacobians_kernel<decltype(dof)::D, false>), dim3(grid_for(n)), dim3(kBlock), robot->lds_bytes, st,
+                           robot->chain, robot->coll, n, x, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, jac, dists);
+        return check_launch();
+    });
 }
 
 int cppf_env_collision_distances_jacobian(const cppf_robot* robot, const float* x, int n, const float* cuboid,
@@ -1085,11 +1212,11 @@ int cppf_env_collision_distances_jacobian(const cppf_robot* robot, const float* 
         hi[k] = Rt[9 + k] + cuboid[3 + k];
     }
     hipStream_t st = (hipStream_t)stream;
-    CPPF_DISPATCH_D(robot->desc.ndof,
-                    hipLaunchKernelGGL((distance_jacobians_kernel<D, true>), dim3(grid_for(n)), dim3(kBlock), robot->lds_bytes,
-                                       st, robot->chain, robot->coll, n, x, lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], jac,
-                                       dists));
-    return check_launch(robot);
+    return for_ndof(robot->desc.ndof, [&](auto dof) {
+        hipLaunchKernelGGL((distance_jacobians_kernel<decltype(dof)::D, true>), dim3(grid_for(n)), dim3(kBlock), robot->lds_bytes, st,
+                           robot->chain, robot->coll, n, x, lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], jac, dists);
+        return check_launch();
+    });
 }
 
 int cppf_pose_error_metrics(const cppf_robot* robot, const float* x, const float* target, int S, int W, float* pos_err_m,
@@ -1101,10 +1228,11 @@ int cppf_pose_error_metrics(const cppf_robot* robot, const float* x, const float
     CPPF_REQUIRE(n <= 0x7fffffffu, "S*W exceeds 2^31-1 rows");
     CPPF_REQUIRE(x && target, "x / target is NULL");
     hipStream_t st = (hipStream_t)stream;
-    CPPF_DISPATCH_D(robot->desc.ndof,
-                    hipLaunchKernelGGL((pose_metrics_kernel<D>), dim3(grid_for(n)), dim3(kBlock), 0, st, robot->chain,
-                                       robot->coll, (int)n, W, x, target, pos_err_m, rot_err_rad));
-    return check_launch(robot);
+    return for_ndof(robot->desc.ndof, [&](auto dof) {
+        hipLaunchKernelGGL((pose_metrics_kernel<decltype(dof)::D>), dim3(grid_for(n)), dim3(kBlock), 0, st, robot->chain, robot->coll,
+                           (int)n, W, x, target, pos_err_m, rot_err_rad);
+        return check_launch();
+    });
 }
 
 int cppf_track_paths(const cppf_robot* robot, const float* target, int T, int k, int S, const cppf_track_params* params,
@@ -1150,11 +1278,12 @@ int cppf_track_paths(const cppf_robot* robot, const float* target, int T, int k,
         CPPF_HIP(hipModuleLaunchKernel(robot->rtc->fn[RTC_TRACK], grid, 1, 1, (unsigned)kTrackBlock, 1, 1, 0, st, args, nullptr));
         return CPPF_OK;
     }
-#define CPPF_BODY \
-    hipLaunchKernelGGL((track_kernel<RB>), dim3(grid), dim3(kTrackBlock), 0, st, robot->chain, robot->coll, prm, tk)
-    CPPF_DISPATCH_RB(robot)
-#undef CPPF_BODY
-    return check_launch(robot);
+    const int rc = for_robot(robot, [&](auto tag) {
+        using RB = typename decltype(tag)::type;
+        hipLaunchKernelGGL((track_kernel<RB>), dim3(grid), dim3(kTrackBlock), 0, st, robot->chain, robot->coll, prm, tk);
+        return CPPF_OK;
+    });
+    return rc ? rc : check_launch();
 }
 
 int cppf_seed_validity(const cppf_robot* robot, const float* x, const float* target, int S, int W, float* out,
@@ -1164,9 +1293,10 @@ int cppf_seed_validity(const cppf_robot* robot, const float* x, const float* tar
     if (S == 0) return CPPF_OK;
     CPPF_REQUIRE(x && target && out, "x / target / out is NULL");
     hipStream_t st = (hipStream_t)stream;
-    CPPF_DISPATCH_D(robot->desc.ndof, hipLaunchKernelGGL((seed_validity_kernel<D>), dim3(S), dim3(64), 0, st,
-                                                        robot->chain, robot->coll, S, W, x, target, out));
-    return check_launch(robot);
+    return for_ndof(robot->desc.ndof, [&](auto dof) {
+        hipLaunchKernelGGL((seed_validity_kernel<decltype(dof)::D>), dim3(S), dim3(64), 0, st, robot->chain, robot->coll, S, W, x, target, out);
+        return check_launch();
+    });
 }
 
 int cppf_seed_summary(const cppf_robot* robot, const float* x, int S, int W, const float* ext_cost, const float* pos_err_m,
@@ -1177,10 +1307,11 @@ int cppf_seed_summary(const cppf_robot* robot, const float* x, int S, int W, con
     if (S == 0) return CPPF_OK;
     CPPF_REQUIRE(x && ext_cost && pos_err_m && rot_err_rad && self_mask && env_mask && jlim_mask && out, "NULL pointer");
     hipStream_t st = (hipStream_t)stream;
-    CPPF_DISPATCH_D(robot->desc.ndof,
-                    hipLaunchKernelGGL((seed_summary_kernel<D>), dim3(S), dim3(64), 0, st, robot->chain, S, W, x, ext_cost,
-                                       pos_err_m, rot_err_rad, self_mask, env_mask, jlim_mask, out));
-    return check_launch(robot);
+    return for_ndof(robot->desc.ndof, [&](auto dof) {
+        hipLaunchKernelGGL((seed_summary_kernel<decltype(dof)::D>), dim3(S), dim3(64), 0, st, robot->chain, S, W, x, ext_cost, pos_err_m,
+                           rot_err_rad, self_mask, env_mask, jlim_mask, out);
+        return check_launch();
+    });
 }
 
 int cppf_select_valid_seed_gathered(const cppf_robot* robot, const float* gathered, int n_chunks, int n_groups, int S_chunk,
@@ -1199,7 +1330,7 @@ int cppf_select_valid_seed_gathered(const cppf_robot* robot, const float* gather
     k.ignore_env = constraints->env_collisions_ignored;
     k.S_chunk = S_chunk, k.n_chunks = n_chunks, k.n_groups = n_groups;
     hipLaunchKernelGGL(select_valid_seed_kernel, dim3((unsigned)n_groups), dim3(256), 0, (hipStream_t)stream, gathered, k, out);
-    return check_launch(robot);
+    return check_launch();
 }
 
 int cppf_select_valid_seed(const cppf_robot* robot, const float* seed_summary, int S, const cppf_constraints* constraints,
@@ -1215,10 +1346,11 @@ int cppf_plan_metrics(const cppf_robot* robot, const float* x, const float* targ
     CPPF_REQUIRE((size_t)S * W <= 0x7fffffffu, "S*W exceeds 2^31-1 rows");
     CPPF_REQUIRE(x && target && out, "x / target / out is NULL");
     hipStream_t st = (hipStream_t)stream;
-    CPPF_DISPATCH_D(robot->desc.ndof,
-                    hipLaunchKernelGGL((plan_metrics_kernel<D>), dim3(S), dim3(64), 0, st, robot->chain, robot->coll, S, W, x,
-                                       target, self_mask, env_mask, q_init, out));
-    return check_launch(robot);
+    return for_ndof(robot->desc.ndof, [&](auto dof) {
+        hipLaunchKernelGGL((plan_metrics_kernel<decltype(dof)::D>), dim3(S), dim3(64), 0, st, robot->chain, robot->coll, S, W, x, target,
+                           self_mask, env_mask, q_init, out);
+        return check_launch();
+    });
 }
 
 int cppf_lm_full_step(const cppf_robot* robot, const float* x_in, const float* target, const float* virtual_configs, int S,
@@ -1231,192 +1363,6 @@ int cppf_lm_full_step(const cppf_robot* robot, const float* x_in, const float* t
 }  // extern "C"
 
 namespace {
-// Which elimination a coupled step of S trajectories of W waypoints resolves to on this handle (see the comments at the launches
-// in lm_full_step_gated): the parallel-in-time form, the row-per-lane form, or neither (the one-wavefront / one-lane kernels).
-// Depends on the sizes, the parameters and the handle's tuning only, so a caller can know it before it launches anything.
-struct FullStepForm {
-    bool use_pcr, use_rows;
-};
-FullStepForm full_step_form(const cppf_robot* robot, size_t n, int W, bool use_pose, bool var_coupling) {
-    const int t_pcr_rows = tune(robot, CPPF_TUNE_PCR_MAX_ROWS);
-    const bool g_pcr_lds = tune(robot, CPPF_TUNE_PCR_LDS) != 0;
-    const bool g_rows_pose = tune(robot, CPPF_TUNE_ROWS_POSE) != 0, g_full_rows = tune(robot, CPPF_TUNE_FULL_ROWS) != 0;
-    const size_t pcr_rows = t_pcr_rows >= 0 ? (size_t)t_pcr_rows : (size_t)((W <= 256 && g_pcr_lds) ? kPcrMaxRowsLds : kPcrMaxRowsGlobal);
-    const size_t pcr_limit = pcr_rows * (robot->desc.ndof <= 7 ? 100 : 50) / 100;
-    FullStepForm f;
-    f.use_pcr = !var_coupling && !use_pose && W <= 512 && n <= pcr_limit && robot->desc.ndof >= 3 && robot->desc.ndof <= 8;
-    f.use_rows = !var_coupling && !f.use_pcr && (!use_pose || g_rows_pose) && g_full_rows && robot->desc.ndof >= 3 &&
-                 robot->desc.ndof <= 12 && W <= (1 << 19);
-    return f;
-}
-const char* const kGatedFormRefusal =
-    "cppflow_hip: the device-side optimiser loop gates the parallel-in-time and the row-per-lane "
-    "elimination only (no pose block, no individually weighted differencing rows, CPPF_TUNE_FULL_ROWS on)";
-
-// cppf_lm_full_step; with a gate (the optimiser loop on the device) only the trajectories it opens are stepped
-int lm_full_step_gated(const cppf_robot* robot, const float* x_in, const float* target, const float* virtual_configs, int S, int W,
-                       const cppf_full_params* params, float* work_blocks, float* work_G, float* work_y, float* x_out, void* stream,
-                       const StepGateK gate) {
-    CPPF_ENTER(robot);
-    CPPF_REQUIRE(params, "params is NULL");
-    CPPF_REQUIRE(S >= 0 && W >= 1, "S < 0 or W < 1");
-    CPPF_REQUIRE(params->lm_lambda > 0.f, "lm_lambda must be > 0");
-    CPPF_REQUIRE(!params->use_virtual_configs || (params->n_virtual_configs > 0 && 2 * params->n_virtual_configs < W),
-                 "2 * n_virtual_configs must be < number of waypoints (optimization_utils.py:449-451)");
-    CPPF_REQUIRE(x_out != x_in, "x_out must not alias x_in (the back substitution reads x_in)");
-    if (S == 0) return CPPF_OK;
-    CPPF_REQUIRE(x_in && target && work_blocks && work_G && work_y && x_out, "NULL pointer");
-    const size_t n = (size_t)S * W;
-    CPPF_REQUIRE(n <= 0x7fffffffu, "S*W exceeds 2^31-1 rows");
-    FullK prm;
-    prm.lm_lambda = params->lm_lambda;
-    prm.a_pos = params->alpha_position;
-    prm.a_rot = params->alpha_rotation;
-    prm.a_diff = params->alpha_differencing;
-    prm.a_diff_pris = params->alpha_differencing_prismatic_scaling;
-    prm.a_vq = params->alpha_virtual_configs;
-    prm.a_self = params->alpha_self_collision;
-    prm.a_env = params->alpha_env_collision;
-    prm.use_pose = params->use_pose;
-    prm.use_diff = params->use_differencing;
-    prm.use_vq = params->use_virtual_configs;
-    prm.n_vq = params->n_virtual_configs;
-    prm.use_self = params->use_self_collisions;
-    prm.use_env = params->use_env_collisions;
-    prm.S = S;
-    prm.W = W;
-    // the "satisfied" row options (cppflow/optimization_utils.py:514-533, 548-606)
-    CPPF_REQUIRE(params->differencing_mode >= 0 && params->differencing_mode <= 2, "differencing_mode must be 0, 1 or 2");
-    CPPF_REQUIRE(!params->pose_do_scale_down_satisfied || (params->pose_scale_down >= 0.f && params->pose_scale_down < 1.f),
-                 "pose scale-down must be in [0, 1) (optimization_utils.py:305)");
-    CPPF_REQUIRE(params->differencing_mode != 2 || (params->differencing_scale_down >= 0.f && params->differencing_scale_down < 1.f),
-                 "differencing scale-down must be in [0, 1) (optimization_utils.py:367)");
-    prm.pose_scale_satisfied = params->use_pose && params->pose_do_scale_down_satisfied;
-    prm.pose_thr_m = params->pose_threshold_m;
-    prm.pose_thr_rad = params->pose_threshold_rad;
-    prm.pose_scale = params->pose_scale_down;
-    prm.diff_mode = params->use_differencing ? params->differencing_mode : 0;
-    prm.diff_thr_rad = params->differencing_threshold_rad;
-    prm.diff_thr_m = params->differencing_threshold_m;
-    prm.diff_scale = params->differencing_scale_down;
-    prm.diff_shift_invalid = params->differencing_shift_invalid_to_threshold;
-    // Individually weighted differencing rows: the coupling between waypoints t and t + 1 is no longer the same constant for
-    // every t, which the tuned elimination kernels assume; such a step goes through the one-lane-per-trajectory kernel with the
-    // couplings read from memory (w2next: the spare tail of work_G -- that kernel keeps d(d+1)/2 of the d*d floats per row).
-    const bool var_coupling = prm.diff_mode != 0;
-    float* const w2next = work_G + n * (size_t)(robot->desc.ndof * (robot->desc.ndof + 1) / 2);
-    // which elimination kernel: see the comments at the launches below
-    const int t_pcr_lds = tune(robot, CPPF_TUNE_PCR_LDS);
-    const bool g_pcr_lds = t_pcr_lds != 0, g_pcr_split = t_pcr_lds != 1;
-    const FullStepForm form = full_step_form(robot, n, W, prm.use_pose != 0, var_coupling);
-    const bool use_pcr = form.use_pcr, use_rows = form.use_rows;
-    prm.fold = use_rows || var_coupling;
-    if (gate.ctl != nullptr && !use_pcr && !use_rows) return fail(CPPF_ERR_UNSUPPORTED, kGatedFormRefusal);
-    hipStream_t st = (hipStream_t)stream;
-#define CPPF_BODY                                                                                                     \
-    if (n >= 131072)                                                                                                  \
-        hipLaunchKernelGGL((full_blocks_kernel<RB, full_blocks_occ<RB>()>), dim3(grid_for(n)), dim3(kBlock), robot->lds_bytes, st, \
-                           robot->chain, robot->coll, prm, x_in, target, virtual_configs, work_blocks, w2next, gate); \
-    else                                                                                                              \
-        hipLaunchKernelGGL((full_blocks_kernel<RB>), dim3(grid_for(n)), dim3(kBlock), robot->lds_bytes, st, robot->chain, \
-                           robot->coll, prm, x_in, target, virtual_configs, work_blocks, w2next, gate)
-    CPPF_DISPATCH_RB(robot)
-#undef CPPF_BODY
-    // Trajectories are eliminated one per wavefront (8 x 8 lane tile) up to 8 joints, one per lane beyond.  With the pose
-    // block the d x d blocks are J^T J + a small diagonal (rank 6 of 7, cond ~1e7): the per-lane kernel's Cholesky with
-    // floored pivots copes with that better than the explicit Gauss-Jordan inverse, so it keeps that case.
-    // Up to ~128k rows (the planner's cadence is one trajectory): parallel cyclic reduction, one workgroup per trajectory, one
-    // lane per waypoint; beyond that its O(T log T) work and traffic lose against the waypoint-after-waypoint kernels
-    if (var_coupling) {
-        CPPF_DISPATCH_D(robot->desc.ndof,
-                        hipLaunchKernelGGL((full_solve_kernel<D, true>), dim3((unsigned)((S + 63) / 64)), dim3(64), 0, st,
-                                           robot->chain, prm, x_in, virtual_configs, work_blocks, work_G, work_y, x_out, w2next));
-        return check_launch(robot);
-    }
-    if (use_pcr) {
-        switch (robot->desc.ndof) {
-#define CPPF_PCR_CASE(DD)                                                                                              \
-    case DD:                                                                                                           \
-        if (W <= 256 && g_pcr_lds) { /* the state in LDS: 256 x ((d(d+1)/2 + d + d^2) | 1) floats */                     \
-            constexpr size_t kState = 256 * (size_t)((DD * (DD + 1) / 2 + DD + DD * DD) | 1) * sizeof(float);           \
-            CPPF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&full_solve_pcr_kernel<DD, 256, true>),         \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)kState));                    \
-            if (g_pcr_split && (DD <= kPcrSplitMaxD || t_pcr_lds == 3)) { /* see kPcrSplitMaxD; 3 forces the split form */ \
-                CPPF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&full_solve_pcr_kernel<DD, 512, true, true>), \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)kState));                \
-                hipLaunchKernelGGL((full_solve_pcr_kernel<DD, 512, true, true>), dim3((unsigned)S), dim3(512), kState, st, \
-                                   robot->chain, prm, x_in, virtual_configs, work_blocks, work_G, x_out, gate);              \
-            } else                                                                                                     \
-            hipLaunchKernelGGL((full_solve_pcr_kernel<DD, 256, true>), dim3((unsigned)S), dim3(256), kState, st,        \
-                               robot->chain, prm, x_in, virtual_configs, work_blocks, work_G, x_out, gate);                  \
-        } else if (W <= 256)                                                                                           \
-            hipLaunchKernelGGL((full_solve_pcr_kernel<DD, 256>), dim3((unsigned)S), dim3(256), 0, st, robot->chain, prm, \
-                               x_in, virtual_configs, work_blocks, work_G, x_out, gate);                                     \
-        else                                                                                                           \
-            hipLaunchKernelGGL((full_solve_pcr_kernel<DD, 512>), dim3((unsigned)S), dim3(512), 0, st, robot->chain, prm, \
-                               x_in, virtual_configs, work_blocks, work_G, x_out, gate);                                     \
-        break;
-            CPPF_PCR_CASE(3) CPPF_PCR_CASE(4) CPPF_PCR_CASE(5) CPPF_PCR_CASE(6) CPPF_PCR_CASE(7) CPPF_PCR_CASE(8)
-#undef CPPF_PCR_CASE
-            default: break;
-        }
-        return check_launch(robot);
-    }
-    // row-per-lane kernels: 8 trajectories per one-wavefront workgroup and two workgroups (the two ends of the path) per 8
-    // trajectories; the LDS reservation caps the workgroups per compute unit at ceil(#workgroups / 256) (160 KB per compute
-    // unit), which spreads a small launch over distinct compute units
-    const int rows_tpw = robot->desc.ndof <= 8 ? 8 : 4;  // trajectories per wavefront: 8 or 16 lanes each
-    const unsigned rows_wgs = 2u * (unsigned)((S + rows_tpw - 1) / rows_tpw);
-    const unsigned rows_per_cu = (rows_wgs + 255) / 256;
-    const size_t rows_lds = rows_per_cu == 1 ? 96 * 1024 : rows_per_cu == 2 ? 64 * 1024 : rows_per_cu == 3 ? 48 * 1024 : 0;
-    switch ((prm.use_pose && !use_rows) ? 0 : robot->desc.ndof) {
-#define CPPF_WAVE_CASE(DD)                                                                                              \
-    case DD:                                                                                                            \
-        if (use_rows) {                                                                                                 \
-            if (rows_lds > 64 * 1024) { /* per device: set whenever it is needed, a host-side table update */           \
-                CPPF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&full_rows_eliminate_kernel<DD>),            \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));                   \
-                CPPF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&full_rows_substitute_kernel<DD>),           \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));                   \
-            }                                                                                                           \
-            hipLaunchKernelGGL((full_rows_eliminate_kernel<DD>), dim3(rows_wgs), dim3(64), rows_lds, st, prm,           \
-                               robot->chain.pris_mask, work_blocks, work_G, work_y, gate);                                    \
-            hipLaunchKernelGGL((full_rows_substitute_kernel<DD>), dim3(rows_wgs), dim3(64), rows_lds, st, prm,          \
-                               robot->chain.pris_mask, x_in, work_blocks, work_G, work_y, x_out, gate);                       \
-        } else                                                                                                          \
-            hipLaunchKernelGGL((full_solve_wave_kernel<DD>), dim3((unsigned)S), dim3(64), 0, st, robot->chain, prm,      \
-                               x_in, virtual_configs, work_blocks, work_G, work_y, x_out);                              \
-        break;
-        CPPF_WAVE_CASE(3) CPPF_WAVE_CASE(4) CPPF_WAVE_CASE(5) CPPF_WAVE_CASE(6) CPPF_WAVE_CASE(7) CPPF_WAVE_CASE(8)
-#undef CPPF_WAVE_CASE
-#define CPPF_ROWS16_CASE(DD) /* 9 .. 12 joints: sixteen lanes per trajectory (no one-wavefront-per-trajectory form) */          \
-    case DD:                                                                                                            \
-        if (use_rows) {                                                                                                 \
-            if (rows_lds > 64 * 1024) {                                                                                 \
-                CPPF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&full_rows_eliminate_kernel<DD>),            \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));                   \
-                CPPF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&full_rows_substitute_kernel<DD>),           \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));                   \
-            }                                                                                                           \
-            hipLaunchKernelGGL((full_rows_eliminate_kernel<DD>), dim3(rows_wgs), dim3(64), rows_lds, st, prm,           \
-                               robot->chain.pris_mask, work_blocks, work_G, work_y, gate);                                    \
-            hipLaunchKernelGGL((full_rows_substitute_kernel<DD>), dim3(rows_wgs), dim3(64), rows_lds, st, prm,          \
-                               robot->chain.pris_mask, x_in, work_blocks, work_G, work_y, x_out, gate);                       \
-        } else                                                                                                          \
-            hipLaunchKernelGGL((full_solve_kernel<DD>), dim3((unsigned)((S + 63) / 64)), dim3(64), 0, st, robot->chain, \
-                               prm, x_in, virtual_configs, work_blocks, work_G, work_y, x_out, nullptr);                \
-        break;
-        CPPF_ROWS16_CASE(9) CPPF_ROWS16_CASE(10) CPPF_ROWS16_CASE(11) CPPF_ROWS16_CASE(12)
-#undef CPPF_ROWS16_CASE
-        default:
-            CPPF_DISPATCH_D(robot->desc.ndof,
-                            hipLaunchKernelGGL((full_solve_kernel<D>), dim3((unsigned)((S + 63) / 64)), dim3(64), 0, st,
-                                               robot->chain, prm, x_in, virtual_configs, work_blocks, work_G, work_y,
-                                               x_out, nullptr));
-    }
-    return check_launch(robot);
-}
-
 // workspace of cppf_lm_optimize_enqueue, in floats (every section a multiple of 4 floats): snapshot | x_new | blocks | G | y |
 // metrics [S,16] | self mask | env mask (one byte per row each)
 struct OptloopLayout {
@@ -1530,10 +1476,14 @@ int cppf_lm_optimize_enqueue(const cppf_robot* robot, float* x, const float* tar
             if (int rc = collision_masks_gated(robot, x, S, W, self_m, env_m, nullptr, nullptr, nullptr, nullptr, stream, g_live)) return rc;
         const uint8_t* const sm = params->constraints.self_collisions_ignored ? nullptr : self_m;
         const uint8_t* const em = params->constraints.env_collisions_ignored ? nullptr : env_m;
-        CPPF_DISPATCH_D(d, hipLaunchKernelGGL((optloop_metrics_kernel<D>), dim3(S), dim3(64), 0, st, robot->chain, robot->coll, S, W, x,
-                                              target, sm, em, metrics, g_live));
+        const int rc = for_ndof(d, [&](auto dof) {
+            hipLaunchKernelGGL((optloop_metrics_kernel<decltype(dof)::D>), dim3(S), dim3(64), 0, st, robot->chain, robot->coll, S, W, x, target,
+                               sm, em, metrics, g_live);
+            return CPPF_OK;
+        });
+        if (rc) return rc;
         hipLaunchKernelGGL(optloop_decide_kernel, dim3(C), dim3(64), 0, st, *params, S, W, d, metrics, x, ws + L.snapshot, control);
-        if (int rc = check_launch(robot)) return rc;
+        if (int rc2 = check_launch()) return rc2;
     }
     return CPPF_OK;
 }
@@ -1547,9 +1497,11 @@ int cppf_mjacs(const cppf_robot* robot, const float* q, int k, int T, float pris
     CPPF_REQUIRE(total <= ((size_t)1 << 40), "k*k*(T-1) exceeds 2^40 entries");
     CPPF_REQUIRE((total + 255) / 256 <= 0x7fffffffu, "grid too large");
     hipStream_t st = (hipStream_t)stream;
-    CPPF_DISPATCH_D(robot->desc.ndof, hipLaunchKernelGGL((mjacs_kernel<D>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
-                                                         st, q, k, T, robot->chain.pris_mask, prismatic_scaling, mjacs));
-    return check_launch(robot);
+    return for_ndof(robot->desc.ndof, [&](auto dof) {
+        hipLaunchKernelGGL((mjacs_kernel<decltype(dof)::D>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, q, k, T,
+                           robot->chain.pris_mask, prismatic_scaling, mjacs);
+        return check_launch();
+    });
 }
 
 constexpr int kDpResidentMaxK = 1024;  // four destinations per workgroup x 256 compute units (dp_resident_kernel)
@@ -1578,7 +1530,11 @@ int cppf_dp_search(const cppf_robot* robot, const float* q, const float* ext_cos
         // spinning 2^22 reads: a partitioned / CU-masked / smaller device takes the per-waypoint launches straight away (AUTO), and a
         // forced CPPF_DP_RESIDENT is refused.  (Other work on the device -- a second resident search on another stream, a full-width
         // fused launch -- can still delay workgroups; the bounded waits stay as the safety net for that.)
-        CPPF_DISPATCH_D(d, form = dp_resident_form<D>(k, tune(robot, CPPF_TUNE_DP_PERSISTENT)));
+        const int rc = for_ndof(d, [&](auto dof) {
+            form = dp_resident_form<decltype(dof)::D>(k, tune(robot, CPPF_TUNE_DP_PERSISTENT));
+            return CPPF_OK;
+        });
+        if (rc) return rc;
         int per_cu = 0;
         CPPF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, form.fn, form.block, 0));
         const int cus = tune(robot, CPPF_TUNE_CU_COUNT) >= 0 ? tune(robot, CPPF_TUNE_CU_COUNT) : robot->cu_count;  // (the test hook: a smaller device)
@@ -1606,30 +1562,34 @@ int cppf_dp_search(const cppf_robot* robot, const float* q, const float* ext_cos
         hipLaunchKernelGGL(dp_backtrace_kernel, dim3(1), dim3(256), dp_stage_bytes(k, T), st, q, work_costsT, work_memoT, k, T, d,
                        dp_stage_bytes(k, T) != 0, best_idx,
                            best_path);
-        return check_launch(robot);
+        return check_launch();
     }
     const int bpb = k >= 4096 ? 4 : (k >= 2048 ? 2 : 1);
     const unsigned blocks = (unsigned)((k + bpb - 1) / bpb);
     for (int t = 1; t < T; ++t) {
         const float* qp = work_qT + (size_t)(t - 1) * k * d;
         const float* qc = work_qT + (size_t)t * k * d;
-#define CPPF_DP_LAUNCH(BPB)                                                                                             \
-    CPPF_DISPATCH_D(d, hipLaunchKernelGGL((dp_step_kernel<D, BPB>), dim3(blocks), dim3(256), 0, st, qp, qc,               \
-                                         work_costsT + (size_t)(t - 1) * k, ext_cost, k, T, t, robot->chain.pris_mask, \
-                                         prismatic_scaling, work_costsT + (size_t)t * k, work_memoT + (size_t)t * k))
-        if (bpb == 4) {
-            CPPF_DP_LAUNCH(4);
-        } else if (bpb == 2) {
-            CPPF_DP_LAUNCH(2);
-        } else {
-            CPPF_DP_LAUNCH(1);
-        }
-#undef CPPF_DP_LAUNCH
+        const int rc = for_ndof(d, [&](auto dof) {
+            constexpr int D = decltype(dof)::D;
+            const auto step = [&](auto bpb_tag) {  // the destinations per workgroup, as a constant
+                hipLaunchKernelGGL((dp_step_kernel<D, decltype(bpb_tag)::value>), dim3(blocks), dim3(256), 0, st, qp, qc,
+                                   work_costsT + (size_t)(t - 1) * k, ext_cost, k, T, t, robot->chain.pris_mask, prismatic_scaling,
+                                   work_costsT + (size_t)t * k, work_memoT + (size_t)t * k);
+            };
+            if (bpb == 4)
+                step(std::integral_constant<int, 4>{});
+            else if (bpb == 2)
+                step(std::integral_constant<int, 2>{});
+            else
+                step(std::integral_constant<int, 1>{});
+            return CPPF_OK;
+        });
+        if (rc) return rc;
     }
     hipLaunchKernelGGL(dp_backtrace_kernel, dim3(1), dim3(256), dp_stage_bytes(k, T), st, q, work_costsT, work_memoT, k, T, d,
                        dp_stage_bytes(k, T) != 0, best_idx,
                        best_path);
-    return check_launch(robot);
+    return check_launch();
 }
 
 int cppf_dp_table_floats(int k, int T, size_t* n_floats) {
@@ -1655,9 +1615,13 @@ int cppf_dp_search_tabled(const cppf_robot* robot, const float* q, const float* 
     CPPF_HIP(hipMemsetAsync(work_memoT, 0, sizeof(int32_t) * (size_t)k, st));
     if (T >= 2) {
         CPPF_REQUIRE(T - 1 <= 65535, "cppf_dp_search_tabled: T <= 65536");
-        CPPF_DISPATCH_D(d, hipLaunchKernelGGL((dp_table_kernel<D>), dim3((unsigned)((kp + 255) / 256), (unsigned)((k + 7) / 8), (unsigned)(T - 1)),
-                                             dim3(256), 0, st, work_qT, k, kp, T, robot->chain.pris_mask, prismatic_scaling,
-                                             reinterpret_cast<uint32_t*>(work_table)));
+        const int rc = for_ndof(d, [&](auto dof) {
+            hipLaunchKernelGGL((dp_table_kernel<decltype(dof)::D>), dim3((unsigned)((kp + 255) / 256), (unsigned)((k + 7) / 8), (unsigned)(T - 1)),
+                               dim3(256), 0, st, work_qT, k, kp, T, robot->chain.pris_mask, prismatic_scaling,
+                               reinterpret_cast<uint32_t*>(work_table));
+            return CPPF_OK;
+        });
+        if (rc) return rc;
         const uint32_t* tab = reinterpret_cast<const uint32_t*>(work_table);
         switch (kp) {
             case 64: hipLaunchKernelGGL(dp_chain_kernel<64>, dim3(1), dim3(512), 0, st, tab, ext_cost, k, T, work_costsT); break;
@@ -1671,7 +1635,7 @@ int cppf_dp_search_tabled(const cppf_robot* robot, const float* q, const float* 
     hipLaunchKernelGGL(dp_backtrace_kernel, dim3(1), dim3(256), dp_stage_bytes(k, T), st, q, work_costsT, work_memoT, k, T, d,
                        dp_stage_bytes(k, T) != 0, best_idx,
                        best_path);
-    return check_launch(robot);
+    return check_launch();
 }
 
 // ---- RCCL behind the C ABI ------------------------------------------------------------------------------------------------------
