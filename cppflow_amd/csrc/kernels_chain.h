@@ -89,6 +89,13 @@ __device__ __forceinline__ void jacobian_from_axes(const RB& rb, const float (&p
 // kernel: atan(a) = a + a s P7(s) on a in [0, 1] after the min / max reduction (max abs error 8e-8, relative 1.6e-7),
 // asin(x) = x + x z P4(z) on |x| <= 0.5 and pi/2 - 2 asin(sqrt((1 - |x|) / 2)) beyond (3.4e-8 / 1.5e-7).  Both keep full
 // RELATIVE accuracy towards 0, which is what the iteration needs as the residual vanishes; exact at 0.
+// Those four figures are the POLYNOMIALS' errors in real arithmetic.  Evaluated in fp32 as written here (restated in numpy float32 with a
+// correctly rounded reciprocal and square root, 4 M points against fp64: tests/test_pose_domain_model.py) the functions measure
+//   atan2_lm  2.85e-7 absolute (next to +-pi: about one ulp of pi), 2.07e-7 relative, 1.4e-7 relative below 1e-3; exact 0 at (0, 1) and (0, 0),
+//             the fp32 pi at (0, -1)
+//   asin_lm   1.66e-7 absolute, 2.61e-7 relative; exact 0 at 0 and the fp32 pi/2 at +-1
+// i.e. inside 4 ulp relative + one ulp of pi (pi/2) behind a fix-up, the budget the device is held to over the whole rotation group by
+// tests/test_gpu_pose_domain.py.
 __device__ __forceinline__ float atan2_lm(float y, float x) {
     const float ax = fabsf(x), ay = fabsf(y);
     const float mx = fmaxf(fmaxf(ax, ay), 1e-30f), mn = fminf(ax, ay);
@@ -243,7 +250,7 @@ __device__ __forceinline__ void pose_metrics(const float (&Rt)[9], const float (
     const float sn = 0.5f * __builtin_sqrtf(CPPF_FMA(a2, a2, CPPF_FMA(a1, a1, a0 * a0)));
     const float cs = 0.5f * (E[0] + E[4] + E[8] - 1.f);
     const float theta = atan2f(sn, cs);
-    rot_err = fmaxf(theta, 8.94427191e-4f);
+    rot_err = theta != theta ? theta : fmaxf(theta, 8.94427191e-4f);  // torch.clamp keeps a NaN (fmaxf would drop it: a valid-looking floor)
 }
 
 // One damped Gauss-Newton update in dual form.  With S = diag(a_rot x3, a_pos x3) the reference scales J and e in place

@@ -478,7 +478,7 @@ __global__ __launch_bounds__(kBlock, quad_min_waves<RB>()) void lm_quad_kernel(c
         const float sn_ = 0.5f * __builtin_sqrtf(CPPF_FMA(a2, a2, CPPF_FMA(a1, a1, a0 * a0)));
         const float cs_ = 0.5f * (qperm<0x00>(dg) + qperm<0x55>(dg) + qperm<0xAA>(dg) - 1.f);
         const float theta = atan2f(sn_, cs_);
-        rot_err = fmaxf(theta, 8.94427191e-4f);
+        rot_err = theta != theta ? theta : fmaxf(theta, 8.94427191e-4f);  // (a NaN stays one, as in pose_metrics)
         if (active && k.is0) {
             if (out.pos_err_m) out.pos_err_m[row] = pos_err;
             if (out.rot_err_rad) out.rot_err_rad[row] = rot_err;

@@ -648,7 +648,7 @@ void orc_pose_metrics_exact(const void* h, const double* x, const double* target
         const REAL vn = SQRT(qe[1] * qe[1] + qe[2] * qe[2] + qe[3] * qe[3]);
         REAL th = 2 * ATAN2(vn, FABS(qe[0]));
         const REAL floor_v = 2 * ACOS((REAL)1 - RC(1e-7));
-        rot_err_rad[r] = th > floor_v ? th : floor_v;
+        rot_err_rad[r] = th != th || th > floor_v ? th : floor_v; /* a NaN stays one, as through torch.clamp */
     }
 }
 
