@@ -1638,6 +1638,55 @@ int cppf_dp_search_tabled(const cppf_robot* robot, const float* q, const float* 
     return check_launch();
 }
 
+static size_t dp_nbest_workspace_words(int k, int T, int n_paths) {  // idxT [T][k], order / alive / far [k], sel [n_paths]
+    return (size_t)T * k + 3 * (size_t)k + (size_t)n_paths;
+}
+
+int cppf_dp_nbest_workspace_bytes(int k, int T, int n_paths, size_t* bytes) {
+    CPPF_REQUIRE(bytes, "bytes is NULL");
+    CPPF_REQUIRE(k >= 1 && T >= 1 && n_paths >= 1, "k, T, n_paths must be >= 1");
+    CPPF_REQUIRE((size_t)k * T <= 0x7fffffffu, "k*T exceeds 2^31-1");
+    *bytes = (dp_nbest_workspace_words(k, T, n_paths) * sizeof(int32_t) + 15) / 16 * 16;
+    return CPPF_OK;
+}
+
+int cppf_dp_nbest(const cppf_robot* robot, const float* q, const float* costsT, const int32_t* memoT, int k, int T, int n_paths,
+                  float min_separation, float prismatic_scaling, void* workspace, float* paths, int32_t* path_idx, float* path_cost,
+                  int32_t* n_found, void* stream) {
+    // every argument is checked before the device is selected (CPPF_ENTER), so that the checks hold for a host-only handle too
+    CPPF_REQUIRE(robot != nullptr, "robot handle is NULL");
+    CPPF_REQUIRE(!(robot->life.load(std::memory_order_acquire) & kRobotDead), "the robot handle was destroyed");
+    CPPF_REQUIRE(k >= 1 && T >= 1 && n_paths >= 1, "k, T, n_paths must be >= 1");
+    CPPF_REQUIRE(std::isfinite(min_separation) && min_separation >= 0.f, "min_separation must be finite and >= 0");
+    CPPF_REQUIRE(q && costsT && memoT && workspace && paths && path_idx && path_cost && n_found, "NULL pointer");
+    CPPF_REQUIRE(((uintptr_t)workspace & 15u) == 0, "workspace must be 16-byte aligned");
+    const int d = robot->desc.ndof;
+    CPPF_REQUIRE((size_t)k * T * d <= 0x7fffffffu, "k*T*d exceeds 2^31-1");
+    CPPF_REQUIRE((size_t)n_paths * T * d <= 0x7fffffffu, "n_paths*T*d exceeds 2^31-1");
+    CPPF_ENTER(robot);
+    hipStream_t st = (hipStream_t)stream;
+    int32_t* const idxT = static_cast<int32_t*>(workspace);
+    int32_t* const order = idxT + (size_t)T * k;
+    int32_t* const alive = order + k;
+    int32_t* const far = alive + k;
+    int32_t* const sel = far + k;
+    const size_t stage = dp_stage_bytes(k, T);
+    if (stage)
+        hipLaunchKernelGGL(dp_trace_all_kernel, dim3(1), dim3(1024), stage, st, memoT, k, T, 1, idxT);
+    else
+        hipLaunchKernelGGL(dp_trace_all_kernel, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, st, memoT, k, T, 0, idxT);
+    const int rc = for_ndof(d, [&](auto dof) {
+        hipLaunchKernelGGL((dp_nbest_select_kernel<decltype(dof)::D>), dim3(1), dim3(1024), 0, st, q, costsT, memoT, k, T, n_paths,
+                           min_separation, robot->chain.pris_mask, prismatic_scaling, idxT, order, alive, far, sel, n_found);
+        return CPPF_OK;
+    });
+    if (rc) return rc;
+    const size_t total = (size_t)n_paths * T * d;
+    hipLaunchKernelGGL(dp_nbest_gather_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, q, costsT, k, T, d, n_paths, idxT,
+                       sel, n_found, paths, path_idx, path_cost);
+    return check_launch();
+}
+
 // ---- RCCL behind the C ABI ------------------------------------------------------------------------------------------------------
 // Declared here instead of including <rccl/rccl.h>: the library is loaded with dlopen so that libcppflow_hip.so has no link-time
 // dependency on it (a process that already holds PyTorch's copy must not get a second one).

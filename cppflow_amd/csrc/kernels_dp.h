@@ -748,3 +748,142 @@ __global__ __launch_bounds__(256) void dp_backtrace_kernel(const float* __restri
         best_path[n] = q[((size_t)best_idx[t] * T + t) * d + j];
     }
 }
+
+// ---- N-best diverse paths out of the tables a finished search has left (cppf_dp_nbest) ------------------------------------------------
+// Every terminal j has a complete best path behind it: idx_j[T-1] = j, idx_j[t-1] = memoT[t][idx_j[t]] (the walk of dp_backtrace_kernel).
+// The terminals are ordered by (costsT[T-1][j], j) -- a cost that is not below +inf counts as +inf, so the first terminal is the one
+// dp_backtrace_kernel picks -- and accepted greedily in that order: a terminal is accepted when its path is at least
+// `min_separation` away from every path accepted before it, sep(a, b) = max over t and joints of |wrap(s (q[idx_a[t],t] - q[idx_b[t],t]))|
+// with the prismatic scale of mjacs_kernel.  Run as rounds: accept the first terminal still alive, then kill -- in parallel over
+// terminals x waypoints -- every terminal closer than `min_separation` to it; at most N rounds.  Three launches on the stream, nothing
+// waits between workgroups: the trace (one lane per terminal), the selection (ONE workgroup of 1024 lanes: every step that needs all
+// terminals' results is separated by a workgroup barrier) and the gather.  The tables are only read.
+
+// One lane per terminal; idxT [T][k] time-major so that the selection's reads at a fixed t are coalesced.  `stage` as in
+// dp_backtrace_kernel: the memo table as bytes in LDS (k <= 256: one workgroup of 1024 lanes copies, the first k walk), else walked in
+// global memory by ceil(k / 256) workgroups.  A table whose search timed out (kDpTimedOut in memoT[0]) holds no paths: nothing is traced.
+__global__ __launch_bounds__(1024) void dp_trace_all_kernel(const int32_t* __restrict__ memoT, int k, int T, int stage,
+                                                            int32_t* __restrict__ idxT) {
+    extern __shared__ uint8_t memo8[];
+    if (memoT[0] & kDpTimedOut) return;  // (uniform)
+    const int j = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (stage) {
+        const int n = T * k;
+        for (int i = threadIdx.x; i < n; i += (int)blockDim.x) memo8[i] = (uint8_t)memoT[i];
+        __syncthreads();
+        if (j >= k) return;
+        int i = j;
+        for (int t = T - 1; t >= 0; --t) {
+            idxT[(size_t)t * k + j] = i;
+            i = min((int)memo8[t * k + i], k - 1);  // (an index of a well-formed table is below k; never read outside the row)
+        }
+    } else {
+        if (j >= k) return;
+        int i = j;
+        for (int t = T - 1; t >= 0; --t) {
+            idxT[(size_t)t * k + j] = i;
+            if (t > 0) i = (int)min((uint32_t)memoT[(size_t)t * k + i], (uint32_t)(k - 1));
+        }
+    }
+}
+
+// the order key of a terminal: (cost, index), a cost that is not below +inf taken as +inf (NaN included) -- the scan of
+// dp_backtrace_kernel never prefers such a terminal to an earlier one either
+__device__ __forceinline__ unsigned long long dp_terminal_key(float c, int j) { return dp_key(c < INFINITY ? c : INFINITY, j); }
+
+// ONE workgroup.  order / alive / far [k] and sel [n_paths] live in the workspace (any k); they are written and read by this
+// workgroup only, with a barrier between every write and the reads that depend on it.  sel[r] = the terminal accepted in round r.
+template <int D>
+__global__ __launch_bounds__(1024) void dp_nbest_select_kernel(const float* __restrict__ q, const float* __restrict__ costsT,
+                                                               const int32_t* __restrict__ memoT, int k, int T, int n_paths,
+                                                               float min_separation, uint32_t pris_mask, float pscale,
+                                                               const int32_t* __restrict__ idxT, int32_t* order, int32_t* alive,
+                                                               int32_t* far, int32_t* sel, int32_t* n_found) {
+    __shared__ int s_next;
+    const int tid = threadIdx.x;
+    if (memoT[0] & kDpTimedOut) {  // (uniform) the search that left the tables has no result: say so, dp_nbest_gather_kernel empties every slot
+        if (tid == 0) n_found[0] = -1;
+        return;
+    }
+    const float* last = costsT + (size_t)(T - 1) * k;
+    for (int j = tid; j < k; j += 1024) {  // rank = terminals in front of j; the keys are distinct, so the ranks are a permutation
+        const unsigned long long key = dp_terminal_key(last[j], j);
+        int rank = 0;
+        for (int i = 0; i < k; ++i) rank += dp_terminal_key(last[i], i) < key ? 1 : 0;
+        order[rank] = j;
+        alive[j] = 1;
+    }
+    const int rounds = min(n_paths, k);
+    if (!(min_separation > 0.f)) {  // nothing is closer than 0: the plain N lowest-cost terminals
+        __syncthreads();
+        for (int r = tid; r < rounds; r += 1024) sel[r] = order[r];
+        if (tid == 0) n_found[0] = rounds;
+        return;
+    }
+    int pos = 0, found = 0;
+    const long long pairs = (long long)k * T;
+    for (int r = 0; r < rounds; ++r) {
+        if (tid == 0) s_next = k;
+        __syncthreads();  // (also: order / alive of the ranking, alive of the previous round)
+        for (int p = pos + tid; p < k; p += 1024)
+            if (alive[order[p]]) {
+                atomicMin(&s_next, p);
+                break;
+            }
+        __syncthreads();
+        const int nxt = s_next;
+        if (nxt >= k) break;  // (uniform) the terminals have run out
+        const int a = order[nxt];
+        if (tid == 0) sel[found] = a;
+        ++found;
+        pos = nxt + 1;
+        if (r + 1 == rounds) break;  // nothing is accepted after this round: nobody asks who is still alive
+        for (int j = tid; j < k; j += 1024) far[j] = 0;
+        __syncthreads();
+        for (long long p = tid; p < pairs; p += 1024) {  // (t, j) = (p / k, p % k): a wavefront reads one stretch of idxT's row t
+            const int t = (int)(p / k), j = (int)(p - (long long)t * k);
+            if (!alive[j]) continue;
+            const int ij = idxT[p], ia = idxT[(size_t)t * k + a];
+            if (ij == ia) continue;  // the two paths share this waypoint's candidate
+            const float* qj = q + ((size_t)ij * T + t) * D;
+            const float* qa = q + ((size_t)ia * T + t) * D;
+            float dq[D];
+#pragma unroll
+            for (int c = 0; c < D; ++c) {
+                dq[c] = qj[c] - qa[c];
+                if ((pris_mask >> c) & 1u) dq[c] *= pscale;
+            }
+            if (max_wrapped_change<D>(dq) >= min_separation) far[j] = 1;  // sep(a, j) >= min_separation <=> some waypoint's change is
+        }
+        __syncthreads();
+        for (int j = tid; j < k; j += 1024)
+            if (alive[j] && !far[j]) alive[j] = 0;  // (the accepted terminal itself included: it is 0 away from itself)
+    }
+    if (tid == 0) n_found[0] = found;
+}
+
+// paths [n_paths][T][d], path_idx [n_paths][T], path_cost [n_paths]: slot s < n_found is terminal sel[s]'s path, the others are empty
+// (NaN, -1, +inf).  One lane per element of `paths`.
+__global__ __launch_bounds__(256) void dp_nbest_gather_kernel(const float* __restrict__ q, const float* __restrict__ costsT, int k, int T,
+                                                              int d, int n_paths, const int32_t* __restrict__ idxT,
+                                                              const int32_t* __restrict__ sel, const int32_t* __restrict__ n_found,
+                                                              float* __restrict__ paths, int32_t* __restrict__ path_idx,
+                                                              float* __restrict__ path_cost) {
+    const size_t n = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (n >= (size_t)n_paths * T * d) return;
+    const int c = (int)(n % d);
+    const size_t r = n / d;
+    const int t = (int)(r % T), s = (int)(r / T);
+    const bool have = s < n_found[0];
+    int i = -1;
+    float v = __builtin_nanf(""), cost = INFINITY;
+    if (have) {
+        const int a = sel[s];
+        i = idxT[(size_t)t * k + a];
+        v = q[((size_t)i * T + t) * d + c];
+        cost = costsT[(size_t)(T - 1) * k + a];
+    }
+    paths[n] = v;
+    if (c == 0) path_idx[r] = i;
+    if (c == 0 && t == 0) path_cost[s] = cost;
+}

@@ -29,7 +29,7 @@ from cppflow_amd.data_type_utils import plan_from_qpath
 from cppflow_amd.data_types import PlannerResult, PlannerSettings, Problem, TimingData
 from cppflow_amd.evaluation_utils import get_mjacs
 from cppflow_amd.optimization import run_lm_optimization
-from cppflow_amd.search import dp_search
+from cppflow_amd.search import dp_search, dp_search_nbest
 
 DEFAULT_RERUN_NEW_K = 125  # planners.py:47
 
@@ -148,10 +148,19 @@ class TrackingSeedProvider:
 
 class Planner:
     def __init__(self, settings: PlannerSettings, robot, seed_provider: Optional[SeedProvider] = None, process_group=None,
-                 candidate_lm_steps: int = 0, device_optimizer: bool = False):
+                 candidate_lm_steps: int = 0, device_optimizer: bool = False, n_search_paths: int = 1,
+                 search_path_separation_rad: float = 0.5):
         """`process_group` / `candidate_lm_steps`: the sharded candidate stage (module docstring); with `candidate_lm_steps` > 0 every
         (candidate, waypoint) row takes that many fused pose-only LM iterations before the masks are evaluated (one launch).
-        `device_optimizer`: the LM optimiser's loop is decided on the device (`run_lm_optimization(device_loop=True)`); same plan."""
+        `device_optimizer`: the LM optimiser's loop is decided on the device (`run_lm_optimization(device_loop=True)`); same plan.
+        `n_search_paths` > 1: the search returns up to that many paths at least `search_path_separation_rad` apart from each other
+        (`dp_search_nbest`; the first one is the path a plain search returns) and `CppFlowPlanner` optimises them together, one
+        trajectory each, and continues with the first valid one.  One rank only."""
+        assert int(n_search_paths) >= 1, "n_search_paths must be >= 1"
+        assert float(search_path_separation_rad) >= 0.0, "search_path_separation_rad must be >= 0"
+        self._n_search_paths = int(n_search_paths)
+        self._search_path_separation_rad = float(search_path_separation_rad)
+        self._search_paths: Optional[torch.Tensor] = None  # [n,T,d]: the last search's paths when n_search_paths > 1
         self._device_optimizer = bool(device_optimizer)
         self._cfg = settings
         self._robot = robot
@@ -175,6 +184,9 @@ class Planner:
         existing = kwargs.get("rerun_data")
         k = self._cfg.k if existing is None else DEFAULT_RERUN_NEW_K
         world = dist.get_world_size(self._group) if dist.is_available() and dist.is_initialized() else 1
+        assert self._n_search_paths == 1 or world == 1, (
+            "n_search_paths > 1 is not supported with more than one rank: the sharded planner keeps one search path"
+        )
         t0 = time()
         if world > 1:
             from cppflow_amd.distributed import padded_shard_size, sharded_candidate_evaluation
@@ -211,7 +223,12 @@ class Planner:
         time_coll = time() - t0
 
         t0 = time()
-        qpath_search = dp_search(self.robot, qs.contiguous(), self_viol, env_viol)
+        if self._n_search_paths > 1:
+            self._search_paths, _, _ = dp_search_nbest(self.robot, qs.contiguous(), self_viol, env_viol, self._n_search_paths,
+                                                       self._search_path_separation_rad)  # fmt: skip
+            qpath_search = self._search_paths[0]
+        else:
+            qpath_search = dp_search(self.robot, qs.contiguous(), self_viol, env_viol)
         time_dp = time() - t0
         debug_info = {}
         if self._cfg.do_return_search_path_mjac:  # (cppflow/planners.py:283-284)
@@ -271,11 +288,21 @@ class CppFlowPlanner(Planner):
         budget = dict(max_n_steps=75, return_if_valid_after_n_steps=int(1e8),
                       convergence_threshold=OPTIMIZATION_CONVERGENCE_THRESHOLD) if self._cfg.anytime_mode_enabled else dict(
             max_n_steps=20, return_if_valid_after_n_steps=0, convergence_threshold=1e6)  # fmt: skip  (planners.py:402-422)
-        opt = run_lm_optimization(problem, search_qpath.contiguous(), tmax_sec=self._cfg.tmax_sec - (time() - t0),
-                                  verbosity=self._cfg.verbosity, device_loop=self._device_optimizer, **budget)  # fmt: skip
+        if self._n_search_paths > 1:
+            # the search's paths as one stack of trajectories [n*T, d]; the device loop lets each alternate and end on its own record
+            n, T = self._search_paths.shape[0], problem.n_timesteps
+            opt = run_lm_optimization(problem, self._search_paths.reshape(n * T, -1).contiguous(),
+                                      tmax_sec=self._cfg.tmax_sec - (time() - t0), verbosity=self._cfg.verbosity, parallel_count=n,
+                                      per_trajectory=self._device_optimizer, device_loop=self._device_optimizer, **budget)  # fmt: skip
+            s = opt.parallel_seed_idx if 0 <= opt.parallel_seed_idx < n else 0
+            x_opt = opt.x_opt.detach()[s * T : (s + 1) * T]
+            debug_info["n_search_paths"], debug_info["optimized_path_index"] = n, s
+        else:
+            opt = run_lm_optimization(problem, search_qpath.contiguous(), tmax_sec=self._cfg.tmax_sec - (time() - t0),
+                                      verbosity=self._cfg.verbosity, device_loop=self._device_optimizer, **budget)  # fmt: skip
+            x_opt = opt.x_opt.detach()
         td.optimizer = time() - t0_opt
         debug_info["n_optimization_steps"] = opt.n_steps_taken
-        x_opt = opt.x_opt.detach()
         if opt.is_valid:
             if problem.initial_configuration is None:
                 return result(x_opt)

@@ -723,6 +723,37 @@ class Robot:
         res = (best_path, best_idx, costsT) + ((memoT,) if return_memo else ())
         return res + ((ran,) if return_method else ())
 
+    def dp_nbest(self, q: torch.Tensor, costsT: torch.Tensor, memoT: torch.Tensor, n_paths: int, min_separation: float,
+                 prismatic_joint_scaling: float = 5.0):
+        """The `n_paths` lowest-cost paths of a finished search that are at least `min_separation` (radians, prismatic joints scaled)
+        apart from each other (`cppf_dp_nbest`): q [k,T,d] and the `costsT` / `memoT` [T,k] of `dp_search(..., return_memo=True)` ->
+        (paths [n_paths,T,d], path_idx [n_paths,T] int32, path_cost [n_paths], n_found [1] int32 -- a DEVICE tensor: nothing is
+        synchronised here).  Slot 0 is the search's own best path; slots from n_found on are NaN / -1 / +inf; n_found = -1 when the
+        tables carry the resident search's timed-out flag."""
+        q = _require_device_tensor(q, "q")
+        costsT = _require_device_tensor(costsT, "costsT")
+        memoT = _require_device_tensor(memoT, "memoT", torch.int32)
+        assert q.dim() == 3 and q.shape[2] == self.ndof, tuple(q.shape)
+        k, T, d = q.shape
+        assert costsT.shape == (T, k) and memoT.shape == (T, k), (tuple(costsT.shape), tuple(memoT.shape), (T, k))
+        n_paths = int(n_paths)
+        dev = q.device
+        nbytes = ctypes.c_size_t(0)
+        _hip.check(_hip.lib().cppf_dp_nbest_workspace_bytes(k, T, n_paths, ctypes.byref(nbytes)))
+        workspace = torch.empty(nbytes.value // 4, dtype=torch.int32, device=dev)
+        paths = torch.empty((n_paths, T, d), dtype=torch.float32, device=dev)
+        path_idx = torch.empty((n_paths, T), dtype=torch.int32, device=dev)
+        path_cost = torch.empty(n_paths, dtype=torch.float32, device=dev)
+        n_found = torch.empty(1, dtype=torch.int32, device=dev)
+        _hip.check(
+            _hip.lib().cppf_dp_nbest(
+                self._handle(dev), q.data_ptr(), costsT.data_ptr(), memoT.data_ptr(), k, T, n_paths, float(min_separation),
+                float(prismatic_joint_scaling), workspace.data_ptr(), paths.data_ptr(), path_idx.data_ptr(), path_cost.data_ptr(),
+                n_found.data_ptr(), _stream_ptr(dev),
+            )  # fmt: skip
+        )
+        return paths, path_idx, path_cost, n_found
+
     def plan_metrics(self, x: torch.Tensor, target: torch.Tensor, self_mask: Optional[torch.Tensor] = None,
                      env_mask: Optional[torch.Tensor] = None, q_init: Optional[torch.Tensor] = None) -> torch.Tensor:  # fmt: skip
         """[S,16] `Plan` metrics (cppflow/data_types.py:140-264) of S paths in one launch; columns PLAN_METRIC_FIELDS.

@@ -77,6 +77,38 @@ def dp_search(
     return best_path
 
 
+def dp_search_nbest(
+    robot,
+    q: torch.Tensor,
+    self_collision_violations: Optional[torch.Tensor],
+    env_collision_violations: Optional[torch.Tensor],
+    n_paths: int,
+    min_separation_rad: float = 0.5,
+    q_costs: Optional[torch.Tensor] = None,
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """`dp_search`, then the `n_paths` lowest-cost paths of its tables that are at least `min_separation_rad` apart from each other
+    (`Robot.dp_nbest`; max over waypoints and joints of the wrapped joint difference, prismatic joints scaled as in the search) ->
+    (paths [n,T,d], path_cost [n], path_idx [n,T]) with 1 <= n <= n_paths found.  paths[0] is what `dp_search` returns, bit for bit.
+    One host read (the number found) after the selection."""
+    assert int(n_paths) >= 1, "n_paths must be >= 1"
+    k, T, d = q.shape
+    if q_costs is None:
+        jlim = joint_limit_almost_violations_3d(robot, q)
+        q_costs = (
+            K_JLIM_COST * jlim
+            + K_COLLISION_COST * env_collision_violations.to(q.device, torch.float32)
+            + K_COLLISION_COST * self_collision_violations.to(q.device, torch.float32)
+        )
+    q_costs = q_costs.contiguous()
+    _, best_idx, costsT, memoT, ran = robot.dp_search(q, q_costs, return_memo=True, return_method=True)
+    if ran == "resident" and int(best_idx[0].item()) < 0:  # as in dp_search: the resident launch's waits expired
+        _, best_idx, costsT, memoT = robot.dp_search(q, q_costs, method="launches", return_memo=True)
+    paths, path_idx, path_cost, n_found = robot.dp_nbest(q, costsT, memoT, n_paths, min_separation_rad)
+    n = int(n_found.item())
+    assert n >= 1, f"dp_nbest found {n} paths"
+    return paths[:n], path_cost[:n], path_idx[:n]
+
+
 def _get_mjacs(q: torch.Tensor, robot, prismatic_joint_scaling: float = 5.0) -> torch.Tensor:
     """[k, k, T-1] maximum joint changes between every pair of candidates at consecutive timesteps
     (cppflow/search.py:100-125)."""

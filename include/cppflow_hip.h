@@ -523,6 +523,26 @@ int cppf_dp_search_tabled(const cppf_robot* robot, const float* q, const float* 
                           float* work_qT, float* work_costsT, int32_t* work_memoT, float* work_table, float* best_path,
                           int32_t* best_idx, void* stream);
 
+/* The N lowest-cost paths of a finished search that are actually different from each other.  Inputs: the candidates q [k,T,d] and
+ * the tables a completed cppf_dp_search / cppf_dp_search_tabled has left -- costsT = work_costsT [T,k], memoT = work_memoT [T,k];
+ * they are read, never written.  Every terminal j has a complete best path behind it (idx_j[T-1] = j, idx_j[t-1] =
+ * memoT[t][idx_j[t]]).  The terminals are ordered by (costsT[T-1][j], j) ascending -- a cost that is not below +inf counts as +inf --
+ * and accepted greedily in that order: a terminal is accepted when its path is at least `min_separation` away from every path
+ * accepted before it, where sep(a, b) = max over waypoints and joints of |wrap(s (q[idx_a[t],t] - q[idx_b[t],t]))|, s =
+ * prismatic_scaling on prismatic joints (as in cppf_mjacs), 1 otherwise; until n_paths are accepted or the terminals run out.
+ * min_separation = 0 gives the plain n_paths lowest-cost terminals.  Slot 0 is the search's own best_path / best_idx, bit for bit.
+ * Outputs (device): paths [n_paths,T,d], path_idx [n_paths,T] (the candidate each waypoint came from), path_cost [n_paths] (the
+ * terminal's cost), n_found [1].  Slots at or beyond n_found hold NaN paths, -1 indices and +inf cost; n_paths > k is allowed.  If
+ * memoT[0] carries the timed-out flag of the resident search (best_idx = -1 there), n_found = -1 and every slot is empty: repeat
+ * the search with CPPF_DP_LAUNCHES.  workspace: cppf_dp_nbest_workspace_bytes(k, T, n_paths) bytes, 16-byte aligned, device.
+ * Three launches on `stream` (trace of all terminals, selection in one workgroup, gather), asynchronous, no host synchronisation.
+ * CPPF_ERR_INVALID, before the device is selected: a NULL / destroyed handle, NULL pointers, k / T / n_paths < 1, a negative or
+ * non-finite min_separation, a misaligned workspace, k*T*d or n_paths*T*d beyond 2^31-1. */
+int cppf_dp_nbest_workspace_bytes(int k, int T, int n_paths, size_t* bytes);
+int cppf_dp_nbest(const cppf_robot* robot, const float* q, const float* costsT, const int32_t* memoT, int k, int T, int n_paths,
+                  float min_separation, float prismatic_scaling, void* workspace, float* paths /*[n_paths,T,d]*/,
+                  int32_t* path_idx /*[n_paths,T]*/, float* path_cost /*[n_paths]*/, int32_t* n_found /*[1]*/, void* stream);
+
 /* ---- seed sharding across the GPUs of one node: RCCL behind the C ABI ---------------------------------------
  * The reference is one process on one device (no collective anywhere in its tree); the MI355X build shards the candidate seeds
  * of cppflow/planners.py:231-251 over the GPUs and needs ONE collective: an all-gather of each rank's packed per-row / per-seed
