@@ -118,6 +118,7 @@ class FullParams(ctypes.Structure):
 
 
 OPT_MODE_POSE, OPT_MODE_DIFF, OPT_MODE_DONE = 0, 1, 2  # CPPF_OPT_MODE_*
+PIN_FIRST, PIN_LAST = 1, 2  # CPPF_PIN_*: waypoint 0 / W-1 of every trajectory is a constant of the optimisation
 OPT_ON_POSE_VALID = {"differencing": 0, "stop": 1, "continue": 2}  # CPPF_OPT_ON_POSE_VALID_*
 
 
@@ -242,11 +243,19 @@ SIGNATURES = {
         ctypes.c_int,
         [_vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(FullParams), _vp, _vp, _vp, _vp, _vp],
     ),
+    "cppf_lm_full_step_pinned": (
+        ctypes.c_int,
+        [_vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(FullParams), ctypes.c_int, _vp, _vp, _vp, _vp, _vp],
+    ),
     "cppf_lm_optimize_workspace_bytes": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
     "cppf_lm_optimize_control_bytes": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(OptloopParams), ctypes.POINTER(ctypes.c_size_t)]),
     "cppf_lm_optimize_enqueue": (
         ctypes.c_int,
         [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(OptloopParams), _vp, _vp, ctypes.c_int, _vp],
+    ),
+    "cppf_lm_optimize_enqueue_pinned": (
+        ctypes.c_int,
+        [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(OptloopParams), ctypes.c_int, _vp, _vp, ctypes.c_int, _vp],
     ),
     "cppf_comm_available": (ctypes.c_int, []),
     "cppf_comm_unique_id": (ctypes.c_int, [_vp]),

@@ -837,10 +837,34 @@ const char* const kGatedFormRefusal =
     "cppflow_hip: the device-side optimiser loop gates the parallel-in-time and the row-per-lane "
     "elimination only (no pose block, no individually weighted differencing rows, CPPF_TUNE_FULL_ROWS on)";
 
-// cppf_lm_full_step; with a gate (the optimiser loop on the device) only the trajectories it opens are stepped
+// What a pinned coupled step refuses, from its arguments alone (before a device is selected, let alone anything launched)
+int full_step_pin_check(const cppf_robot* robot, int S, int W, const cppf_full_params* params, int pin) {
+    CPPF_REQUIRE(pin >= 0 && pin <= (CPPF_PIN_FIRST | CPPF_PIN_LAST), "pin_mask must be a combination of CPPF_PIN_FIRST and CPPF_PIN_LAST");
+    if (pin == 0) return CPPF_OK;
+    CPPF_REQUIRE(robot != nullptr, "robot handle is NULL");
+    CPPF_REQUIRE(!(robot->life.load(std::memory_order_acquire) & kRobotDead), "the robot handle was destroyed");
+    CPPF_REQUIRE(params, "params is NULL");
+    if (params->differencing_mode != 0 || params->pose_do_scale_down_satisfied)
+        return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: a pinned end waypoint is not combined with the \"satisfied\" row options "
+                                          "(differencing_mode != 0, pose_do_scale_down_satisfied)");
+    // Every route to full_solve_wave_kernel, restated from the end of lm_full_step_gated (keep the two in step): up to 8 joints,
+    // no pose block, and neither the parallel-in-time nor the row-per-lane form -- which is CPPF_TUNE_FULL_ROWS = 0 beyond the
+    // parallel-in-time sizes, and also fewer than 3 joints or more than 2^19 waypoints, where the row-per-lane form does not exist.
+    if (S >= 1 && W >= 1 && (size_t)S * W <= 0x7fffffffu && !params->use_pose && robot->desc.ndof <= 8) {
+        const FullStepForm form = full_step_form(robot, (size_t)S * W, W, false, false);
+        if (!form.use_pcr && !form.use_rows)
+            return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: the one-wavefront-per-trajectory elimination (what a step resolves to under "
+                                              "CPPF_TUNE_FULL_ROWS = 0, with fewer than 3 joints or beyond 2^19 waypoints) takes no "
+                                              "pinned end waypoint");
+    }
+    return CPPF_OK;
+}
+
+// cppf_lm_full_step(_pinned); with a gate (the optimiser loop on the device) only the trajectories it opens are stepped
 int lm_full_step_gated(const cppf_robot* robot, const float* x_in, const float* target, const float* virtual_configs, int S, int W,
-                       const cppf_full_params* params, float* work_blocks, float* work_G, float* work_y, float* x_out, void* stream,
-                       const StepGateK gate) {
+                       const cppf_full_params* params, int pin, float* work_blocks, float* work_G, float* work_y, float* x_out,
+                       void* stream, const StepGateK gate) {
+    if (int rc = full_step_pin_check(robot, S, W, params, pin)) return rc;
     CPPF_ENTER(robot);
     CPPF_REQUIRE(params, "params is NULL");
     CPPF_REQUIRE(S >= 0 && W >= 1, "S < 0 or W < 1");
@@ -869,6 +893,7 @@ int lm_full_step_gated(const cppf_robot* robot, const float* x_in, const float* 
     prm.use_env = params->use_env_collisions;
     prm.S = S;
     prm.W = W;
+    prm.pin = pin;
     // the "satisfied" row options (cppflow/optimization_utils.py:514-533, 548-606)
     CPPF_REQUIRE(params->differencing_mode >= 0 && params->differencing_mode <= 2, "differencing_mode must be 0, 1 or 2");
     CPPF_REQUIRE(!params->pose_do_scale_down_satisfied || (params->pose_scale_down >= 0.f && params->pose_scale_down < 1.f),
@@ -1353,11 +1378,18 @@ int cppf_plan_metrics(const cppf_robot* robot, const float* x, const float* targ
     });
 }
 
+int cppf_lm_full_step_pinned(const cppf_robot* robot, const float* x_in, const float* target, const float* virtual_configs, int S,
+                             int W, const cppf_full_params* params, int pin_mask, float* work_blocks, float* work_G, float* work_y,
+                             float* x_out, void* stream) {
+    return lm_full_step_gated(robot, x_in, target, virtual_configs, S, W, params, pin_mask, work_blocks, work_G, work_y, x_out,
+                              stream, StepGateK{nullptr, 0, 0u});
+}
+
 int cppf_lm_full_step(const cppf_robot* robot, const float* x_in, const float* target, const float* virtual_configs, int S,
                       int W, const cppf_full_params* params, float* work_blocks, float* work_G, float* work_y,
                       float* x_out, void* stream) {
-    return lm_full_step_gated(robot, x_in, target, virtual_configs, S, W, params, work_blocks, work_G, work_y, x_out, stream,
-                              StepGateK{nullptr, 0, 0u});
+    return cppf_lm_full_step_pinned(robot, x_in, target, virtual_configs, S, W, params, 0, work_blocks, work_G, work_y, x_out,
+                                    stream);
 }
 
 }  // extern "C"
@@ -1407,6 +1439,12 @@ int cppf_lm_optimize_control_bytes(int S, const cppf_optloop_params* params, siz
 int cppf_lm_optimize_enqueue(const cppf_robot* robot, float* x, const float* target, int S, int W,
                              const cppf_optloop_params* params, void* workspace, int32_t* control, int n_iterations,
                              void* stream) {
+    return cppf_lm_optimize_enqueue_pinned(robot, x, target, S, W, params, 0, workspace, control, n_iterations, stream);
+}
+
+int cppf_lm_optimize_enqueue_pinned(const cppf_robot* robot, float* x, const float* target, int S, int W,
+                                    const cppf_optloop_params* params, int pin_mask, void* workspace, int32_t* control,
+                                    int n_iterations, void* stream) {
     // every argument is checked before the device is selected (CPPF_ENTER), so that the checks hold for a host-only handle too
     CPPF_REQUIRE(robot != nullptr, "robot handle is NULL");
     CPPF_REQUIRE(!(robot->life.load(std::memory_order_acquire) & kRobotDead), "the robot handle was destroyed");
@@ -1421,6 +1459,7 @@ int cppf_lm_optimize_enqueue(const cppf_robot* robot, float* x, const float* tar
     CPPF_REQUIRE(params->trace_capacity >= 0, "trace_capacity must be >= 0");
     CPPF_REQUIRE(params->convergence_threshold >= 0.0, "convergence_threshold must be >= 0");
     CPPF_REQUIRE(params->diff.lm_lambda > 0.f, "diff.lm_lambda must be > 0");
+    if (int rc = full_step_pin_check(robot, S, W, &params->diff, pin_mask)) return rc;
     CPPF_REQUIRE(!params->diff.use_virtual_configs || (params->diff.n_virtual_configs > 0 && 2 * params->diff.n_virtual_configs < W),
                  "2 * n_virtual_configs must be < number of waypoints (optimization_utils.py:449-451)");
     cppf_lm_params lp = {};
@@ -1469,9 +1508,9 @@ int cppf_lm_optimize_enqueue(const cppf_robot* robot, float* x, const float* tar
     const size_t total = n * (size_t)d;
     for (int it = 0; it < n_iterations; ++it) {
         if (int rc = launch_quad(robot, false, n, st, prm, x, target, oq, g_pose)) return rc;
-        if (int rc = lm_full_step_gated(robot, x, target, x, S, W, &params->diff, ws + L.blocks, ws + L.G, ws + L.y, x_new, stream, g_diff))
+        if (int rc = lm_full_step_gated(robot, x, target, x, S, W, &params->diff, pin_mask, ws + L.blocks, ws + L.G, ws + L.y, x_new, stream, g_diff))
             return rc;
-        hipLaunchKernelGGL(optloop_clamp_kernel, dim3(grid_for(total)), dim3(kBlock), 0, st, robot->chain, total, W, x_new, x, g_live);
+        hipLaunchKernelGGL(optloop_clamp_kernel, dim3(grid_for(total)), dim3(kBlock), 0, st, robot->chain, total, W, pin_mask, x_new, x, g_live);
         if (want_masks)
             if (int rc = collision_masks_gated(robot, x, S, W, self_m, env_m, nullptr, nullptr, nullptr, nullptr, stream, g_live)) return rc;
         const uint8_t* const sm = params->constraints.self_collisions_ignored ? nullptr : self_m;

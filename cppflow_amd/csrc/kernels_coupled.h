@@ -35,7 +35,21 @@ struct FullK {
     int32_t diff_mode;  // 0 none, 1 differencing_do_ignore_satisfied (filter + shift to threshold), 2 differencing_do_scale_satisfied
     float diff_thr_rad, diff_thr_m, diff_scale;
     int32_t diff_shift_invalid;  // differencing_scale_down_satisfied_shift_invalid_to_threshold
+    // CPPF_PIN_FIRST | CPPF_PIN_LAST: waypoint 0 / W-1 of every trajectory is a constant of the step.  The system is then the one of
+    // the FREE waypoints [full_t0, full_t1) alone: the pinned waypoint's block is never read, the differencing row to it stays in its
+    // free neighbour's diagonal and right-hand side (the waypoint-local terms below keep asking "is there a waypoint before / after
+    // me on the PATH"), and only the coupling E G E across it is gone (the eliminations ask "... in the SYSTEM").  x_out of a pinned
+    // row is a copy of x_in.  Not combined with the "satisfied" options (refused on the host).
+    int32_t pin;
 };
+__device__ __forceinline__ int full_t0(const FullK& prm) { return prm.pin & 1; }
+__device__ __forceinline__ int full_t1(const FullK& prm) { return prm.W - ((prm.pin >> 1) & 1); }
+// x_out := x_in for one row, bit for bit
+template <int D>
+__device__ __forceinline__ void copy_row(const float* __restrict__ x, float* __restrict__ x_out, size_t row) {
+#pragma unroll
+    for (int j = 0; j < D; ++j) x_out[row * D + j] = x[row * D + j];
+}
 
 // Weight (squared) and residual of ONE differencing row under the "satisfied" options.  rho = the wrapped joint change of the row,
 // a = alpha_differencing (x the prismatic scaling where the reference applies it: not in filter mode, optimization_utils.py:601).
@@ -510,10 +524,12 @@ __global__ __launch_bounds__(64) void full_solve_kernel(const ChainK ch, const F
     }
     const float beta = prm.a_vq * prm.a_diff, beta2 = beta * beta;
 
+    const int f0 = full_t0(prm), f1 = full_t1(prm);  // the free waypoints (all of them without a pin)
     float G[D][D], y[D], xp[D], xc[D], xn[D];
-    load_x<D>(x, base, xc);
+    if (f0 < f1) load_x<D>(x, base + f0, xc);
+    if (f0 > 0 && f0 < f1) load_x<D>(x, base + f0 - 1, xp);
     // ---- forward elimination
-    for (int t = 0; t < T; ++t) {
+    for (int t = f0; t < f1; ++t) {
         const float* blk = blocks + (base + t) * (NT + D);
         float A[D][D], b[D];
         {
@@ -529,7 +545,8 @@ __global__ __launch_bounds__(64) void full_solve_kernel(const ChainK ch, const F
 #pragma unroll
             for (int j = 0; j < D; ++j) b[j] = blk[NT + j];
         }
-        const bool has_next = t + 1 < T, has_prev = t > 0;
+        const bool has_next = t + 1 < T, has_prev = t > 0;  // on the path: the waypoint's own terms
+        const bool cpl_prev = t > f0;                       // in the system: the Schur coupling
         if constexpr (VAR) {
             if (has_prev) load_x<D>(w2next, base + t - 1, a2);  // the coupling with the predecessor
         } else {
@@ -563,7 +580,7 @@ __global__ __launch_bounds__(64) void full_solve_kernel(const ChainK ch, const F
                 for (int j = 0; j < D; ++j) b[j] = CPPF_FMA(-beta2, xv ? v[j] : 0.f, b[j]);
             }
         }
-        if (has_prev) {
+        if (cpl_prev) {
             // D' = A - E G E ,  y = b - E G y_prev   with E = -diag(a2)
             float Gy[D];
 #pragma unroll
@@ -604,7 +621,7 @@ __global__ __launch_bounds__(64) void full_solve_kernel(const ChainK ch, const F
     float dl[D];
 #pragma unroll
     for (int j = 0; j < D; ++j) dl[j] = 0.f;
-    for (int t = T - 1; t >= 0; --t) {
+    for (int t = f1 - 1; t >= f0; --t) {
         const float* gin = workG + (base + t) * NT;
         const float* yin = worky + (base + t) * D;
         float rhs[D], Gt[D][D];
@@ -623,7 +640,7 @@ __global__ __launch_bounds__(64) void full_solve_kernel(const ChainK ch, const F
             if (t + 1 < T) load_x<D>(w2next, base + t, a2);  // the coupling with the successor
         }
 #pragma unroll
-        for (int j = 0; j < D; ++j) rhs[j] = (t + 1 < T) ? CPPF_FMA(a2[j], dl[j], yin[j]) : yin[j];
+        for (int j = 0; j < D; ++j) rhs[j] = (t + 1 < f1) ? CPPF_FMA(a2[j], dl[j], yin[j]) : yin[j];
         float nd[D];
 #pragma unroll
         for (int i = 0; i < D; ++i) {
@@ -641,6 +658,8 @@ __global__ __launch_bounds__(64) void full_solve_kernel(const ChainK ch, const F
         }
         store_x<D>(x_out, base + t, xr);
     }
+    if (f0 > 0) copy_row<D>(x, x_out, base);
+    if (f1 < T) copy_row<D>(x, x_out, base + T - 1);
 }
 
 // Wavefront-parallel form of full_solve_kernel for D <= 8: one wavefront per trajectory, lane l <-> element
@@ -906,8 +925,9 @@ __global__ __launch_bounds__(64) void full_rows_eliminate_kernel(const FullK prm
     static_assert(D <= 16, "one row of the padded block per lane: 8 or 16 lanes per trajectory");
     constexpr int NT = D * (D + 1) / 2, STRIDE = NT + D;
     const int wave = blockIdx.x >> 1, dir = blockIdx.x & 1;
-    const int T = prm.W, m = T / 2;
-    const int start = dir ? T - 1 : 0, sgn = dir ? -1 : 1, len = dir ? T - 1 - m : m;  // waypoint of step tau: start + sgn tau
+    // the chains run over the free waypoints [f0, f1) only (a pinned end is not part of the system) and join in their middle
+    const int f0 = full_t0(prm), f1 = full_t1(prm), m = f0 + (f1 - f0) / 2;
+    const int start = dir ? f1 - 1 : f0, sgn = dir ? -1 : 1, len = dir ? f1 - 1 - m : m - f0;  // waypoint of step tau: start + sgn tau
     if (len <= 0) return;
     RowsLane<D> L = rows_lane<D>(prm, pris_mask, wave, threadIdx.x);
     if (rows_gate<D>(gate, prm, wave, threadIdx.x, L)) return;
@@ -982,8 +1002,8 @@ __global__ __launch_bounds__(64) void full_rows_substitute_kernel(const FullK pr
                                                                   const StepGateK gate) {
     constexpr int NT = D * (D + 1) / 2, STRIDE = NT + D;
     const int wave = blockIdx.x >> 1, dir = blockIdx.x & 1;
-    const int T = prm.W, m = T / 2;
-    const int start = dir ? T - 1 : 0, sgn = dir ? -1 : 1, len = dir ? T - 1 - m : m;
+    const int T = prm.W, f0 = full_t0(prm), f1 = full_t1(prm), m = f0 + (f1 - f0) / 2;
+    const int start = dir ? f1 - 1 : f0, sgn = dir ? -1 : 1, len = dir ? f1 - 1 - m : m - f0;
     RowsLane<D> L = rows_lane<D>(prm, pris_mask, wave, threadIdx.x);
     if (rows_gate<D>(gate, prm, wave, threadIdx.x, L)) return;
     const float* blk = blocks + L.ubase * STRIDE;
@@ -991,6 +1011,10 @@ __global__ __launch_bounds__(64) void full_rows_substitute_kernel(const FullK pr
     const float* yw = worky + L.ubase * D;
     const float* xin = x + L.ubase * D;
     float* xo = x_out + L.ubase * D;
+    // a pinned end goes out as it came in: the wavefront of its side of the path copies it
+    if (L.live && dir == 0 && f0 > 0) xo[L.offy] = xin[L.offy];
+    if (L.live && dir == 1 && f1 < T) xo[(size_t)(T - 1) * D + L.offy] = xin[(size_t)(T - 1) * D + L.offy];
+    if (f1 <= f0) return;  // no free waypoint (wavefront-uniform)
     // ---- the chains' operands, PB steps ahead of their use (a step is ~0.15 us), requested before the join's arithmetic
     constexpr int PB = 16;
     float qG[PB][D], qy[PB], qx[PB];
@@ -1013,14 +1037,14 @@ __global__ __launch_bounds__(64) void full_rows_substitute_kernel(const FullK pr
         for (int c = 0; c < kRowsGW<D>; ++c) A[c] = c < D ? bm[L.offM[c]] : 0.f;
         float rhs = bm[L.offb];
         const float xm = xin[(size_t)m * D + L.offy];
-        if (m > 0) {
+        if (m > f0) {
             float Gp[D];
             const float* gt = gw + (size_t)(m - 1) * (D * D);
 #pragma unroll
             for (int c = 0; c < D; ++c) Gp[c] = gt[L.offG + c];
             rhs = CPPF_FMA(L.a2r, rows_couple<D>(L, Gp, yw[(size_t)(m - 1) * D + L.offy], A), rhs);
         }
-        if (m + 1 < T) {
+        if (m + 1 < f1) {
             float Gn[D];
             const float* gt = gw + (size_t)(m + 1) * (D * D);
 #pragma unroll
@@ -1136,7 +1160,8 @@ __global__ __launch_bounds__(BS) void full_solve_pcr_kernel(const ChainK ch, con
     constexpr bool kLean = CPPF_PCR_LEAN(D, BS, kLds, kSplit);  // which form of the general level (below)
     const int s = blockIdx.x, t = kSplit ? (int)(threadIdx.x & (TW - 1)) : (int)threadIdx.x, T = prm.W;
     const int h = kSplit ? (int)(threadIdx.x / TW) : 0;  // wavefront-uniform
-    const bool act = t < T;
+    const int f0 = full_t0(prm), f1 = full_t1(prm);
+    const bool act = t >= f0 && t < f1;  // the free waypoints: a pinned end is not part of the system (its lane copies it at the end)
     const size_t base = (size_t)s * T;
     auto st_blk = [&](int u) {
         if constexpr (kLds)
@@ -1211,7 +1236,7 @@ __global__ __launch_bounds__(BS) void full_solve_pcr_kernel(const ChainK ch, con
 #pragma unroll
         for (int i = 0; i < D; ++i)
 #pragma unroll
-            for (int j = 0; j < D; ++j) Lt[i * D + j] = (i == j && has_prev) ? -a2[i] : 0.f;  // E = -diag(a^2)
+            for (int j = 0; j < D; ++j) Lt[i * D + j] = (i == j && t > f0) ? -a2[i] : 0.f;  // E = -diag(a^2): no coupling across a pin
     }
     __syncthreads();
 
@@ -1240,7 +1265,7 @@ __global__ __launch_bounds__(BS) void full_solve_pcr_kernel(const ChainK ch, con
                 M[j][i] = v;
             }
     };
-    for (int st = 1; st < T; st <<= 1) {
+    for (int st = 1; st < f1 - f0; st <<= 1) {
         float nD[D][D], ny[D], nL[D][D];
         if (act && h == 0) {
             float Dn[D][D], P[D][D];
@@ -1259,7 +1284,7 @@ __global__ __launch_bounds__(BS) void full_solve_pcr_kernel(const ChainK ch, con
 #pragma unroll
             for (int j = 0; j < D; ++j) ny[j] = h == 0 ? own[NT + j] : 0.f;
             const bool do_m = !kSplit || h == 0, do_p = !kSplit || h == 1;
-            const int tm = do_m ? t - st : -1, tp = do_p ? t + st : T;
+            const int tm = do_m && t - st >= f0 ? t - st : -1, tp = do_p && t + st < f1 ? t + st : T;  // neighbours in the system
             if (st == 1) {
                 if (h == 0) {
                     load_sym(own, nD);
@@ -1274,13 +1299,13 @@ __global__ __launch_bounds__(BS) void full_solve_pcr_kernel(const ChainK ch, con
 #pragma unroll
                     for (int j = 0; j < D; ++j) nL[i][j] = 0.f;
                 // First level: every coupling block is still the diagonal E = -diag(a^2) the assembly wrote (0 above waypoint
-                // 0), so each matrix product below collapses to a row / column scaling.  The results are bit-identical to the
+                // f0), so each matrix product below collapses to a row / column scaling.  The results are bit-identical to the
                 // general branch (its other terms are exact zeros): ~250 instead of ~1 800 multiply-adds for this level.
                 float lt[D], lm[D];
                 int t1 = t;  // (opaque: these sixteen selects are otherwise hoisted out of the level loop and held in registers across it)
                 asm volatile("" : "+v"(t1));
 #pragma unroll
-                for (int j = 0; j < D; ++j) lt[j] = t1 > 0 ? -a2[j] : 0.f, lm[j] = t1 > 1 && tm >= 0 ? -a2[j] : 0.f;
+                for (int j = 0; j < D; ++j) lt[j] = t1 > f0 ? -a2[j] : 0.f, lm[j] = t1 > f0 + 1 && tm >= 0 ? -a2[j] : 0.f;
                 if (tm >= 0) {
                     float P[D][D];
                     const float* nb = st_blk(tm);
@@ -1607,4 +1632,5 @@ __global__ __launch_bounds__(BS) void full_solve_pcr_kernel(const ChainK ch, con
         }
         store_x<D>(x_out, base + t, xr);
     }
+    if (h == 0 && t < T && !act) copy_row<D>(x, x_out, base + t);  // a pinned end
 }

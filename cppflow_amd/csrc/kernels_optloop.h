@@ -134,13 +134,18 @@ __global__ __launch_bounds__(64) void optloop_decide_kernel(const cppf_optloop_p
     }
 }
 
-// x := clamp(x_new) for the trajectories the gate opens (the host loop's `opt_state.x = clamp_to_joint_limits(robot, x_new)`)
-__global__ __launch_bounds__(kBlock) void optloop_clamp_kernel(const ChainK ch, size_t total, int W, const float* __restrict__ x_new,
-                                                               float* __restrict__ x, const StepGateK gate) {
+// x := clamp(x_new) for the trajectories the gate opens (the host loop's `opt_state.x = clamp_to_joint_limits(robot, x_new)`).
+// This launch is the loop's only writer of x, so a pinned end waypoint (CPPF_PIN_FIRST / CPPF_PIN_LAST) is held by skipping its
+// elements here, whichever step wrote x_new.
+__global__ __launch_bounds__(kBlock) void optloop_clamp_kernel(const ChainK ch, size_t total, int W, int pin,
+                                                               const float* __restrict__ x_new, float* __restrict__ x,
+                                                               const StepGateK gate) {
     const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= total) return;
     const size_t row = i / (size_t)ch.ndof;
-    if (!step_open(gate, (int)(row / (size_t)W))) return;
+    const size_t s = row / (size_t)W, t = row - s * (size_t)W;
+    if (((pin & CPPF_PIN_FIRST) && t == 0) || ((pin & CPPF_PIN_LAST) && t + 1 == (size_t)W)) return;
+    if (!step_open(gate, (int)s)) return;
     x[i] = clamp_joint(ch, (int)(i - row * (size_t)ch.ndof), x_new[i]);
 }
 

@@ -35,6 +35,8 @@ class OptimizationProblem:
     verbosity: int
     parallel_count: int
     results_df: Optional[Dict]
+    # _hip.PIN_FIRST | _hip.PIN_LAST: waypoint 0 / W-1 of every trajectory is a constant of the optimisation (its value: the seed's)
+    pin_mask: int = 0
 
     @property
     def robot(self):
@@ -110,8 +112,9 @@ def levenberg_marquardt_full(
     opt_state.x is [parallel_count * W, ndof] and every trajectory is smoothed independently in the same launch."""
     opt_problem.problem.bind_obstacles()
     x_new = opt_problem.robot.lm_full_step(
-        opt_state.x, _unstacked_target(opt_problem), opt_params, virtual_configs=opt_params.virtual_configs
-    )
+        opt_state.x, _unstacked_target(opt_problem), opt_params, virtual_configs=opt_params.virtual_configs,
+        pin=opt_problem.pin_mask,
+    )  # fmt: skip
     if not return_residual:
         return x_new
     # inspection path: the dense (J, r) the reference would have factored (the step above never forms them)
@@ -154,7 +157,12 @@ def run_lm_alternating_loss(
     granularity in this mode (the last valid trajectory is still what comes back).  `per_trajectory=True` (device loop only): every
     one of the `parallel_count` trajectories alternates and terminates by its OWN flags (a finished one is gated off) instead of
     all following one decision; the result is the lowest-index valid trajectory (`parallel_seed_idx`), `x_opt` holds every
-    trajectory's own result."""
+    trajectory's own result.
+
+    `opt_problem.pin_mask` (`run_lm_optimization(pin_first=..., pin_last=...)`): the named end waypoints of every trajectory are
+    constants of the optimisation.  The coupled step takes them as boundary conditions (`cppf_lm_full_step_pinned`); the pose step
+    is the unchanged kernel and its result for those rows is discarded -- here they are put back after the clamp, on the device
+    the clamp (the loop's only writer of x) skips them.  Validity, masks and metrics see the whole path, pinned rows included."""
     assert not return_residuals and not save_images and results_df is None, "debug outputs are not supported"
     assert on_pose_valid in ("differencing", "stop", "continue")
     assert device_loop or (sync_every is None and not per_trajectory), "sync_every / per_trajectory belong to device_loop=True"
@@ -172,6 +180,8 @@ def run_lm_alternating_loss(
     target = _unstacked_target(opt_problem)
     printc = print if verbosity > 1 else (lambda *a, **k: None)
     W = opt_problem.n_timesteps
+    pinned_rows = _pinned_rows(opt_problem.pin_mask, opt_problem.parallel_count, W, opt_state.x.device)
+    x_pinned = opt_state.x[pinned_rows].clone() if pinned_rows is not None else None
     # copies: the loop overwrites virtual_configs (the reference copies for the same reason, :184-187)
     params_diff = OptimizationParameters(**params_diff.__dict__)
     params_pose = OptimizationParameters(**params_pose.__dict__)
@@ -196,6 +206,8 @@ def run_lm_alternating_loss(
             printc(f"i: {i}  --> only pose")
             x_new = levenberg_marquardt_only_pose(opt_problem, opt_state, params_pose)
         opt_state.x = clamp_to_joint_limits(robot, x_new)  # :259
+        if pinned_rows is not None:
+            opt_state.x[pinned_rows] = x_pinned  # (a copy: the same bits the seed held)
         opt_state.n_steps += 1
 
         # one evaluation of every trajectory per iteration: validity maxima, collision counts and the TL measure (the summed
@@ -238,6 +250,18 @@ def run_lm_alternating_loss(
     )
 
 
+def _pinned_rows(pin_mask: int, S: int, W: int, device) -> Optional[torch.Tensor]:
+    """Row indices of the pinned end waypoints of S stacked trajectories of W waypoints, or None without a pin."""
+    from cppflow_amd import _hip
+
+    assert 0 <= pin_mask <= (_hip.PIN_FIRST | _hip.PIN_LAST), pin_mask
+    if pin_mask == 0:
+        return None
+    starts = torch.arange(S, device=device, dtype=torch.long) * W
+    rows = ([starts] if pin_mask & _hip.PIN_FIRST else []) + ([starts + (W - 1)] if pin_mask & _hip.PIN_LAST else [])
+    return torch.unique(torch.cat(rows))
+
+
 DEVICE_LOOP_TIMED_CHUNK = 4  # iterations enqueued between two looks at the clock when the device loop runs under a time limit
 DEVICE_LOOP_TRACE_CAPACITY = 4096  # iterations whose decision the device writes down (an anytime run may take more; those are not traced)
 
@@ -278,7 +302,7 @@ def _run_device_loop(opt_problem, opt_state, params_diff, params_pose, tmax_sec,
     enqueued = 0
     while True:
         k = min(chunk, max_n_steps - enqueued)
-        robot.lm_optimize_enqueue(x, target, prm, workspace, control, k)
+        robot.lm_optimize_enqueue(x, target, prm, workspace, control, k, pin=opt_problem.pin_mask)
         enqueued += k
         host = control.cpu().numpy()  # the one device-to-host copy of this chunk
         rec = host[: C * 16].reshape(C, 16)
@@ -325,10 +349,14 @@ def run_lm_optimization(
     device_loop: bool = False,
     sync_every: Optional[int] = None,
     per_trajectory: bool = False,
+    pin_first: bool = False,
+    pin_last: bool = False,
 ) -> OptimizationResult:
     """Optimise a trajectory (or `parallel_count` seeds at once): x_seed is [parallel_count * W, ndof]
     (cppflow/optimization.py:376-426).  The target path is NOT stacked: rows index it modulo W.
-    `device_loop` / `sync_every` / `per_trajectory`: see `run_lm_alternating_loss`."""
+    `device_loop` / `sync_every` / `per_trajectory`: see `run_lm_alternating_loss`.
+    `pin_first` / `pin_last`: waypoint 0 / W-1 of EVERY trajectory is held at its value in `x_seed` (`x_opt` carries those rows
+    bit for bit) -- a start the robot stands at, a goal configuration that is given.  Any combination is served."""
     if SELF_COLLISIONS_IGNORED:
         warnings.warn("robot-robot are collisions will be ignored during LM optimization")
     if ENV_COLLISIONS_IGNORED:
@@ -337,9 +365,12 @@ def run_lm_optimization(
     assert problem.n_timesteps * parallel_count == x_seed.shape[0]
     assert x_seed.shape[1] == problem.robot.ndof
     assert isinstance(max_n_steps, int), f"error: max_n_steps must be int, is {type(max_n_steps)}"
+    from cppflow_amd import _hip
+
     opt_problem = OptimizationProblem(
-        problem, problem.constraints, x_seed, problem.target_path, verbosity, parallel_count, results_df
-    )
+        problem, problem.constraints, x_seed, problem.target_path, verbosity, parallel_count, results_df,
+        pin_mask=(_hip.PIN_FIRST if pin_first else 0) | (_hip.PIN_LAST if pin_last else 0),
+    )  # fmt: skip
     opt_state = OptimizationState(x_seed.clone(), 0, time())
     return run_lm_alternating_loss(
         opt_problem, opt_state, ALT_LOSS_V2_1_DIFF, ALT_LOSS_V2_1_POSE, return_residuals=False, verbosity=verbosity,

@@ -149,13 +149,18 @@ class TrackingSeedProvider:
 class Planner:
     def __init__(self, settings: PlannerSettings, robot, seed_provider: Optional[SeedProvider] = None, process_group=None,
                  candidate_lm_steps: int = 0, device_optimizer: bool = False, n_search_paths: int = 1,
-                 search_path_separation_rad: float = 0.5):
+                 search_path_separation_rad: float = 0.5, pin_initial_configuration: bool = False):
         """`process_group` / `candidate_lm_steps`: the sharded candidate stage (module docstring); with `candidate_lm_steps` > 0 every
         (candidate, waypoint) row takes that many fused pose-only LM iterations before the masks are evaluated (one launch).
         `device_optimizer`: the LM optimiser's loop is decided on the device (`run_lm_optimization(device_loop=True)`); same plan.
         `n_search_paths` > 1: the search returns up to that many paths at least `search_path_separation_rad` apart from each other
         (`dp_search_nbest`; the first one is the path a plain search returns) and `CppFlowPlanner` optimises them together, one
-        trajectory each, and continues with the first valid one.  One rank only."""
+        trajectory each, and continues with the first valid one.  One rank only.
+        `pin_initial_configuration`: with `problem.initial_configuration` given, `CppFlowPlanner`'s optimiser holds waypoint 0 of
+        every search path (they all start there) fixed (`run_lm_optimization(pin_first=True)`): the plan starts at the initial
+        configuration bit for bit and the transition out of it is one the optimiser saw, instead of accepting any start within
+        SUCCESS_THRESHOLD_initial_q_norm_dist of it or swapping it in afterwards.  Off: the reference's behaviour."""
+        self._pin_initial_configuration = bool(pin_initial_configuration)
         assert int(n_search_paths) >= 1, "n_search_paths must be >= 1"
         assert float(search_path_separation_rad) >= 0.0, "search_path_separation_rad must be >= 0"
         self._n_search_paths = int(n_search_paths)
@@ -288,23 +293,26 @@ class CppFlowPlanner(Planner):
         budget = dict(max_n_steps=75, return_if_valid_after_n_steps=int(1e8),
                       convergence_threshold=OPTIMIZATION_CONVERGENCE_THRESHOLD) if self._cfg.anytime_mode_enabled else dict(
             max_n_steps=20, return_if_valid_after_n_steps=0, convergence_threshold=1e6)  # fmt: skip  (planners.py:402-422)
+        pin_first = self._pin_initial_configuration and problem.initial_configuration is not None
         if self._n_search_paths > 1:
             # the search's paths as one stack of trajectories [n*T, d]; the device loop lets each alternate and end on its own record
             n, T = self._search_paths.shape[0], problem.n_timesteps
             opt = run_lm_optimization(problem, self._search_paths.reshape(n * T, -1).contiguous(),
                                       tmax_sec=self._cfg.tmax_sec - (time() - t0), verbosity=self._cfg.verbosity, parallel_count=n,
-                                      per_trajectory=self._device_optimizer, device_loop=self._device_optimizer, **budget)  # fmt: skip
+                                      per_trajectory=self._device_optimizer, device_loop=self._device_optimizer, pin_first=pin_first,
+                                      **budget)  # fmt: skip
             s = opt.parallel_seed_idx if 0 <= opt.parallel_seed_idx < n else 0
             x_opt = opt.x_opt.detach()[s * T : (s + 1) * T]
             debug_info["n_search_paths"], debug_info["optimized_path_index"] = n, s
         else:
             opt = run_lm_optimization(problem, search_qpath.contiguous(), tmax_sec=self._cfg.tmax_sec - (time() - t0),
-                                      verbosity=self._cfg.verbosity, device_loop=self._device_optimizer, **budget)  # fmt: skip
+                                      verbosity=self._cfg.verbosity, device_loop=self._device_optimizer, pin_first=pin_first,
+                                      **budget)  # fmt: skip
             x_opt = opt.x_opt.detach()
         td.optimizer = time() - t0_opt
         debug_info["n_optimization_steps"] = opt.n_steps_taken
         if opt.is_valid:
-            if problem.initial_configuration is None:
+            if problem.initial_configuration is None or pin_first:  # (pinned: x_opt[0] IS the initial configuration)
                 return result(x_opt)
             if torch.norm(problem.initial_configuration - x_opt[0]) < SUCCESS_THRESHOLD_initial_q_norm_dist:
                 return result(x_opt)

@@ -581,11 +581,13 @@ class Robot:
         return out
 
     def lm_full_step(self, x: torch.Tensor, target: torch.Tensor, opt_params, virtual_configs: Optional[torch.Tensor] = None,
-                     x_out: Optional[torch.Tensor] = None, constraints=None) -> torch.Tensor:  # fmt: skip
+                     x_out: Optional[torch.Tensor] = None, constraints=None, pin: int = 0) -> torch.Tensor:  # fmt: skip
         """One coupled LM step (levenberg_marquardt_full, cppflow/optimization.py:95-144) for every trajectory in
         x [S*W, d]; target [W,7].  `opt_params` is an OptimizationParameters (e.g. ALT_LOSS_V2_1_DIFF); its "satisfied" row
         options (pose scale-down, differencing filter / scale-down: cppflow/optimization_utils.py:514-533, 562-598) are applied
-        on the device, with thresholds from `constraints` (default: opt_params.constraints if present, else DEFAULT_CONSTRAINTS)."""
+        on the device, with thresholds from `constraints` (default: opt_params.constraints if present, else DEFAULT_CONSTRAINTS).
+        `pin` = `_hip.PIN_FIRST | _hip.PIN_LAST`: waypoint 0 / W-1 of every trajectory is held fixed at its value in `x` (it comes
+        back bit for bit; its free neighbour feels it through the differencing row).  Not combined with the "satisfied" options."""
         x = self._x2d(x)
         target = _require_device_tensor(target, "target_path")
         n, W = x.shape[0], target.shape[0]
@@ -605,9 +607,9 @@ class Robot:
         if x_out is None:
             x_out = torch.empty_like(x)
         _hip.check(
-            _hip.lib().cppf_lm_full_step(
+            _hip.lib().cppf_lm_full_step_pinned(
                 self._handle(dev), x.data_ptr(), target.data_ptr(), xv.data_ptr() if xv is not None else None, n // W, W,
-                ctypes.byref(prm), blocks.data_ptr(), G.data_ptr(), y.data_ptr(), x_out.data_ptr(), _stream_ptr(dev),
+                ctypes.byref(prm), int(pin), blocks.data_ptr(), G.data_ptr(), y.data_ptr(), x_out.data_ptr(), _stream_ptr(dev),
             )  # fmt: skip
         )
         return x_out
@@ -653,9 +655,10 @@ class Robot:
         return workspace, control
 
     def lm_optimize_enqueue(self, x: torch.Tensor, target: torch.Tensor, prm: "_hip.OptloopParams", workspace: torch.Tensor,
-                            control: torch.Tensor, n_iterations: int) -> None:
+                            control: torch.Tensor, n_iterations: int, pin: int = 0) -> None:
         """Enqueue `n_iterations` gated iterations of the alternating loop on x [S*W, d] (in place) and return without
-        synchronising; copy `control` back to see what was decided (`_hip.OptloopRecord` per record, then the trace)."""
+        synchronising; copy `control` back to see what was decided (`_hip.OptloopRecord` per record, then the trace).
+        `pin` (`_hip.PIN_FIRST | _hip.PIN_LAST`): the named end rows of every trajectory are never written."""
         xc = self._x2d(x)
         assert xc.data_ptr() == x.data_ptr(), "lm_optimize_enqueue works on x in place: x must be contiguous"
         target = _require_device_tensor(target, "target_path")
@@ -664,8 +667,8 @@ class Robot:
         assert workspace.is_cuda and workspace.dtype == torch.float32 and workspace.is_contiguous()
         assert control.is_cuda and control.dtype == torch.int32 and control.is_contiguous()
         _hip.check(
-            _hip.lib().cppf_lm_optimize_enqueue(
-                self._handle(x.device), x.data_ptr(), target.data_ptr(), n // W, W, ctypes.byref(prm), workspace.data_ptr(),
+            _hip.lib().cppf_lm_optimize_enqueue_pinned(
+                self._handle(x.device), x.data_ptr(), target.data_ptr(), n // W, W, ctypes.byref(prm), int(pin), workspace.data_ptr(),
                 control.data_ptr(), int(n_iterations), _stream_ptr(x.device),
             )  # fmt: skip
         )

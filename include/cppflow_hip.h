@@ -409,6 +409,23 @@ int cppf_lm_full_step(const cppf_robot* robot, const float* x_in, const float* t
                       int W, const cppf_full_params* params, float* work_blocks, float* work_G, float* work_y,
                       float* x_out, void* stream);
 
+/* The same step with the start and / or the goal configuration held fixed.  pin_mask = CPPF_PIN_FIRST | CPPF_PIN_LAST (any
+ * combination; 0 is cppf_lm_full_step bit for bit, anything else CPPF_ERR_INVALID): waypoint 0 and / or W-1 of EVERY trajectory
+ * is a constant of the optimisation, its value whatever x_in holds in that row.  Its columns leave the system: its pose,
+ * collision and virtual-config rows vanish, the differencing row to its free neighbour n keeps n's column only (a_j^2 on the
+ * diagonal of n's block, -+ a_j^2 wrap(x_n - x_p) on its right-hand side, as for any other neighbour), and the coupling between
+ * the two is gone -- a boundary condition of the block elimination.  Virtual-config membership (t < n or t >= W - n) stays indexed
+ * on the full path.  x_out of a pinned row is a copy of x_in (no arithmetic touches it); with no free waypoint (W = 1, or W = 2
+ * with both ends pinned) x_out == x_in.  Same workspaces as cppf_lm_full_step.  Served by the parallel-in-time, the row-per-lane
+ * and the one-lane elimination; CPPF_ERR_UNSUPPORTED -- before anything is launched or a device selected -- together with the
+ * "satisfied" row options (differencing_mode != 0, pose_do_scale_down_satisfied) and for the one-wavefront-per-trajectory
+ * cross-check kernel (CPPF_TUNE_FULL_ROWS = 0 beyond the parallel-in-time form's sizes). */
+#define CPPF_PIN_FIRST 1
+#define CPPF_PIN_LAST 2
+int cppf_lm_full_step_pinned(const cppf_robot* robot, const float* x_in, const float* target, const float* virtual_configs, int S,
+                             int W, const cppf_full_params* params, int pin_mask, float* work_blocks, float* work_G,
+                             float* work_y, float* x_out, void* stream);
+
 /* ---- the alternating LM optimiser loop on the device (run_lm_alternating_loss, cppflow/optimization.py:147-373) -------------------
  * cppf_lm_optimize_enqueue() enqueues `n_iterations` iterations of  { pose step | coupled step ; clamp ; capsule masks ; plan
  * metrics ; decide }  on `stream` and returns without synchronising.  Which step an iteration takes, whether the trajectory is
@@ -481,6 +498,13 @@ int cppf_lm_optimize_control_bytes(int S, const cppf_optloop_params* params, siz
 int cppf_lm_optimize_enqueue(const cppf_robot* robot, float* x, const float* target, int S, int W,
                              const cppf_optloop_params* params, void* workspace, int32_t* control, int n_iterations,
                              void* stream);
+/* The loop with pinned end waypoints (pin_mask as for cppf_lm_full_step_pinned; 0 is cppf_lm_optimize_enqueue bit for bit): the rows
+ * of x that the mask names are never written -- the pose step and the coupled step both write the workspace, and the clamp, the
+ * loop's only writer of x, skips them.  Masks, metrics and the decision see the whole path, pinned rows included.  Same workspace
+ * and control block. */
+int cppf_lm_optimize_enqueue_pinned(const cppf_robot* robot, float* x, const float* target, int S, int W,
+                                    const cppf_optloop_params* params, int pin_mask, void* workspace, int32_t* control,
+                                    int n_iterations, void* stream);
 
 /* _get_mjacs (cppflow/search.py:100-125): q [k,T,d] -> mjacs [k,k,T-1], mjacs[i,j,t] = max over joints of
  * |wrap(s (q[i,t+1] - q[j,t]))| with s = prismatic_scaling on prismatic joints.  cppf_dp_search does not need it (it never

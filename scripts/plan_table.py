@@ -13,7 +13,13 @@ synchronize (TimingData.ikflow is host time up to the provider's return, which f
 `--device-loop` writes a second table instead: per problem (LmIk provider) the optimiser stage with the host loop and with the loop
 decided on the device (`CppFlowPlanner(device_optimizer=True)`), same process, alternating, median of `--repeats` plans each after one
 warm-up plan of either kind; and the cost of enqueuing gated-off iterations behind a finished loop (host time per iteration to
-enqueue, device time per iteration to drain), which is what enqueuing ahead pays for."""
+enqueue, device time per iteration to drain), which is what enqueuing ahead pays for.
+
+`--pin` writes a third table (profiles/plan_table_pinned.txt): per problem (Tracking provider) the initial configuration is row 0 of
+the problem's own unpinned valid plan; then the planner runs from it twice -- the swap route (`pin_initial_configuration=False`:
+accept a start within 0.2 rad, else swap q0 in) and the pinned route (`True`: waypoint 0 held fixed through the optimiser) -- and
+the table puts side by side: valid or not, the failing constraint, LM steps, `initial_q_norm_dist` and the joint change of
+transition 0 -> 1 (max over the joints; degrees over the revolute, cm over the prismatic ones)."""
 
 import argparse
 import os
@@ -157,10 +163,62 @@ def main_device_loop(a, names):
         f.write("\n".join(lines) + "\n")
 
 
+def first_transition(plan, robot):
+    """(max |revolute joint change| in degrees, max |prismatic joint change| in cm) of transition 0 -> 1 of the plan"""
+    import math
+
+    rev, pris = robot.split_configs_to_revolute_and_prismatic(plan.q_path[1:2] - plan.q_path[0:1])
+    rev = (torch.remainder(rev + math.pi, 2 * math.pi) - math.pi).abs()
+    return (math.degrees(float(rev.max())) if rev.numel() else 0.0), (100.0 * float(pris.abs().max()) if pris.numel() else 0.0)
+
+
+def main_pin(a, names):
+    import dataclasses
+
+    device = "cuda:0"
+
+    def plan(problem, pin):
+        settings = PlannerSettings(k=a.k, tmax_sec=a.tmax, anytime_mode_enabled=False, do_rerun_if_large_dp_search_mjac=True,
+                                   do_rerun_if_optimization_fails=False, verbosity=0)  # fmt: skip
+        planner = CppFlowPlanner(settings, problem.robot, seed_provider=TrackingSeedProvider(seed=0), pin_initial_configuration=pin)
+        return planner.generate_plan(problem)
+
+    def cells(res, robot):
+        flags = res.plan.validity_flags()
+        deg, cm = first_transition(res.plan, robot)
+        failed = ",".join(f for f, ok in flags.items() if not ok) or "-"
+        return (f"{str(res.plan.is_valid):5s} {res.debug_info.get('n_optimization_steps', 0):3d} {res.plan.initial_q_norm_dist:9.2e} {deg:7.3f} {cm:6.3f} "
+                f"{res.plan.mjac_deg:7.3f} {res.plan.mjac_cm:6.3f} {failed:24s}")  # fmt: skip
+
+    plan(load("panda__1cube_mini", device), False)  # warm-up
+    side = f"{'valid':5s} {'lm':>3s} {'q0_dist':>9s} {'t01_deg':>7s} {'t01_cm':>6s} {'mjacdeg':>7s} {'mjaccm':>6s} {'failed':24s}"
+    lines = [f"# scripts/plan_table.py --pin: CppFlowPlanner.generate_plan (Tracking provider, k = {a.k}, tmax_sec = {a.tmax}, constraints "
+             "0.01 cm / 0.1 deg / 7 deg / 2 cm) from an initial configuration = row 0 of the problem's own unpinned valid plan; the swap "
+             "route (pin_initial_configuration=False) and the pinned route (True) side by side.  q0_dist = initial_q_norm_dist (rad), "
+             "t01 = the joint change of transition 0 -> 1, mjac = the plan's maximum joint change",
+             f"# torch {torch.__version__}, device {torch.cuda.get_device_name(0)}",
+             f"{'problem':26s} {'T':>4s} | swap: {side} | pinned: {side}"]  # fmt: skip
+    print("\n".join(lines), flush=True)
+    for name in names:
+        problem = load(name, device)
+        base = plan(problem, False)
+        if not base.plan.is_valid:
+            ln = f"{name:26s} {problem.n_timesteps:4d} | no valid unpinned plan to take q0 from"
+        else:
+            with_q0 = dataclasses.replace(problem, initial_configuration=base.plan.q_path[0:1].clone())
+            ln = f"{name:26s} {problem.n_timesteps:4d} | swap: {cells(plan(with_q0, False), problem.robot)} | pinned: {cells(plan(with_q0, True), problem.robot)}"
+        print(ln, flush=True)
+        lines.append(ln)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--device-loop", action="store_true", help="the optimiser stage, host loop vs device loop (a table of its own)")
+    ap.add_argument("--pin", action="store_true", help="swap route vs pinned initial configuration (a table of its own)")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--problems", default=",".join(README_PROBLEMS + FIXTURES))
     ap.add_argument("--k", type=int, default=175)
@@ -170,7 +228,9 @@ def main():
     assert torch.cuda.is_available(), "plan_table.py runs the planner on the MI355X"
     names = [n for n in a.problems.split(",") if n]
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "plan_table_device_loop.txt" if a.device_loop else "plan_table.txt")
+        a.out = os.path.join(ROOT, "profiles", "plan_table_pinned.txt" if a.pin else "plan_table_device_loop.txt" if a.device_loop else "plan_table.txt")
+    if a.pin:
+        return main_pin(a, names)
     if a.device_loop:
         return main_device_loop(a, names)
     # warm-up: the first planning call of a process pays for allocator growth and library loading
