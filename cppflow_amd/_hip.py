@@ -183,6 +183,7 @@ class LmOutputs(ctypes.Structure):
 
 
 MAX_BATCH = 16  # CPPF_MAX_BATCH
+MAX_SCENE_OBSTACLES = 4096  # CPPF_MAX_SCENE_OBSTACLES
 
 
 class LmBatchItem(ctypes.Structure):
@@ -219,6 +220,11 @@ SIGNATURES = {
     "cppf_lm_batch_launch": (ctypes.c_int, [_vp, _vp]),
     "cppf_lm_batch_destroy": (None, [_vp]),
     "cppf_collision_masks": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cppf_scene_workspace_bytes": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
+    "cppf_scene_env_collisions": (
+        ctypes.c_int,
+        [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp],
+    ),
     "cppf_self_collision_distances": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _vp]),
     "cppf_env_collision_distances": (
         ctypes.c_int,

@@ -2,6 +2,8 @@
 
 Each function is one launch of the collision kernel over all k*T rows; the distance matrices of the reference
 (`[k*T, P]`, one per obstacle) are never written to HBM -- the min / "< 0" / OR reduction happens in registers.
+A problem with more than 8 cuboids (`Problem.uses_scene`) answers its env half from the scene kernel over ALL of its cuboids
+(`Problem.collision_masks`) and its self half from the same launch as before; with up to 8 nothing differs.
 The klampt exact-mesh variants (`:89-131`) are out of scope.
 """
 
@@ -22,8 +24,7 @@ def get_only_non_colliding_qpaths(
 def qpaths_batched_env_collisions(problem, q: torch.Tensor) -> torch.Tensor:
     """q [k, T, d] -> bool [k, T]: the config touches any of the problem's cuboids (collision_detection.py:27-49)."""
     assert q.dim() == 3, f"q must be [k x ntimesteps x n_dofs], is {tuple(q.shape)}"
-    problem.bind_obstacles()
-    return problem.robot.collision_masks(q, only=("env",))["env_mask"]
+    return problem.collision_masks(q, only=("env",))["env_mask"]
 
 
 def qpaths_batched_self_collisions(problem, q: torch.Tensor) -> torch.Tensor:
@@ -34,8 +35,7 @@ def qpaths_batched_self_collisions(problem, q: torch.Tensor) -> torch.Tensor:
 
 def qpaths_batched_collisions(problem, q: torch.Tensor):
     """Both masks from ONE launch (the native form of planners.py:234-251): (self [k,T], env [k,T])."""
-    problem.bind_obstacles()
-    r = problem.robot.collision_masks(q, only=("self", "env"))
+    r = problem.collision_masks(q, only=("self", "env"))
     return r["self_mask"], r["env_mask"]
 
 
@@ -46,8 +46,7 @@ def self_colliding_configs_capsule(problem, qpath: torch.Tensor) -> torch.Tensor
 
 def env_colliding_configs_capsule(problem, qpath: torch.Tensor) -> torch.Tensor:
     """qpath [T, d] -> bool [T] (collision_detection.py:77-86)."""
-    problem.bind_obstacles()
-    return problem.robot.collision_masks(qpath.unsqueeze(0), only=("env",))["env_mask"][0]
+    return problem.collision_masks(qpath.unsqueeze(0), only=("env",))["env_mask"][0]
 
 
 def env_colliding_links_capsule(problem, q: torch.Tensor) -> List[str]:

@@ -65,6 +65,7 @@ constexpr int kBlock = CPPF_BLOCK;
 #include "kernels_coupled.h"
 #include "kernels_dp.h"
 #include "kernels_optloop.h"
+#include "kernels_scene.h"
 
 // ---- host side --------------------------------------------------------------------------------------------------------------
 
@@ -1723,6 +1724,103 @@ int cppf_dp_nbest(const cppf_robot* robot, const float* q, const float* costsT, 
     const size_t total = (size_t)n_paths * T * d;
     hipLaunchKernelGGL(dp_nbest_gather_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, q, costsT, k, T, d, n_paths, idxT,
                        sel, n_found, paths, path_idx, path_cost);
+    return check_launch();
+}
+
+// ---- obstacle scenes (kernels_scene.h) --------------------------------------------------------------------------------------------
+int cppf_scene_workspace_bytes(int n_rows, int n_obs, size_t* bytes) {
+    CPPF_REQUIRE(bytes, "bytes is NULL");
+    CPPF_REQUIRE(n_rows >= 0, "n_rows < 0");
+    CPPF_REQUIRE(n_obs >= 0 && n_obs <= CPPF_MAX_SCENE_OBSTACLES, "n_obs out of range (0 .. CPPF_MAX_SCENE_OBSTACLES)");
+    // one 64-bit key per row, one 32-bit key per cuboid (kernels_scene.h); never 0, so that "workspace is NULL" stays a refusal
+    *bytes = ((size_t)n_rows * sizeof(unsigned long long) + (size_t)n_obs * sizeof(uint32_t) + 15) / 16 * 16 + 16;
+    return CPPF_OK;
+}
+
+int cppf_scene_env_collisions(const cppf_robot* robot, const float* q, int S, int W, const float* box_lo, const float* box_hi, int n_obs,
+                              float reach_m, uint8_t* env_mask, float* min_env, int32_t* nearest_obs, float* obs_min, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+    // every argument is checked before the device is selected (CPPF_ENTER), so that the checks hold for a host-only handle too
+    CPPF_REQUIRE(robot != nullptr, "robot handle is NULL");
+    CPPF_REQUIRE(!(robot->life.load(std::memory_order_acquire) & kRobotDead), "the robot handle was destroyed");
+    CPPF_REQUIRE(S >= 0 && W >= 0, "S / W < 0");
+    const size_t n = (size_t)S * W;
+    CPPF_REQUIRE(n <= 0x7fffffffu, "S*W exceeds 2^31-1 rows");
+    CPPF_REQUIRE(n_obs >= 0 && n_obs <= CPPF_MAX_SCENE_OBSTACLES, "n_obs out of range (0 .. CPPF_MAX_SCENE_OBSTACLES)");
+    CPPF_REQUIRE(reach_m >= 0.f, "reach_m must be in [0, +inf] (not NaN, not negative)");
+    CPPF_REQUIRE(n == 0 || (q && env_mask), "q / env_mask is NULL");
+    CPPF_REQUIRE(n_obs == 0 || (box_lo && box_hi), "box_lo / box_hi is NULL");
+    CPPF_REQUIRE(workspace, "workspace is NULL");
+    CPPF_REQUIRE(((uintptr_t)workspace & 15u) == 0, "workspace must be 16-byte aligned");
+    size_t need = 0;
+    if (int rc = cppf_scene_workspace_bytes((int)n, n_obs, &need)) return rc;
+    CPPF_REQUIRE(workspace_bytes >= need, "workspace is smaller than cppf_scene_workspace_bytes(S*W, n_obs)");
+    const int d = robot->desc.ndof;
+    if (d < 3) return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: kernels are built for ndof in 3..12");
+    const bool table = use_table(robot);  // (a handle specialised at run time takes the generic form: same bits)
+    const size_t lds = table ? 0 : robot->lds_bytes;
+    if (lds > (size_t)160 * 1024 - 1024)
+        return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: the generic scene kernel cannot stage this many capsules");
+    CPPF_ENTER(robot);
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0 && (n_obs == 0 || !obs_min)) return CPPF_OK;
+
+    const bool want_min = min_env || nearest_obs || obs_min;
+    SceneK sc;
+    sc.box_lo = box_lo;
+    sc.box_hi = box_hi;
+    sc.row_key = static_cast<unsigned long long*>(workspace);
+    uint32_t* const obs_key = reinterpret_cast<uint32_t*>(sc.row_key + n);
+    sc.obs_key = obs_min ? obs_key : nullptr;
+    sc.n = (int)n;
+    sc.n_obs = n_obs;
+    sc.reach = want_min ? reach_m : 0.f;
+    double r_max = 0.0;
+    for (int c = 0; c < CPPF_MAX_CAPSULES; ++c) sc.cull2[c] = 0.f;
+    for (int c = 0; c < robot->coll.ncaps; ++c) {
+        r_max = std::max(r_max, (double)robot->desc.cap_r[c]);
+        // (reach = 0: cull_threshold of the same double sum as cap_cull[c], i.e. cap_cull[c] itself)
+        sc.cull2[c] = cull_threshold(cap_half_length(robot->desc, c) + (double)robot->desc.cap_r[c] + (double)sc.reach);
+    }
+    sc.tile_cull2 = cull_threshold(r_max + (double)sc.reach);
+    // chunks of cuboids (grid.y): enough workgroups for four per compute unit (four wavefronts per SIMD) where the rows alone do not
+    // give them, in groups of 8 cuboids -- a lone wavefront per SIMD issues at a fraction of the rate, and one plan's rows are a
+    // single workgroup (measured: 1 x 256 rows, 64 cuboids, reach = inf, one chunk of 64: 253 us).  A chunk repeats the capsule FK
+    // of its rows, which is small beside 8 cuboids x every capsule.  The result does not depend on the cut (integer min over keys).
+    const unsigned row_blocks = grid_for(n);
+    const int groups = (n_obs + 7) / 8;
+    int n_chunks = 1;
+    sc.chunk = 64;
+    if (groups > 0 && row_blocks > 0) {
+        const unsigned want_blocks = 4u * (unsigned)(robot->cu_count > 0 ? robot->cu_count : 256);
+        n_chunks = (int)std::min<unsigned>((unsigned)groups, std::max(1u, (want_blocks + row_blocks - 1) / row_blocks));
+        const int groups_per_chunk = (groups + n_chunks - 1) / n_chunks;
+        n_chunks = (groups + groups_per_chunk - 1) / groups_per_chunk;
+        sc.chunk = groups_per_chunk * 8;
+    }
+
+    {
+        // (a launch, not a memset node: a captured hipMemsetAsync of this odd byte count did not take effect on replay)
+        const size_t words = 2 * n + (size_t)n_obs;
+        hipLaunchKernelGGL(scene_init_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, reinterpret_cast<uint32_t*>(workspace), words);
+    }
+    if (n > 0 && n_obs > 0) {
+        const int rc = for_robot(robot, [&](auto tag) {
+            using RB = typename decltype(tag)::type;
+            const auto launch = [&](auto kernel) {
+                if (lds > (size_t)64 * 1024)
+                    CPPF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                hipLaunchKernelGGL(kernel, dim3(row_blocks, (unsigned)n_chunks), dim3(kBlock), lds, st, robot->chain, robot->coll, sc, q);
+                return CPPF_OK;
+            };
+            return want_min ? launch(&scene_kernel<RB, true>) : launch(&scene_kernel<RB, false>);
+        });
+        if (rc) return rc;
+        if (int rc2 = check_launch()) return rc2;
+    }
+    const size_t items = std::max(n, obs_min ? (size_t)n_obs : (size_t)0);
+    hipLaunchKernelGGL(scene_finish_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, sc.row_key, obs_key, (int)n, n_obs,
+                       want_min ? 1 : 0, env_mask, min_env, nearest_obs, obs_min);
     return check_launch();
 }
 

@@ -258,8 +258,7 @@ def plans_from_qpaths(qpaths: torch.Tensor, problem: Problem) -> List[Plan]:
     flat = q.view(S * T, d)
     pose = rb.forward_kinematics(flat).view(S, T, 7)
     pe, re = rb.pose_error_metrics(flat, problem.target_path)
-    problem.bind_obstacles()
-    masks = rb.collision_masks(q, only=("self", "env"))
+    masks = problem.collision_masks(q, only=("self", "env"))  # (more than 8 cuboids: env from the scene kernel, whole scene)
     self_c, env_c = masks["self_mask"], masks["env_mask"]
     if SELF_COLLISIONS_IGNORED:
         self_c = torch.zeros_like(self_c)

@@ -317,6 +317,8 @@ class Problem:
     obstacles_Tcuboids: Optional[List] = field(default_factory=list)
     obstacles_cuboids: Optional[List] = field(default_factory=list)
     obstacles_klampt: Optional[List] = field(default_factory=list)  # kept for signature parity; never populated here
+    # more than 8 cuboids only: indices of the cuboids bound to the robot handle (choose_active_obstacles); None = not chosen yet
+    active_obstacles: Optional[List[int]] = None
 
     @property
     def n_timesteps(self) -> int:
@@ -354,9 +356,90 @@ class Problem:
         if self.initial_configuration is not None:
             assert self.initial_configuration.dim() == 2, "'initial_configuration' should be [1, ndof]"
 
+    @property
+    def n_obstacles(self) -> int:
+        return len(self.obstacles_cuboids or [])
+
+    @property
+    def uses_scene(self) -> bool:
+        """More cuboids than a robot handle holds: the whole scene lives in device memory (`cppflow_amd.scene`), the handle gets
+        an active subset (`choose_active_obstacles`)."""
+        from cppflow_amd.robot_model import MAX_OBSTACLES
+
+        return self.n_obstacles > MAX_OBSTACLES
+
     def bind_obstacles(self) -> None:
-        """Hand this problem's cuboids to the robot's kernels (host-side copy of <= 8 boxes)."""
-        self.robot.set_obstacles(self.obstacles_cuboids or [], self.obstacles_Tcuboids or [])
+        """Hand this problem's cuboids to the robot's kernels (host-side copy of <= 8 boxes).  A scene of more than 8 binds its
+        active set -- the kernels that take obstacles from the handle (the coupled LM step, the fused launch's epilogue) then see
+        those and only those; whole-scene answers come from `collision_masks` / `env_collision_mask`."""
+        if not self.uses_scene:
+            self.robot.set_obstacles(self.obstacles_cuboids or [], self.obstacles_Tcuboids or [])
+            return
+        assert self.active_obstacles is not None, (
+            f"this problem has {self.n_obstacles} cuboids, more than the 8 a robot handle holds, "
+            "and no active set has been chosen: call choose_active_obstacles(q, reach_m) first"
+        )
+        idx = list(self.active_obstacles)
+        self.robot.set_obstacles([self.obstacles_cuboids[i] for i in idx], [self.obstacles_Tcuboids[i] for i in idx])
+
+    def scene(self, device=None):
+        """The problem's cuboids as an `ObstacleScene` on `device` (default: the target path's), built once per device."""
+        from cppflow_amd.scene import ObstacleScene
+
+        dev = torch.device(device) if device is not None else self.target_path.device
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        cache = self.__dict__.setdefault("_scene_cache", {})
+        key = (str(dev), self.n_obstacles)
+        if key not in cache:
+            cache.clear()
+            cache[key] = ObstacleScene.from_cuboids(self.obstacles_cuboids or [], self.obstacles_Tcuboids or [], dev)
+        return cache[key]
+
+    def scene_collisions(self, q: torch.Tensor, reach_m: float = float("inf"),
+                         want=("env_mask", "min_env", "nearest_obs", "obs_min")) -> dict:
+        """`Robot.scene_env_collisions` of q [k, T, d] (or [n, d]) against ALL of this problem's cuboids."""
+        sc = self.scene(q.device)
+        return self.robot.scene_env_collisions(q, sc.lo, sc.hi, reach=reach_m, want=want)
+
+    def choose_active_obstacles(self, q: torch.Tensor, reach_m: float, first=None) -> List[int]:
+        """Pick the <= 8 cuboids the handle's kernels get from the configurations q: those that come closest to any row of q
+        within `reach_m` (`select_active_obstacles` on the scene kernel's `obs_min`; `first`: indices taken before any other).
+        Returns the sorted indices and keeps them in `active_obstacles`.  With <= 8 cuboids every cuboid is active."""
+        from cppflow_amd.robot_model import MAX_OBSTACLES
+        from cppflow_amd.scene import select_active_obstacles
+
+        if not self.uses_scene:
+            return list(range(self.n_obstacles))
+        obs_min = self.scene_collisions(q, reach_m, want=("env_mask", "obs_min"))["obs_min"]
+        self.active_obstacles = select_active_obstacles(obs_min, MAX_OBSTACLES, first=first)
+        return self.active_obstacles
+
+    def env_collision_mask(self, q: torch.Tensor) -> torch.Tensor:
+        """q [k, T, d] -> bool [k, T]: the configuration touches ANY cuboid of the problem, however many there are."""
+        return self.collision_masks(q, only=("env",))["env_mask"]
+
+    def collision_masks(self, q: torch.Tensor, only=None, want_min_dists: bool = False) -> dict:
+        """`Robot.collision_masks` against this problem's obstacles.  Up to 8 cuboids: exactly that launch on the bound handle.
+        More: `env_mask` (and `min_env`) come from the scene kernel over the whole scene, everything else from the existing
+        launch, which is then not asked for its env half; `ext_cost` is re-formed from the three masks (100 jlim + 1000 env +
+        1000 self, exact in fp32 as in the kernel)."""
+        if not self.uses_scene:
+            self.bind_obstacles()
+            return self.robot.collision_masks(q, want_min_dists=want_min_dists, only=only)
+        parts = ("self", "env", "jlim") if only is None else tuple(only)
+        assert set(parts) <= {"self", "env", "jlim"} and len(parts) > 0, parts
+        rest = tuple(p for p in parts if p != "env")
+        res = self.robot.collision_masks(q, want_min_dists=want_min_dists, only=rest) if rest else {}
+        if "env" in parts:
+            sc = self.scene_collisions(q, want=("env_mask", "min_env") if want_min_dists else ("env_mask",))
+            res["env_mask"] = sc["env_mask"]
+            if want_min_dists:
+                res["min_env"] = sc["min_env"]
+        if only is None:
+            res["ext_cost"] = (100.0 * res["jlim_mask"].to(torch.float32) + 1000.0 * res["env_mask"].to(torch.float32)
+                               + 1000.0 * res["self_mask"].to(torch.float32))  # fmt: skip
+        return res
 
     def __str__(self) -> str:
         return (

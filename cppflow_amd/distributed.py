@@ -680,6 +680,10 @@ def sharded_candidate_evaluation(problem, qs_local: torch.Tensor, lm_steps: int 
     rb = problem.robot
     k_local, T, d = qs_local.shape
     world = dist.get_world_size(group) if dist.is_initialized() else 1
+    assert not problem.uses_scene, (
+        f"{problem.n_obstacles} cuboids: the sharded candidate stage takes its obstacles from the robot handle (at most 8) in the fused launch's epilogue; "
+        "problems with more than 8 cuboids are served by CppFlowPlanner / run_lm_optimization and Problem.collision_masks"
+    )
     problem.bind_obstacles()
     rb.set_joint_limit_padding(DEFAULT_JLIM_SAFETY_PADDING_REVOLUTE, DEFAULT_JLIM_SAFETY_PADDING_PRISMATIC)  # search.py:20-21
     qs_local = qs_local.contiguous()

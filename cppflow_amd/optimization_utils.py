@@ -351,8 +351,7 @@ def evaluate_seeds(problem, target_path: torch.Tensor, x: torch.Tensor, parallel
     robot = problem.robot
     self_m = env_m = None
     if not (SELF_COLLISIONS_IGNORED and ENV_COLLISIONS_IGNORED):
-        problem.bind_obstacles()
-        masks = robot.collision_masks(x.view(parallel_count, W, -1), only=("self", "env"))
+        masks = problem.collision_masks(x.view(parallel_count, W, -1), only=("self", "env"))  # (always the whole scene)
         self_m = None if SELF_COLLISIONS_IGNORED else masks["self_mask"].view(-1)
         env_m = None if ENV_COLLISIONS_IGNORED else masks["env_mask"].view(-1)
     return robot.plan_metrics(x, target, self_m, env_m).cpu()

@@ -311,6 +311,8 @@ class CppFlowPlanner(Planner):
             x_opt = opt.x_opt.detach()
         td.optimizer = time() - t0_opt
         debug_info["n_optimization_steps"] = opt.n_steps_taken
+        if problem.uses_scene:  # (more than 8 cuboids: what the optimiser's kernels were given, and how often it was chosen)
+            debug_info["scene_selection_rounds"], debug_info["active_obstacles"] = opt.scene_selection_rounds, opt.active_obstacles
         if opt.is_valid:
             if problem.initial_configuration is None or pin_first:  # (pinned: x_opt[0] IS the initial configuration)
                 return result(x_opt)

@@ -502,6 +502,47 @@ class Robot:
                 res[k] = res[k].view(torch.bool)
         return res
 
+    def scene_env_collisions(self, q: torch.Tensor, box_lo: torch.Tensor, box_hi: torch.Tensor, reach: float = float("inf"),
+                             want: Sequence[str] = ("env_mask", "min_env", "nearest_obs", "obs_min")) -> Dict[str, torch.Tensor]:
+        """q [S, W, d] (or [n, d]) against the O <= 4096 axis-aligned cuboids box_lo / box_hi [O, 3] (device, world-frame corners:
+        `cppflow_amd.scene.ObstacleScene`) in one call (`cppf_scene_env_collisions`); the handle's own obstacles are not involved.
+        env_mask (bool, always returned), min_env (float: the minimum distance where it is < reach, else +inf), nearest_obs (int32:
+        the lowest cuboid index attaining it, else -1) are shaped like q without its last axis; obs_min [O] is the per-cuboid
+        minimum over all rows where < reach, else +inf.  Asking for env_mask alone takes the form without square roots."""
+        q = _require_device_tensor(q, "q")
+        assert q.dim() in (2, 3) and q.shape[-1] == self.ndof, f"q must be [k, ntimesteps, {self.ndof}] or [n, {self.ndof}], is {tuple(q.shape)}"
+        lead = tuple(q.shape[:-1])
+        S, W = (1, lead[0]) if q.dim() == 2 else lead
+        dev = q.device
+        box_lo, box_hi = _require_device_tensor(box_lo, "box_lo"), _require_device_tensor(box_hi, "box_hi")
+        assert box_lo.dim() == 2 and box_lo.shape[1] == 3 and box_hi.shape == box_lo.shape, (tuple(box_lo.shape), tuple(box_hi.shape))
+        assert box_lo.device == dev and box_hi.device == dev, "q, box_lo and box_hi must be on one device"
+        O = int(box_lo.shape[0])
+        want = tuple(want)
+        assert set(want) <= {"env_mask", "min_env", "nearest_obs", "obs_min"}, want
+        res: Dict[str, torch.Tensor] = {"env_mask": torch.empty(lead, dtype=torch.uint8, device=dev)}
+        if "min_env" in want:
+            res["min_env"] = torch.empty(lead, dtype=torch.float32, device=dev)
+        if "nearest_obs" in want:
+            res["nearest_obs"] = torch.empty(lead, dtype=torch.int32, device=dev)
+        if "obs_min" in want:
+            res["obs_min"] = torch.empty((O,), dtype=torch.float32, device=dev)
+        nbytes = ctypes.c_size_t()
+        _hip.check(_hip.lib().cppf_scene_workspace_bytes(S * W, O, ctypes.byref(nbytes)))
+        work = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+
+        def ptr(k):
+            return res[k].data_ptr() if k in res else None
+
+        _hip.check(
+            _hip.lib().cppf_scene_env_collisions(
+                self._handle(dev), q.data_ptr(), S, W, box_lo.data_ptr(), box_hi.data_ptr(), O, float(reach), ptr("env_mask"),
+                ptr("min_env"), ptr("nearest_obs"), ptr("obs_min"), work.data_ptr(), nbytes.value, _stream_ptr(dev),
+            )  # fmt: skip
+        )
+        res["env_mask"] = res["env_mask"].view(torch.bool)
+        return res
+
     def pose_error_metrics(self, x: torch.Tensor, target: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """(positional error [n] in metres, rotational error [n] in radians); target [W,7], n % W == 0."""
         x = self._x2d(x)

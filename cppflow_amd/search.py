@@ -37,10 +37,13 @@ def joint_limit_almost_violations_3d(
 
 def q_costs_external(robot, q: torch.Tensor, problem=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """(cost [k,T] float32, jlim, env, self masks) in ONE launch, with the default paddings of search.py:20-21."""
-    if problem is not None:
-        problem.bind_obstacles()
     robot.set_joint_limit_padding(DEFAULT_JLIM_SAFETY_PADDING_REVOLUTE, DEFAULT_JLIM_SAFETY_PADDING_PRISMATIC)
-    r = robot.collision_masks(q)
+    if problem is not None and problem.uses_scene:
+        r = problem.collision_masks(q)  # more than 8 cuboids: env (and the cost's env term) against the whole scene
+    else:
+        if problem is not None:
+            problem.bind_obstacles()
+        r = robot.collision_masks(q)
     return r["ext_cost"], r["jlim_mask"], r["env_mask"], r["self_mask"]
 
 

@@ -259,6 +259,26 @@ void cppf_lm_batch_destroy(cppf_lm_batch* batch);                   /* also rele
 int cppf_collision_masks(const cppf_robot* robot, const float* q, int S, int W, uint8_t* self_mask, uint8_t* env_mask,
                          uint8_t* jlim_mask, float* ext_cost, float* min_self, float* min_env, void* stream);
 
+/* Obstacle scenes: q [S*W, d] against n_obs <= CPPF_MAX_SCENE_OBSTACLES axis-aligned cuboids held in DEVICE memory (box_lo / box_hi
+ * [n_obs, 3], world-frame corners, formed as cppf_set_obstacles forms them: translation + local corner in fp32), in one call.  The
+ * handle's own <= CPPF_MAX_OBSTACLES cuboids are neither read nor changed.  With d(r,c,o) = sqrt(seg_box_dist2) - radius of capsule c
+ * -- bit for bit the value cppf_collision_masks' min_env is the minimum of -- and D(r,o) = min_c d(r,c,o):
+ *   env_mask[r]    = any_o D(r,o) < 0                                         (exact whatever reach_m is)
+ *   min_env[r]     = min_o D(r,o) if that is < reach_m, else +inf              (n_obs = 0: +inf, mask 0)
+ *   nearest_obs[r] = the lowest o attaining a finite min_env[r], else -1
+ *   obs_min[o]     = min_r D(r,o) if that is < reach_m, else +inf              (what a planner picks its active cuboids by)
+ * reach_m in [0, +inf]: distances are truncated there, which lets the kernel skip cuboids no row of a wavefront comes near; every
+ * output is bit-identical to the unculled definition and the same on every run.  min_env / nearest_obs / obs_min may be NULL (all
+ * three NULL: the mask-only form, no square roots).  workspace: cppf_scene_workspace_bytes(S*W, n_obs) bytes, 16-byte aligned,
+ * device; its contents on return are scratch.  Three launches on `stream` (keys to all-ones, the scene kernel, the decode), asynchronous, no host synchronisation, capturable
+ * in a graph.  CPPF_ERR_INVALID, before the device is selected: a NULL / destroyed handle, NULL pointers, n_obs out of range, a NaN or
+ * negative reach_m, a short or misaligned workspace.  n_obs = 0 is valid. */
+#define CPPF_MAX_SCENE_OBSTACLES 4096
+int cppf_scene_workspace_bytes(int n_rows, int n_obs, size_t* bytes);
+int cppf_scene_env_collisions(const cppf_robot* robot, const float* q, int S, int W, const float* box_lo, const float* box_hi, int n_obs,
+                              float reach_m, uint8_t* env_mask, float* min_env, int32_t* nearest_obs, float* obs_min, void* workspace,
+                              size_t workspace_bytes, void* stream);
+
 /* Robot.self_collision_distances(x) -> [n, n_pairs] (call site cppflow/collision_detection.py:65) */
 int cppf_self_collision_distances(const cppf_robot* robot, const float* x, int n, float* dists, void* stream);
 
