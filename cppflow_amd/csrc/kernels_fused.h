@@ -12,23 +12,24 @@ __device__ __forceinline__ void load_target(const float* __restrict__ target, in
 
 // What one row hands to the in-kernel per-seed summary (block_seed_summary)
 struct RowSummary {
-    float pos_err = 0.f, rot_err = 0.f, cost = 0.f;
+    float pos_err = 0.f, rot_err = 0.f;
     int self_hit = 0, env_hit = 0, jl = 0;
 };
 
-// DPP reduction of a NON-NEGATIVE value over the 64 lanes of a wavefront into lane 63 (other lanes end up with partial
-// results).  Lanes without a source in a DPP step read the identity 0 (`old` operand), valid for max and for sums here
-// because every reduced quantity is >= 0.  No LDS traffic (ds_bpermute butterflies cost ~50 LDS-pipe ops per wave).
+// DPP reduction of a 32-bit UNSIGNED value over the 64 lanes of a wavefront into lane 63 (other lanes end up with partial
+// results).  Lanes without a source lane in a DPP step read 0 (bound_ctrl zero fill), the identity of both operations (unsigned
+// maximum, integer sum): a DPP move that fills with the consuming operation's identity folds into it, so every step is ONE
+// v_max_u32_dpp / v_add_u32_dpp.  No LDS traffic (ds_bpermute butterflies cost ~50 LDS-pipe ops per wave).
 template <int CTRL>
-__device__ __forceinline__ float dpp_or_zero(float x) {  // lanes without a source lane read 0
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, false));
+__device__ __forceinline__ uint32_t dpp_or_zero(uint32_t x) {  // lanes without a source lane read 0
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xf, 0xf, true);
 }
 
 template <bool IS_MAX>
-__device__ __forceinline__ float wave_reduce_to_lane63(float v) {
-    auto op = [](float a, float b) { return IS_MAX ? fmaxf(a, b) : a + b; };
-    const float s1 = dpp_or_zero<0x111>(v), s2 = dpp_or_zero<0x112>(v), s3 = dpp_or_zero<0x113>(v);  // row_shr:1,2,3
-    v = op(op(v, s1), op(s2, s3));         // the 4 lanes ending here (within a row of 16)
+__device__ __forceinline__ uint32_t wave_reduce_to_lane63(uint32_t v) {
+    auto op = [](uint32_t a, uint32_t b) { return IS_MAX ? __builtin_elementwise_max(a, b) : a + b; };
+    v = op(v, dpp_or_zero<0x111>(v));      // row_shr:1   -> 2 lanes ending here (within a row of 16)
+    v = op(v, dpp_or_zero<0x112>(v));      // row_shr:2   -> 4 lanes
     v = op(v, dpp_or_zero<0x114>(v));      // row_shr:4   -> 8 lanes
     v = op(v, dpp_or_zero<0x118>(v));      // row_shr:8   -> lane 15 of each row holds its row
     v = op(v, dpp_or_zero<0x142>(v));      // row_bcast:15 -> lanes 31 / 63 hold rows 0-1 / 2-3
@@ -36,22 +37,66 @@ __device__ __forceinline__ float wave_reduce_to_lane63(float v) {
     return v;
 }
 
-// Per-seed summary inside the fused launch (same 8 numbers, bit for bit, as seed_summary_kernel; every reduction is a max
-// or a sum of small integers / multiples of 100, so the order does not matter).  Requires W in {64, 128, 256}: a workgroup
-// then covers whole seeds and a seed is 1, 2 or 4 whole wavefronts.  Joint changes need the NEXT waypoint's final q:
-// lane + 1 through DPP wave_shl:1, the first lane of the next wavefront through LDS.
+// The bit pattern of nan_to_inf(x) for an x that is +0, positive or NaN -- NEVER -0 or negative: callers form x as
+// constant * fabsf(.), whose sign bit is clear by construction.  Among such patterns the unsigned order IS the float order
+// (+0 = 0 < denormals < normals < +inf = 0x7f800000 < every NaN), so a maximum of them can be taken with integer
+// instructions, bit for bit, and nan_to_inf is one unsigned minimum against +inf's pattern.
+__device__ __forceinline__ uint32_t nonneg_bits_nan_to_inf(float x) {
+    return __builtin_elementwise_min(__builtin_bit_cast(uint32_t, x), 0x7f800000u);
+}
+
 // A workgroup barrier for an exchange through LDS ONLY.  __syncthreads() also waits for every global access in flight
 // (s_waitcnt vmcnt(0)) -- here the row's 13 output stores, issued just before: a memory round trip for nothing.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+// max over the revolute / prismatic joints of nan_to_inf(|change|) in degrees / cm, as bit patterns (nan_to_inf once, on the maximum:
+// a NaN's pattern is above every number's).  rb.pris(j) is a compile-time constant for a robot-specialised kernel (no prismatic
+// arithmetic at all for an all-revolute arm), a scalar otherwise.
+template <class RB>
+__device__ __forceinline__ void joint_change_maxima(const RB& rb, const float (&dq)[RB::D], const float (&wr)[RB::D], uint32_t& mrev,
+                                                    uint32_t& mpri) {
+    const float rad2deg = 57.29577951308232087680f;
+    mrev = mpri = 0u;
+#pragma unroll
+    for (int j = 0; j < RB::D; ++j) {
+        // (|c * x| == c * |x| bit for bit, c > 0: rounding is symmetric in the sign)
+        if (rb.pris(j))
+            mpri = __builtin_elementwise_max(mpri, __builtin_bit_cast(uint32_t, 100.f * fabsf(dq[j])));
+        else
+            mrev = __builtin_elementwise_max(mrev, __builtin_bit_cast(uint32_t, rad2deg * fabsf(wr[j])));
+    }
+    mrev = __builtin_elementwise_min(mrev, 0x7f800000u), mpri = __builtin_elementwise_min(mpri, 0x7f800000u);
+}
+
+// whether a kernel's robot can have a prismatic joint: read off the table of a robot-specialised kernel, else assumed
+template <class RB, bool = RB::kStatic>
+struct MayHavePrismatic {
+    static constexpr bool value = true;
+};
+template <class RB>
+struct MayHavePrismatic<RB, true> {
+    static constexpr bool value = RB::Table::pris_mask != 0;
+};
+
+// Per-seed summary inside the fused launch (same 8 numbers, bit for bit, as seed_summary_kernel).  Requires W in {64, 128,
+// 256}: a workgroup then covers whole seeds and a seed is 1, 2 or 4 whole wavefronts.
+//  - The four maxima (position / rotation error, revolute / prismatic joint change) are reduced as UNSIGNED integers on
+//    their bit patterns (nonneg_bits_nan_to_inf: every reduced value is a non-NaN float >= +0, for which the two orders agree).
+//  - The three hit counts travel in one word, jl | env_hit << 10 | self_hit << 20, through one integer-sum chain: a field is at
+//    most W <= 256 < 2^10, so no carry crosses fields.  The cost sum follows from the counts: a row's cost is
+//    100 jl + 1000 env + 1000 self (lm_row_finish), every term and partial sum of the seed's total is an integer below 2^24,
+//    so 100.f * sum(jl) + 1000.f * sum(env) + 1000.f * sum(self) equals the sum of the rows' costs in any order, bit for bit.
+//  - Joint changes need the NEXT waypoint's final q: lane + 1 through DPP wave_shl:1, the first lane of the next wavefront
+//    through LDS.
 template <class RB>
 __device__ __forceinline__ void block_seed_summary(const RB& rb, int W, size_t row, bool active, const float (&q)[RB::D],
                                                    const RowSummary& rs, float* __restrict__ out) {
     constexpr int D = RB::D;
+    static_assert(kBlock <= 256, "a seed's hit counts (<= W <= kBlock) are packed into 10-bit fields");
     __shared__ float s_q[kBlock / 64][D];
-    __shared__ float s_red[kBlock / 64][8];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float rad2deg = 57.29577951308232087680f;
+    __shared__ uint32_t s_red[kBlock / 64][5];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform: scalar LDS bases
+    const float rad2deg = 57.29577951308232087680f, pi = 3.14159265358979323846f;
     const int wps = W >> 6;  // wavefronts per seed: 1, 2 or 4
     if (wps > 1) {
         if (lane == 0) {
@@ -63,52 +108,59 @@ __device__ __forceinline__ void block_seed_summary(const RB& rb, int W, size_t r
     const bool seed_ends_here = ((wave + 1) & (wps - 1)) == 0;  // this wavefront holds the seed's last waypoints
     const bool has_next = active && !(lane == 63 && seed_ends_here);
     const int nw = wave + 1 < kBlock / 64 ? wave + 1 : wave;
-    float mrev = 0.f, mpri = 0.f;
     float dq[D], wr[D];
 #pragma unroll
     for (int j = 0; j < D; ++j) {
-        float qn = dpp_or_zero<0x130>(q[j]);  // wave_shl:1 -- lane i reads lane i + 1
-        qn = (lane == 63) ? s_q[nw][j] : qn;  // (stale but unused when wps == 1: has_next is false there)
-        dq[j] = wr[j] = qn - q[j];
+        // wave_shl:1 -- lane i reads lane i + 1; lane 63 has no source lane and keeps `old`, the next wavefront's first q
+        // (stale but unused when wps == 1: has_next is false there)
+        const float qn = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, s_q[nw][j]), __builtin_bit_cast(int, q[j]),
+                                                                               0x130, 0xf, 0xf, false));
+        dq[j] = qn - q[j];
+        // wrap_pi_all's result whenever 0 <= dq + pi < 2 pi, which holds for every |dq| < pi - 1e-6: the same two roundings
+        wr[j] = (dq[j] + pi) - pi;
     }
-    wrap_pi_all<D>(wr);  // (one rare branch for the row instead of one per joint)
+    uint32_t mrev, mpri;
+    joint_change_maxima<RB>(rb, dq, wr, mrev, mpri);
+    mrev = has_next ? mrev : 0u, mpri = has_next ? mpri : 0u;
+    // Consecutive waypoints of a path never differ by half a turn: ONE wave-uniform test, on the result.  A revolute change
+    // outside (-pi, pi) -- where the unwrapped form is not wrap_pi_all's -- or a NaN shows as >= 171 degrees here (NaN: +inf),
+    // and the wavefront then redoes the set through wrap_pi_all itself (never taken in practice).
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(mrev >= __builtin_bit_cast(uint32_t, 171.f)) != 0ull, 0)) {
 #pragma unroll
-    for (int j = 0; j < D; ++j) {
-        const bool pr = rb.pris(j);
-        const float a = nan_to_inf(pr ? fabsf(100.f * dq[j]) : fabsf(rad2deg * wr[j]));
-        mpri = fmaxf(mpri, pr ? a : 0.f);
-        mrev = fmaxf(mrev, pr ? 0.f : a);
+        for (int j = 0; j < D; ++j) wr[j] = dq[j];
+        wrap_pi_all<D>(wr);
+        uint32_t mr, mp;  // (mp == mpri: prismatic changes are not wrapped)
+        joint_change_maxima<RB>(rb, dq, wr, mr, mp);
+        mrev = has_next ? mr : 0u;
     }
-    float v[8] = {nan_to_inf(100.f * rs.pos_err), nan_to_inf(rad2deg * rs.rot_err), has_next ? mrev : 0.f, has_next ? mpri : 0.f,
-                  (float)rs.self_hit, (float)rs.env_hit, (float)rs.jl, rs.cost};
+    // An inactive lane has q = 0, a zeroed RowSummary and has_next false: all five values are already 0 there, the identity of
+    // both reductions (no select on `active`).
+    uint32_t v[5] = {nonneg_bits_nan_to_inf(100.f * fabsf(rs.pos_err)), nonneg_bits_nan_to_inf(rad2deg * fabsf(rs.rot_err)), mrev, mpri,
+                     (uint32_t)rs.jl | (uint32_t)rs.env_hit << 10 | (uint32_t)rs.self_hit << 20};
 #pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = active ? v[k] : 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = wave_reduce_to_lane63<true>(v[k]);
-#pragma unroll
-    for (int k = 4; k < 8; ++k) v[k] = wave_reduce_to_lane63<false>(v[k]);
+    for (int k = 0; k < 3; ++k) v[k] = wave_reduce_to_lane63<true>(v[k]);
+    if constexpr (MayHavePrismatic<RB>::value) v[3] = wave_reduce_to_lane63<true>(v[3]);  // (else 0 in every lane)
+    v[4] = wave_reduce_to_lane63<false>(v[4]);
     float* o = out + ((uint32_t)row >> (31 - __builtin_clz((uint32_t)W))) * 8;  // seed = row / W, W a power of two
-    if (wps == 1) {
-        if (active && lane == 63) {
+    if (wps > 1) {
+        if (lane == 63) {
 #pragma unroll
-            for (int k = 0; k < 8; ++k) o[k] = v[k];
+            for (int k = 0; k < 5; ++k) s_red[wave][k] = v[k];
         }
-        return;
+        lds_barrier();
     }
-    if (lane == 63) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) s_red[wave][k] = v[k];
-    }
-    lds_barrier();
     if (active && lane == 63 && seed_ends_here) {
-        for (int i = 1; i < wps; ++i) {
+#pragma unroll 1
+        for (int i = 1; i < wps; ++i) {  // (at most three trips)
 #pragma unroll
-            for (int k = 0; k < 4; ++k) v[k] = fmaxf(v[k], s_red[wave - i][k]);
-#pragma unroll
-            for (int k = 4; k < 8; ++k) v[k] += s_red[wave - i][k];
+            for (int k = 0; k < 4; ++k) v[k] = __builtin_elementwise_max(v[k], s_red[wave - i][k]);
+            v[4] += s_red[wave - i][4];
         }
 #pragma unroll
-        for (int k = 0; k < 8; ++k) o[k] = v[k];
+        for (int k = 0; k < 4; ++k) o[k] = __builtin_bit_cast(float, v[k]);
+        const float jl = (float)(v[4] & 1023u), env = (float)((v[4] >> 10) & 1023u), self = (float)(v[4] >> 20);
+        o[4] = self, o[5] = env, o[6] = jl;
+        o[7] = 100.f * jl + 1000.f * env + 1000.f * self;
     }
 }
 
@@ -331,7 +383,6 @@ __device__ __forceinline__ void lm_row_finish(const RB& rb, const CollK& co, con
             c = collide_from_lds<COLL == 2>(co, lds, tid, do_self, do_env);
         }
         rs.self_hit = c.self_hit, rs.env_hit = c.env_hit;
-        rs.cost = 100.f * (float)rs.jl + 1000.f * (float)c.env_hit + 1000.f * (float)c.self_hit;
         write_coll_outputs(row, c, rs.jl, out.self_mask, out.env_mask, out.jlim_mask, out.ext_cost, out.min_self,
                            out.min_env);
     } else {
@@ -415,7 +466,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(lm_waves
     (void)single;  // read through the kernel-argument segment's address (fused_item), like a table entry
     constexpr int D = RB::D;
     __shared__ float s_gate[kBlock / 64][GateLds<D>::kFloats];  // the conditioning gate's slots, per wavefront (lm_solve_gated)
-    // (+ block_seed_summary's s_q [kBlock / 64][D] and s_red [kBlock / 64][8]: the host's bound must cover all of it)
+    // (+ block_seed_summary's s_q [kBlock / 64][D] and s_red [kBlock / 64][5]: the host's bound must cover all of it)
     static_assert(sizeof(s_gate) + (kBlock / 64) * (D + 8) * sizeof(float) <= fused_static_lds_bound(D), "fused_static_lds_bound is stale");
     const RB rb{ch, co};
     uint32_t blk;
