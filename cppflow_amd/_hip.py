@@ -253,6 +253,11 @@ SIGNATURES = {
         ctypes.c_int,
         [_vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(FullParams), ctypes.c_int, _vp, _vp, _vp, _vp, _vp],
     ),
+    "cppf_lm_full_step_scene": (
+        ctypes.c_int,
+        [_vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(FullParams), ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp, _vp,
+         _vp, _vp],
+    ),
     "cppf_lm_optimize_workspace_bytes": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
     "cppf_lm_optimize_control_bytes": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(OptloopParams), ctypes.POINTER(ctypes.c_size_t)]),
     "cppf_lm_optimize_enqueue": (

@@ -62,10 +62,10 @@ constexpr int kBlock = CPPF_BLOCK;
 #include "kernels_track.h"
 #include "kernels_quad.h"
 #include "kernels_eval.h"
+#include "kernels_scene.h"  // (ahead of the coupled step: its scene form shares the box / broadcast helpers)
 #include "kernels_coupled.h"
 #include "kernels_dp.h"
 #include "kernels_optloop.h"
-#include "kernels_scene.h"
 
 // ---- host side --------------------------------------------------------------------------------------------------------------
 
@@ -862,9 +862,10 @@ int full_step_pin_check(const cppf_robot* robot, int S, int W, const cppf_full_p
 }
 
 // cppf_lm_full_step(_pinned); with a gate (the optimiser loop on the device) only the trajectories it opens are stepped
+// `scene` (cppf_lm_full_step_scene; never together with a gate): the environment rows come from its cuboids, not the handle's
 int lm_full_step_gated(const cppf_robot* robot, const float* x_in, const float* target, const float* virtual_configs, int S, int W,
                        const cppf_full_params* params, int pin, float* work_blocks, float* work_G, float* work_y, float* x_out,
-                       void* stream, const StepGateK gate) {
+                       void* stream, const StepGateK gate, const SceneStepK* scene = nullptr) {
     if (int rc = full_step_pin_check(robot, S, W, params, pin)) return rc;
     CPPF_ENTER(robot);
     CPPF_REQUIRE(params, "params is NULL");
@@ -925,7 +926,18 @@ int lm_full_step_gated(const cppf_robot* robot, const float* x_in, const float* 
     hipStream_t st = (hipStream_t)stream;
     const int rc = for_robot(robot, [&](auto tag) {
         using RB = typename decltype(tag)::type;
-        if (n >= 131072)
+        if (scene != nullptr) {
+            // ONE instantiation per robot, the unconstrained build: a planner steps S <= 8 trajectories, far below the row count at
+            // which the occupancy-bound build of the handle form pays.  (A handle specialised at run time takes the generic form,
+            // like every coupled step: for_robot.)
+            SceneStepK sc = *scene;
+            double r_max = 0.0;
+            for (int c = 0; c < robot->coll.ncaps; ++c) r_max = std::max(r_max, (double)robot->desc.cap_r[c]);
+            sc.tile_cull2 = cull_threshold(r_max);
+            // (dynamic LDS as for the handle form beside it: chain12's 13 capsules are 78 KB in both)
+            hipLaunchKernelGGL((full_blocks_kernel<RB, 0, true>), dim3(grid_for(n)), dim3(kBlock), robot->lds_bytes, st, robot->chain,
+                               robot->coll, prm, x_in, target, virtual_configs, work_blocks, w2next, sc);
+        } else if (n >= 131072)
             hipLaunchKernelGGL((full_blocks_kernel<RB, full_blocks_occ<RB>()>), dim3(grid_for(n)), dim3(kBlock), robot->lds_bytes, st,
                                robot->chain, robot->coll, prm, x_in, target, virtual_configs, work_blocks, w2next, gate);
         else
@@ -1391,6 +1403,24 @@ int cppf_lm_full_step(const cppf_robot* robot, const float* x_in, const float* t
                       float* x_out, void* stream) {
     return cppf_lm_full_step_pinned(robot, x_in, target, virtual_configs, S, W, params, 0, work_blocks, work_G, work_y, x_out,
                                     stream);
+}
+
+int cppf_lm_full_step_scene(const cppf_robot* robot, const float* x_in, const float* target, const float* virtual_configs, int S,
+                            int W, const cppf_full_params* params, int pin_mask, const float* box_lo, const float* box_hi,
+                            int n_obs, float* work_blocks, float* work_G, float* work_y, float* x_out, void* stream) {
+    // every argument is checked before the device is selected (CPPF_ENTER), so that the checks hold for a host-only handle too
+    CPPF_REQUIRE(robot != nullptr, "robot handle is NULL");
+    CPPF_REQUIRE(!(robot->life.load(std::memory_order_acquire) & kRobotDead), "the robot handle was destroyed");
+    CPPF_REQUIRE(params, "params is NULL");
+    CPPF_REQUIRE(pin_mask >= 0 && pin_mask <= (CPPF_PIN_FIRST | CPPF_PIN_LAST),
+                 "pin_mask must be a combination of CPPF_PIN_FIRST and CPPF_PIN_LAST");
+    CPPF_REQUIRE(n_obs >= 0 && n_obs <= CPPF_MAX_SCENE_OBSTACLES, "n_obs out of range (0 .. CPPF_MAX_SCENE_OBSTACLES)");
+    CPPF_REQUIRE(n_obs == 0 || (box_lo && box_hi), "box_lo / box_hi is NULL");
+    CPPF_REQUIRE(S >= 0 && W >= 1, "S < 0 or W < 1");
+    CPPF_REQUIRE(S == 0 || (x_in && target && work_blocks && work_G && work_y && x_out), "NULL pointer");
+    const SceneStepK scene{box_lo, box_hi, n_obs, 0.f};  // (the tile threshold: lm_full_step_gated, from the handle's radii)
+    return lm_full_step_gated(robot, x_in, target, virtual_configs, S, W, params, pin_mask, work_blocks, work_G, work_y, x_out,
+                              stream, StepGateK{nullptr, 0, 0u}, &scene);
 }
 
 }  // extern "C"

@@ -289,21 +289,75 @@ constexpr int full_blocks_occ() {
     if (RB::kStatic) return full_blocks_fits_128<RB>::value ? 4 : 3;
     return RB::D <= 6 ? 4 : 3;
 }
-template <class RB, int OCC = 0>
+// The scene form (SCENE; cppf_lm_full_step_scene): the environment rows come from ALL n_obs <= CPPF_MAX_SCENE_OBSTACLES cuboids of a
+// scene in device memory (box_lo / box_hi [n_obs, 3], as kernels_scene.h takes them) instead of the handle's <= 8 in the argument
+// segment.  Environment rows of row r: for o = 0 .. n_obs-1 ascending, c = 0 .. ncaps-1 ascending, the same cull_far / seg_box_closest /
+// point_grad / rank1 with the same operands as the loop over co.obs_lo -- a (capsule, cuboid) pair contributes only when it
+// penetrates, so a cuboid that penetrates nothing adds not even a "+ 0", and whenever a handle can hold the penetrating cuboids (in
+// ascending order) the two forms give the same block bit for bit.  In front of it the culling of scene_kernel: 64 cuboids per tile,
+// one per lane, against the wavefront's box (every capsule segment of every row of the wavefront, mask-only threshold: reach = 0), a
+// ballot, a wave-uniform loop over the survivors with their corners broadcast by v_readlane.  A culled cuboid is further than
+// r_max + 1 cm from every segment of the wavefront and cannot penetrate, so the culling changes no bit.  The tile test needs all 64
+// lanes: a lane past the last row stays, works on a copy of the last row and stores nothing (as in scene_kernel); the gate argument
+// does not exist in this form (its place in the argument list holds the scene).
+struct SceneStepK {
+    const float* box_lo;  // DEVICE [n_obs, 3] world-frame corners
+    const float* box_hi;
+    int32_t n_obs;
+    float tile_cull2;  // (r_max + 1 cm)^2 (1 + 1e-4), rounded up: wavefront box vs cuboid (cull_threshold(r_max) on the host)
+};
+template <bool SCENE>
+struct FullBlocksTail {
+    using type = StepGateK;
+};
+template <>
+struct FullBlocksTail<true> {
+    using type = SceneStepK;
+};
+
+// bit set of the lanes whose cuboid (base + lane, corners loaded into llo / lhi) may come within the tile threshold of the box
+__device__ __forceinline__ unsigned long long scene_step_tile(const SceneStepK& sc, int base, int lane, const float (&blo)[3],
+                                                              const float (&bhi)[3], float (&llo)[3], float (&lhi)[3]) {
+    const int ol = base + lane;
+    const bool have = ol < sc.n_obs;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        llo[k] = have ? sc.box_lo[(size_t)ol * 3 + k] : 0.f;
+        lhi[k] = have ? sc.box_hi[(size_t)ol * 3 + k] : 0.f;
+    }
+    float g2 = 0.f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float g = fmaxf(fmaxf(llo[k] - bhi[k], blo[k] - lhi[k]), 0.f);
+        g2 = CPPF_FMA(g, g, g2);
+    }
+    return __builtin_amdgcn_ballot_w64(have && !(g2 > sc.tile_cull2));
+}
+
+template <class RB, int OCC = 0, bool SCENE = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(OCC ? OCC : 1, OCC ? OCC : 8))) void full_blocks_kernel(const ChainK ch, const CollK co, const FullK prm,
                                                              const float* __restrict__ x,
                                                              const float* __restrict__ target,
                                                              const float* __restrict__ xv, float* __restrict__ blocks,
-                                                             float* __restrict__ w2next, const StepGateK gate) {
+                                                             float* __restrict__ w2next,
+                                                             const typename FullBlocksTail<SCENE>::type gate) {
     extern __shared__ float lds[];
     constexpr int D = RB::D;
     constexpr int NT = D * (D + 1) / 2;
     const RB rb{ch, co};
     const int tid = threadIdx.x;
-    const size_t row = (size_t)blockIdx.x * kBlock + tid;
+    const size_t row0 = (size_t)blockIdx.x * kBlock + tid;
     const size_t n = (size_t)prm.S * prm.W;
-    if (row >= n) return;
-    if (gate.ctl != nullptr && !step_open(gate, (int)(row / (size_t)prm.W))) return;  // like the tail rows: before any wavefront-wide vote
+    bool valid = true;  // (the scene form's tail lanes: false)
+    if constexpr (SCENE) {
+        // a wavefront with no row at all leaves (wave-uniform: row0 - lane is its first row)
+        if (row0 - (size_t)(tid & 63) >= n) return;
+        valid = row0 < n;
+    } else {
+        if (row0 >= n) return;
+        if (gate.ctl != nullptr && !step_open(gate, (int)(row0 / (size_t)prm.W))) return;  // like the tail rows: before any wavefront-wide vote
+    }
+    const size_t row = valid ? row0 : n - 1;
     float q[D];
     load_x<D>(x, row, q);
     unsigned long long near_self = ~0ull, near_env = ~0ull;  // wavefront-uniform
@@ -312,11 +366,35 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(OCC ? OC
         constexpr int L = T::L > 0 ? T::L : 1;
         static_assert(T::P <= 64, "pair set is a 64-bit mask");
         near_self = 0ull;
-        const bool env_bits = prm.use_env && co.nobs * T::L <= 64;
-        if (env_bits || !prm.use_env) near_env = 0ull;
-        if (prm.use_self || env_bits) {
+        // (the scene form: the bit set o * L + c cannot describe a scene -- there near_env has one bit per TILE of 64 cuboids, set
+        // where the tile test below, on the register capsules' box, leaves a cuboid for this wavefront; the general pass skips the
+        // other tiles unread and reads the surviving ones a second time, deliberately: their corners are 6 registers per tile,
+        // which cannot be kept across the capsule stage for up to 64 tiles)
+        const bool env_bits = !SCENE && prm.use_env && co.nobs * T::L <= 64;
+        bool scene_env = false;
+        if constexpr (SCENE) scene_env = prm.use_env && gate.n_obs > 0;
+        if (env_bits || !prm.use_env || (SCENE && !scene_env)) near_env = 0ull;
+        if (prm.use_self || env_bits || scene_env) {
             float R[9], p[3], wc[L][3], wh[L][3];
             capsule_fk_static<RB>(rb, q, R, p, wc, wh);
+            if constexpr (SCENE) {
+                if (scene_env) {
+                    float blo[3] = {INFINITY, INFINITY, INFINITY}, bhi[3] = {-INFINITY, -INFINITY, -INFINITY};
+#pragma unroll
+                    for (int c = 0; c < T::L; ++c) box_add_segment(wc[c], wh[c], blo, bhi);
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        blo[k] = wave_min(blo[k]);
+                        bhi[k] = wave_max(bhi[k]);
+                    }
+                    static_assert(CPPF_MAX_SCENE_OBSTACLES <= 64 * 64, "one bit of near_env per tile of 64 cuboids");
+                    near_env = 0ull;
+                    for (int base = 0; base < gate.n_obs; base += 64) {
+                        float llo[3], lhi[3];
+                        if (scene_step_tile(gate, base, tid & 63, blo, bhi, llo, lhi) != 0ull) near_env |= 1ull << (base >> 6);
+                    }
+                }
+            }
             if (prm.use_self) {
 #pragma unroll
                 for (int pi = 0; pi < T::P; ++pi) {
@@ -345,7 +423,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(OCC ? OC
             for (int k = 0; k < NT; ++k) M[k] = 0.f;
 #pragma unroll
             for (int j = 0; j < D; ++j) m[j] = 0.f;
-            full_block_store<RB>(rb, prm, row, q, x, xv, M, m, blocks, w2next);
+            if (valid) full_block_store<RB>(rb, prm, row, q, x, xv, M, m, blocks, w2next);
             return;
         }
     }
@@ -433,7 +511,56 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(OCC ? OC
             }
         }
     }
-    if (prm.use_env) {  // :685-727
+    if constexpr (SCENE) {
+        if (prm.use_env && near_env != 0ull && gate.n_obs > 0) {  // :685-727 over the scene
+            const float w = prm.a_env * prm.a_env;
+            const int lane = tid & 63;
+            // the wavefront's box: every capsule segment of every row of the wavefront (all 64 lanes are here)
+            float blo[3] = {INFINITY, INFINITY, INFINITY}, bhi[3] = {-INFINITY, -INFINITY, -INFINITY};
+            for (int c = 0; c < co.ncaps; ++c) {
+                float wc[3], wh[3];
+                lds_capsule(lds, tid, c, wc, wh);
+                box_add_segment(wc, wh, blo, bhi);
+            }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                blo[k] = wave_min(blo[k]);
+                bhi[k] = wave_max(bhi[k]);
+            }
+            for (int base = 0; base < gate.n_obs; base += 64) {
+                // (a tile the pre-screen's box test left empty holds nothing that can penetrate; the generic form: all ones)
+                if (!((near_env >> ((base >> 6) & 63)) & 1ull)) continue;
+                float llo[3], lhi[3];
+                unsigned long long live = scene_step_tile(gate, base, lane, blo, bhi, llo, lhi);
+                while (live != 0ull) {  // the survivors, cuboids ascending, for the whole wavefront
+                    const int j = __builtin_ctzll(live);
+                    live &= live - 1ull;
+                    const float lo[3] = {readlane_f(llo[0], j), readlane_f(llo[1], j), readlane_f(llo[2], j)};
+                    const float hi[3] = {readlane_f(lhi[0], j), readlane_f(lhi[1], j), readlane_f(lhi[2], j)};
+                    for (int c = 0; c < co.ncaps; ++c) {
+                        float wc[3], wh[3], cs[3], cb[3];
+                        lds_capsule(lds, tid, c, wc, wh);
+                        if (cull_far(point_box_dist2(wc, lo, hi), co.cap_cull[c])) continue;
+                        const float sd = seg_box_closest(wc, wh, lo, hi, cs, cb);
+                        const float dist = sd - co.cap_r[c];
+                        if (dist < 0.f) {
+                            float nrm[3] = {0.f, 0.f, 0.f}, g[D];
+                            if (sd > kTouch) {
+#pragma unroll
+                                for (int i = 0; i < 3; ++i) nrm[i] = (cs[i] - cb[i]) / sd;
+                            }
+#pragma unroll
+                            for (int j2 = 0; j2 < D; ++j2) g[j2] = 0.f;
+                            point_grad<RB>(rb, co.cap_link[c], nrm, cs, ax, og, 1.f, g);
+                            rank1<D>(M, m, g, w, -w * dist);
+                        }
+                    }
+                }
+            }
+        }
+        if (!valid) return;
+    }
+    if (!SCENE && prm.use_env) {  // :685-727
         const float w = prm.a_env * prm.a_env;
         for (int o = 0; o < co.nobs; ++o)
             for (int c = 0; c < co.ncaps; ++c) {

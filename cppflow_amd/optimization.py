@@ -110,18 +110,27 @@ def levenberg_marquardt_full(
     opt_state: OptimizationState,
     opt_params: OptimizationParameters,
     return_residual: bool = False,
+    scene_in_step: bool = False,
 ):
     """The coupled LM step (cppflow/optimization.py:116-144): pose / differencing / virtual-config / capsule-collision
     residuals of whole trajectories, solved as a block-tridiagonal system per trajectory on the device
     (`cppf_lm_full_step`).  Unlike the reference (`assert parallel_count == 1`, :128) any number of seeds is accepted:
-    opt_state.x is [parallel_count * W, ndof] and every trajectory is smoothed independently in the same launch."""
-    opt_problem.problem.bind_obstacles()
+    opt_state.x is [parallel_count * W, ndof] and every trajectory is smoothed independently in the same launch.
+    `scene_in_step`: the environment rows come from every cuboid of the problem's scene in device memory
+    (`cppf_lm_full_step_scene`) instead of what `bind_obstacles` hands the robot handle."""
+    scene = None
+    if scene_in_step:  # every cuboid of the scene, from device memory: the handle's own are not involved
+        sc = opt_problem.problem.scene(opt_state.x.device)
+        scene = (sc.lo, sc.hi)
+    else:
+        opt_problem.problem.bind_obstacles()
     x_new = opt_problem.robot.lm_full_step(
         opt_state.x, _unstacked_target(opt_problem), opt_params, virtual_configs=opt_params.virtual_configs,
-        pin=opt_problem.pin_mask,
+        pin=opt_problem.pin_mask, scene=scene,
     )  # fmt: skip
     if not return_residual:
         return x_new
+    assert not scene_in_step, "the dense residual / Jacobian take the handle's cuboids"
     # inspection path: the dense (J, r) the reference would have factored (the step above never forms them)
     assert opt_problem.parallel_count == 1, "the dense residual / Jacobian are defined for one trajectory (:128)"
     jacobian, residual = LmResidualFns.get_r_and_J(
@@ -148,6 +157,7 @@ def run_lm_alternating_loss(
     device_loop: bool = False,
     sync_every: Optional[int] = None,
     per_trajectory: bool = False,
+    scene_in_step: bool = False,
 ):
     """The alternating loop of cppflow/optimization.py:147-373 with its bookkeeping and termination rules.
 
@@ -164,6 +174,9 @@ def run_lm_alternating_loss(
     all following one decision; the result is the lowest-index valid trajectory (`parallel_seed_idx`), `x_opt` holds every
     trajectory's own result.
 
+    `scene_in_step` (host loop only; `run_lm_optimization` decides it): every coupled step reads the problem's whole scene
+    (`levenberg_marquardt_full(scene_in_step=True)`); nothing is bound to the robot handle for the environment.
+
     `opt_problem.pin_mask` (`run_lm_optimization(pin_first=..., pin_last=...)`): the named end waypoints of every trajectory are
     constants of the optimisation.  The coupled step takes them as boundary conditions (`cppf_lm_full_step_pinned`); the pose step
     is the unchanged kernel and its result for those rows is discarded -- here they are put back after the clamp, on the device
@@ -172,6 +185,7 @@ def run_lm_alternating_loss(
     assert on_pose_valid in ("differencing", "stop", "continue")
     assert device_loop or (sync_every is None and not per_trajectory), "sync_every / per_trajectory belong to device_loop=True"
     assert sync_every is None or (isinstance(sync_every, int) and sync_every >= 1), "sync_every must be a positive int"
+    assert not (device_loop and scene_in_step), "scene_in_step belongs to the host loop: the device loop's launches read the robot handle"
     if tmax_sec is None:
         assert (max_n_steps is not None) and (return_if_valid_after_n_steps is not None)
         assert return_if_valid_after_n_steps <= max_n_steps
@@ -205,7 +219,9 @@ def run_lm_alternating_loss(
         if pose_pos_valid and pose_rot_valid and on_pose_valid == "differencing":
             printc(f"i: {i}  ----> differencing")
             params_diff.virtual_configs = opt_state.x.clone()  # :253
-            x_new = levenberg_marquardt_full(opt_problem, opt_state, params_diff)
+            # (the keyword only where it is set: the call without it is the one callers that substitute the step function know)
+            scene_kw = {"scene_in_step": True} if scene_in_step else {}
+            x_new = levenberg_marquardt_full(opt_problem, opt_state, params_diff, **scene_kw)
             took_differencing = True
         else:
             printc(f"i: {i}  --> only pose")
@@ -357,6 +373,7 @@ def run_lm_optimization(
     pin_first: bool = False,
     pin_last: bool = False,
     scene_activation_distance_m: float = DEFAULT_SCENE_ACTIVATION_DISTANCE_M,
+    scene_in_step: bool = False,
 ) -> OptimizationResult:
     """Optimise a trajectory (or `parallel_count` seeds at once): x_seed is [parallel_count * W, ndof]
     (cppflow/optimization.py:376-426).  The target path is NOT stacked: rows index it modulo W.
@@ -369,7 +386,18 @@ def run_lm_optimization(
     distance to the result -- and the loop runs again from the seed within what is left of `tmax_sec`.  `is_valid` always speaks
     for the whole scene: the host loop evaluates every iteration against it, the device loop decides on the active set and is
     re-validated here (the trajectory it chose is the one that is checked).  `scene_selection_rounds` / `active_obstacles` of
-    the result say what happened."""
+    the result say what happened.
+    `scene_in_step=True` (host loop only): for such a problem the coupled step reads EVERY cuboid of the scene from device memory
+    (`Robot.lm_full_step(scene=...)`, `cppf_lm_full_step_scene`) -- no active set is chosen, nothing is bound to the handle for the
+    environment and nothing is re-selected (`scene_selection_rounds` = 0, `active_obstacles` = None); the per-iteration evaluation
+    is the whole scene's as before.  On a problem of at most 8 cuboids the host loop runs exactly as without the flag.  Together
+    with `device_loop=True` the flag is refused (AssertionError) whatever the problem holds: the combination is a mistake of the
+    caller's, and it is reported the same way for every problem (`Planner` refuses it at construction)."""
+    # (first of all, before anything touches the device: the device loop's gated launches read the handle, not a scene)
+    assert not (device_loop and scene_in_step), (
+        "scene_in_step=True is not combined with device_loop=True: the device loop's gated mask and step launches take their "
+        "cuboids from the robot handle"
+    )
     if SELF_COLLISIONS_IGNORED:
         warnings.warn("robot-robot are collisions will be ignored during LM optimization")
     if ENV_COLLISIONS_IGNORED:
@@ -384,6 +412,7 @@ def run_lm_optimization(
         problem, problem.constraints, x_seed, problem.target_path, verbosity, parallel_count, results_df,
         pin_mask=(_hip.PIN_FIRST if pin_first else 0) | (_hip.PIN_LAST if pin_last else 0),
     )  # fmt: skip
+    scene_in_step = bool(scene_in_step) and problem.uses_scene
 
     def run(tmax) -> OptimizationResult:
         opt_state = OptimizationState(x_seed.clone(), 0, time())
@@ -391,10 +420,12 @@ def run_lm_optimization(
             opt_problem, opt_state, ALT_LOSS_V2_1_DIFF, ALT_LOSS_V2_1_POSE, return_residuals=False, verbosity=verbosity,
             tmax_sec=tmax, max_n_steps=max_n_steps, return_if_valid_after_n_steps=return_if_valid_after_n_steps,
             convergence_threshold=convergence_threshold, save_images=False, results_df=results_df, on_pose_valid=on_pose_valid,
-            device_loop=device_loop, sync_every=sync_every, per_trajectory=per_trajectory,
+            device_loop=device_loop, sync_every=sync_every, per_trajectory=per_trajectory, scene_in_step=scene_in_step,
         )  # fmt: skip
 
     if not problem.uses_scene:
+        return run(tmax_sec)
+    if scene_in_step:  # (is_valid: the host loop evaluated every iteration against the whole scene)
         return run(tmax_sec)
 
     W, t_start = problem.n_timesteps, time()

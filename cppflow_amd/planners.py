@@ -149,7 +149,7 @@ class TrackingSeedProvider:
 class Planner:
     def __init__(self, settings: PlannerSettings, robot, seed_provider: Optional[SeedProvider] = None, process_group=None,
                  candidate_lm_steps: int = 0, device_optimizer: bool = False, n_search_paths: int = 1,
-                 search_path_separation_rad: float = 0.5, pin_initial_configuration: bool = False):
+                 search_path_separation_rad: float = 0.5, pin_initial_configuration: bool = False, scene_optimizer: bool = False):
         """`process_group` / `candidate_lm_steps`: the sharded candidate stage (module docstring); with `candidate_lm_steps` > 0 every
         (candidate, waypoint) row takes that many fused pose-only LM iterations before the masks are evaluated (one launch).
         `device_optimizer`: the LM optimiser's loop is decided on the device (`run_lm_optimization(device_loop=True)`); same plan.
@@ -159,7 +159,14 @@ class Planner:
         `pin_initial_configuration`: with `problem.initial_configuration` given, `CppFlowPlanner`'s optimiser holds waypoint 0 of
         every search path (they all start there) fixed (`run_lm_optimization(pin_first=True)`): the plan starts at the initial
         configuration bit for bit and the transition out of it is one the optimiser saw, instead of accepting any start within
-        SUCCESS_THRESHOLD_initial_q_norm_dist of it or swapping it in afterwards.  Off: the reference's behaviour."""
+        SUCCESS_THRESHOLD_initial_q_norm_dist of it or swapping it in afterwards.  Off: the reference's behaviour.
+        `scene_optimizer`: for a problem with more than 8 cuboids `CppFlowPlanner`'s optimiser steps against the whole scene
+        (`run_lm_optimization(scene_in_step=True)`) instead of an active set of 8; not together with `device_optimizer`."""
+        assert not (device_optimizer and scene_optimizer), (
+            "scene_optimizer=True is not combined with device_optimizer=True: the device loop's gated mask and step launches take "
+            "their cuboids from the robot handle"
+        )
+        self._scene_optimizer = bool(scene_optimizer)
         self._pin_initial_configuration = bool(pin_initial_configuration)
         assert int(n_search_paths) >= 1, "n_search_paths must be >= 1"
         assert float(search_path_separation_rad) >= 0.0, "search_path_separation_rad must be >= 0"
@@ -300,19 +307,21 @@ class CppFlowPlanner(Planner):
             opt = run_lm_optimization(problem, self._search_paths.reshape(n * T, -1).contiguous(),
                                       tmax_sec=self._cfg.tmax_sec - (time() - t0), verbosity=self._cfg.verbosity, parallel_count=n,
                                       per_trajectory=self._device_optimizer, device_loop=self._device_optimizer, pin_first=pin_first,
-                                      **budget)  # fmt: skip
+                                      scene_in_step=self._scene_optimizer, **budget)  # fmt: skip
             s = opt.parallel_seed_idx if 0 <= opt.parallel_seed_idx < n else 0
             x_opt = opt.x_opt.detach()[s * T : (s + 1) * T]
             debug_info["n_search_paths"], debug_info["optimized_path_index"] = n, s
         else:
             opt = run_lm_optimization(problem, search_qpath.contiguous(), tmax_sec=self._cfg.tmax_sec - (time() - t0),
                                       verbosity=self._cfg.verbosity, device_loop=self._device_optimizer, pin_first=pin_first,
-                                      **budget)  # fmt: skip
+                                      scene_in_step=self._scene_optimizer, **budget)  # fmt: skip
             x_opt = opt.x_opt.detach()
         td.optimizer = time() - t0_opt
         debug_info["n_optimization_steps"] = opt.n_steps_taken
         if problem.uses_scene:  # (more than 8 cuboids: what the optimiser's kernels were given, and how often it was chosen)
             debug_info["scene_selection_rounds"], debug_info["active_obstacles"] = opt.scene_selection_rounds, opt.active_obstacles
+            if self._scene_optimizer:
+                debug_info["scene_optimizer"] = True
         if opt.is_valid:
             if problem.initial_configuration is None or pin_first:  # (pinned: x_opt[0] IS the initial configuration)
                 return result(x_opt)

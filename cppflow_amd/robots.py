@@ -622,13 +622,17 @@ class Robot:
         return out
 
     def lm_full_step(self, x: torch.Tensor, target: torch.Tensor, opt_params, virtual_configs: Optional[torch.Tensor] = None,
-                     x_out: Optional[torch.Tensor] = None, constraints=None, pin: int = 0) -> torch.Tensor:  # fmt: skip
+                     x_out: Optional[torch.Tensor] = None, constraints=None, pin: int = 0,
+                     scene: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> torch.Tensor:  # fmt: skip
         """One coupled LM step (levenberg_marquardt_full, cppflow/optimization.py:95-144) for every trajectory in
         x [S*W, d]; target [W,7].  `opt_params` is an OptimizationParameters (e.g. ALT_LOSS_V2_1_DIFF); its "satisfied" row
         options (pose scale-down, differencing filter / scale-down: cppflow/optimization_utils.py:514-533, 562-598) are applied
         on the device, with thresholds from `constraints` (default: opt_params.constraints if present, else DEFAULT_CONSTRAINTS).
         `pin` = `_hip.PIN_FIRST | _hip.PIN_LAST`: waypoint 0 / W-1 of every trajectory is held fixed at its value in `x` (it comes
-        back bit for bit; its free neighbour feels it through the differencing row).  Not combined with the "satisfied" options."""
+        back bit for bit; its free neighbour feels it through the differencing row).  Not combined with the "satisfied" options.
+        `scene` = (box_lo, box_hi), device [O, 3] world-frame corners (`cppflow_amd.scene.ObstacleScene`: `.lo`, `.hi`), O <= 4096:
+        the environment rows come from ALL of these cuboids instead of the handle's at most 8, which are then neither read nor
+        changed (`cppf_lm_full_step_scene`).  Where a handle could hold the cuboids that penetrate, the result is the same bit for bit."""
         x = self._x2d(x)
         target = _require_device_tensor(target, "target_path")
         n, W = x.shape[0], target.shape[0]
@@ -647,6 +651,19 @@ class Robot:
         y = torch.empty(n * d, dtype=torch.float32, device=dev)
         if x_out is None:
             x_out = torch.empty_like(x)
+        if scene is not None:
+            box_lo, box_hi = (_require_device_tensor(t, name) for t, name in zip(scene, ("box_lo", "box_hi")))
+            assert box_lo.dim() == 2 and box_lo.shape[1] == 3 and box_hi.shape == box_lo.shape, (tuple(box_lo.shape), tuple(box_hi.shape))
+            assert box_lo.device == dev and box_hi.device == dev, "x, box_lo and box_hi must be on one device"
+            O = int(box_lo.shape[0])
+            _hip.check(
+                _hip.lib().cppf_lm_full_step_scene(
+                    self._handle(dev), x.data_ptr(), target.data_ptr(), xv.data_ptr() if xv is not None else None, n // W, W,
+                    ctypes.byref(prm), int(pin), box_lo.data_ptr() if O else None, box_hi.data_ptr() if O else None, O,
+                    blocks.data_ptr(), G.data_ptr(), y.data_ptr(), x_out.data_ptr(), _stream_ptr(dev),
+                )  # fmt: skip
+            )
+            return x_out
         _hip.check(
             _hip.lib().cppf_lm_full_step_pinned(
                 self._handle(dev), x.data_ptr(), target.data_ptr(), xv.data_ptr() if xv is not None else None, n // W, W,

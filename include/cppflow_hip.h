@@ -446,6 +446,26 @@ int cppf_lm_full_step_pinned(const cppf_robot* robot, const float* x_in, const f
                              int W, const cppf_full_params* params, int pin_mask, float* work_blocks, float* work_G,
                              float* work_y, float* x_out, void* stream);
 
+/* The same step with its environment rows taken from a whole obstacle scene: n_obs <= CPPF_MAX_SCENE_OBSTACLES axis-aligned cuboids
+ * in DEVICE memory (box_lo / box_hi [n_obs, 3], world-frame corners formed as for cppf_scene_env_collisions), instead of the handle's
+ * <= CPPF_MAX_OBSTACLES; the handle's own cuboids are neither read nor changed.  Environment rows of a row r: for o = 0 .. n_obs-1
+ * ascending and every capsule c ascending, the (capsule, cuboid) pair contributes its row -- the same closest points, distance,
+ * gradient and accumulation as in cppf_lm_full_step_pinned -- exactly when it penetrates (distance < 0); a pair that does not
+ * contributes nothing.  Hence the contract: whenever the cuboids that penetrate some row of the call can be bound to a handle (at
+ * most 8 of them, in ascending index order), x_out equals cppf_lm_full_step_pinned on that handle BIT FOR BIT, whatever else the
+ * scene holds; and trajectories whose penetrating cuboids differ each equal the step with their own set bound.  In front of the
+ * exact test the kernel culls 64 cuboids at a time against the bounding box of a wavefront's capsules (threshold: largest capsule
+ * radius + 1 cm); a culled cuboid cannot penetrate, so the culling changes no bit, and two runs are bit-identical.
+ * Workspaces, aliasing rule, pin_mask and the CPPF_ERR_UNSUPPORTED cases are those of cppf_lm_full_step_pinned.  Asynchronous on
+ * `stream`, no host synchronisation, capturable in a graph.  n_obs = 0 is valid (the step on a handle without obstacles), and so is
+ * params->use_env_collisions = 0 (the scene is then not read).  A handle specialised at run time (cppf_robot_specialize) is served
+ * by the generic kernels, as for every coupled step: same bits.  CPPF_ERR_INVALID, before a device is selected: a NULL / destroyed
+ * handle, NULL pointers (box_lo / box_hi may be NULL only with n_obs = 0), n_obs out of range, a pin_mask outside
+ * CPPF_PIN_FIRST | CPPF_PIN_LAST.  The device-side optimiser loop (cppf_lm_optimize_enqueue) does not take a scene. */
+int cppf_lm_full_step_scene(const cppf_robot* robot, const float* x_in, const float* target, const float* virtual_configs, int S,
+                            int W, const cppf_full_params* params, int pin_mask, const float* box_lo, const float* box_hi,
+                            int n_obs, float* work_blocks, float* work_G, float* work_y, float* x_out, void* stream);
+
 /* ---- the alternating LM optimiser loop on the device (run_lm_alternating_loss, cppflow/optimization.py:147-373) -------------------
  * cppf_lm_optimize_enqueue() enqueues `n_iterations` iterations of  { pose step | coupled step ; clamp ; capsule masks ; plan
  * metrics ; decide }  on `stream` and returns without synchronising.  Which step an iteration takes, whether the trajectory is
