@@ -184,6 +184,8 @@ class LmOutputs(ctypes.Structure):
 
 MAX_BATCH = 16  # CPPF_MAX_BATCH
 MAX_SCENE_OBSTACLES = 4096  # CPPF_MAX_SCENE_OBSTACLES
+MOTION_MAX_LEVEL = 6  # CPPF_MOTION_MAX_LEVEL
+MOTION_CERTIFIED, MOTION_HIT = 1, 2  # cppf_motion_clearance's status bits (CPPF_MOTION_*)
 
 
 class LmBatchItem(ctypes.Structure):
@@ -225,6 +227,13 @@ SIGNATURES = {
         ctypes.c_int,
         [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp],
     ),
+    "cppf_motion_workspace_bytes": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
+    "cppf_motion_clearance": (
+        ctypes.c_int,
+        [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_float, _vp, _vp, _vp, _vp, _vp,
+         ctypes.c_size_t, _vp],
+    ),
+    "cppf_motion_rho": (ctypes.c_int, [_vp, ctypes.POINTER(_f)]),
     "cppf_self_collision_distances": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _vp]),
     "cppf_env_collision_distances": (
         ctypes.c_int,

@@ -63,6 +63,7 @@ constexpr int kBlock = CPPF_BLOCK;
 #include "kernels_quad.h"
 #include "kernels_eval.h"
 #include "kernels_scene.h"  // (ahead of the coupled step: its scene form shares the box / broadcast helpers)
+#include "kernels_motion.h"
 #include "kernels_coupled.h"
 #include "kernels_dp.h"
 #include "kernels_optloop.h"
@@ -102,7 +103,9 @@ struct cppf_robot {
     int cu_count;      // compute units of `device` (0 for the host-only handle): what a resident launch's grid is held against
     int static_id;     // index into robots_gen.h when the description equals a generated table, else -1
     size_t lds_bytes;  // generic path only: capsule end points, 6 floats per capsule per lane
-    void* d_quad;      // device: QuadPairRec[CPPF_MAX_PAIRS] then QuadCapRec[CPPF_MAX_CAPSULES] (quad shape's striped collision stage)
+    void* d_quad;      // device: QuadPairRec[CPPF_MAX_PAIRS] then QuadCapRec[CPPF_MAX_CAPSULES] (quad shape's striped collision stage),
+                       // then the travel-bound table rho[CPPF_MAX_DOF][CPPF_MAX_CAPSULES] of cppf_motion_clearance
+    float rho[CPPF_MAX_DOF][CPPF_MAX_CAPSULES];  // host copy of that table (motion_rho_table)
     RtcModule* rtc;    // kernels compiled for this description by cppf_robot_specialize (hipRTC), else NULL
     // Test / tuning switches of THIS handle (cppf_debug_set, include/cppflow_hip_debug.h): no process-wide dispatch state, two
     // handles on two threads can hold different settings.  Atomics: a setter may race with a launch on another thread.
@@ -185,6 +188,38 @@ float cull_threshold(double reach) {
     float f = (float)y;
     if ((double)f < y) f = std::nextafterf(f, INFINITY);
     return f;
+}
+
+// Travel bounds of cppf_motion_clearance (kernels_motion.h): rho[j][c] >= the distance of any point of capsule c from the axis of
+// revolute joint j <= cap_link[c] -- the translations of the fixed transforms between joint j and the capsule's link, the largest
+// excursion of every prismatic joint in between, and the capsule's own extent from its link's origin; 1 for a prismatic joint
+// j <= cap_link[c] (a point moves as far as the joint does); 0 for a joint behind the link.  fp64, rounded UP to fp32.
+constexpr int kQuadTableRecs = CPPF_MAX_PAIRS + CPPF_MAX_CAPSULES;  // uint4 records of d_quad in front of the rho table
+float round_up_f32(double y) {
+    float f = (float)y;
+    if ((double)f < y) f = std::nextafterf(f, INFINITY);
+    return f;
+}
+void motion_rho_table(const cppf_robot_desc& d, float (&rho)[CPPF_MAX_DOF][CPPF_MAX_CAPSULES]) {
+    const auto norm3 = [](const float* v) { return std::sqrt((double)v[0] * v[0] + (double)v[1] * v[1] + (double)v[2] * v[2]); };
+    for (int j = 0; j < CPPF_MAX_DOF; ++j)
+        for (int c = 0; c < CPPF_MAX_CAPSULES; ++c) rho[j][c] = 0.f;
+    for (int c = 0; c < d.n_capsules; ++c) {
+        const int l = d.cap_link[c];
+        const double tail = std::max(norm3(d.cap_p0[c]), norm3(d.cap_p1[c])) + (double)d.cap_r[c];
+        for (int j = 0; j <= l; ++j) {
+            if (d.jtype[j] == CPPF_JOINT_PRISMATIC) {
+                rho[j][c] = 1.f;
+                continue;
+            }
+            double sum = tail;
+            for (int i = j + 1; i <= l; ++i) {
+                sum += norm3(&d.F[i][9]);
+                if (d.jtype[i] == CPPF_JOINT_PRISMATIC) sum += std::max(std::fabs((double)d.lo[i]), std::fabs((double)d.hi[i]));
+            }
+            rho[j][c] = round_up_f32(sum);
+        }
+    }
 }
 
 // does a description equal a generated compile-time table exactly?
@@ -431,9 +466,12 @@ int cppf_robot_create(const cppf_robot_desc* desc, int device, cppf_robot** out)
     if (fused_static_block() != kBlock) rb->static_id = -1;  // (the two translation units were built for different workgroup sizes)
     rb->rtc = nullptr;
     rb->d_quad = nullptr;
-    // device tables of the quad shape (static per robot: pair list, thresholds)
+    motion_rho_table(*desc, rb->rho);
+    // device tables of the quad shape (static per robot: pair list, thresholds) and, behind them, the travel bounds
     if (device != kNoDevice) {
-        std::vector<uint4> host(CPPF_MAX_PAIRS + CPPF_MAX_CAPSULES, uint4{0, 0, 0, 0});
+        static_assert(sizeof(rb->rho) % sizeof(uint4) == 0, "the rho table is a whole number of uint4 records");
+        std::vector<uint4> host(kQuadTableRecs + sizeof(rb->rho) / sizeof(uint4), uint4{0, 0, 0, 0});
+        std::memcpy(&host[kQuadTableRecs], rb->rho, sizeof(rb->rho));
         for (int p = 0; p < co.npairs; ++p) {
             QuadPairRec r{co.pair_a[p], co.pair_b[p], co.pair_thr[p], co.pair_cull[p]};
             std::memcpy(&host[p], &r, sizeof r);
@@ -459,7 +497,7 @@ int cppf_robot_create(const cppf_robot_desc* desc, int device, cppf_robot** out)
 
 namespace {
 void robot_free(cppf_robot* robot) {
-    {
+    if (robot->device != kNoDevice) {  // (a host-only handle owns nothing on a device, and selecting "its" device would leave an error behind)
         DeviceGuard guard(robot->device);
         if (robot->d_quad) (void)hipFree(robot->d_quad);
         if (robot->rtc) {
@@ -1851,6 +1889,108 @@ int cppf_scene_env_collisions(const cppf_robot* robot, const float* q, int S, in
     const size_t items = std::max(n, obs_min ? (size_t)n_obs : (size_t)0);
     hipLaunchKernelGGL(scene_finish_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, sc.row_key, obs_key, (int)n, n_obs,
                        want_min ? 1 : 0, env_mask, min_env, nearest_obs, obs_min);
+    return check_launch();
+}
+
+// ---- motion between the waypoints (kernels_motion.h) ------------------------------------------------------------------------------
+int cppf_motion_rho(const cppf_robot* robot, float* rho) {
+    CPPF_REQUIRE(robot != nullptr, "robot handle is NULL");
+    CPPF_REQUIRE(!(robot->life.load(std::memory_order_acquire) & kRobotDead), "the robot handle was destroyed");
+    CPPF_REQUIRE(rho, "rho is NULL");
+    std::memcpy(rho, robot->rho, sizeof(robot->rho));
+    return CPPF_OK;
+}
+
+int cppf_motion_workspace_bytes(int S, int W, size_t* bytes) {
+    CPPF_REQUIRE(bytes, "bytes is NULL");
+    CPPF_REQUIRE(S >= 0, "S < 0");
+    CPPF_REQUIRE(W >= 2, "W < 2: a motion needs two waypoints");
+    // three 32-bit words per transition (kernels_motion.h); never 0, so that "workspace is NULL" stays a refusal
+    *bytes = ((size_t)S * (size_t)(W - 1) * 3 * sizeof(uint32_t) + 15) / 16 * 16 + 16;
+    return CPPF_OK;
+}
+
+int cppf_motion_clearance(const cppf_robot* robot, const float* q, int S, int W, int level, const float* box_lo, const float* box_hi,
+                          int n_obs, float reach_m, uint8_t* status, float* min_clear, int32_t* hit_node, float* nodes, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+    // every argument is checked before the device is selected (CPPF_ENTER), so that the checks hold for a host-only handle too
+    CPPF_REQUIRE(robot != nullptr, "robot handle is NULL");
+    CPPF_REQUIRE(!(robot->life.load(std::memory_order_acquire) & kRobotDead), "the robot handle was destroyed");
+    CPPF_REQUIRE(S >= 0, "S < 0");
+    CPPF_REQUIRE(W >= 2, "W < 2: a motion needs two waypoints");
+    CPPF_REQUIRE(level >= 0 && level <= CPPF_MOTION_MAX_LEVEL, "level out of range (0 .. CPPF_MOTION_MAX_LEVEL)");
+    const size_t n_nodes = ((size_t)(W - 1) << level) + 1;  // per path
+    CPPF_REQUIRE((size_t)S * (n_nodes + 64) <= 0x7fffffffu, "S * ((W-1) * 2^level + 1) exceeds 2^31-1 nodes");
+    CPPF_REQUIRE(n_obs >= 0 && n_obs <= CPPF_MAX_SCENE_OBSTACLES, "n_obs out of range (0 .. CPPF_MAX_SCENE_OBSTACLES)");
+    CPPF_REQUIRE(reach_m >= 0.f, "reach_m must be in [0, +inf] (not NaN, not negative)");
+    CPPF_REQUIRE(S == 0 || (q && status), "q / status is NULL");
+    CPPF_REQUIRE(n_obs == 0 || (box_lo && box_hi), "box_lo / box_hi is NULL");
+    CPPF_REQUIRE(workspace, "workspace is NULL");
+    CPPF_REQUIRE(((uintptr_t)workspace & 15u) == 0, "workspace must be 16-byte aligned");
+    size_t need = 0;
+    if (int rc = cppf_motion_workspace_bytes(S, W, &need)) return rc;
+    CPPF_REQUIRE(workspace_bytes >= need, "workspace is smaller than cppf_motion_workspace_bytes(S, W)");
+    const int d = robot->desc.ndof;
+    if (d < 3) return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: kernels are built for ndof in 3..12");
+    const bool table = use_table(robot);  // (a handle specialised at run time takes the generic form: same bits)
+    const size_t lds = table ? 0 : robot->lds_bytes;
+    if (lds > (size_t)160 * 1024 - 1024)
+        return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: the generic motion kernel cannot stage this many capsules");
+    CPPF_ENTER(robot);
+    hipStream_t st = (hipStream_t)stream;
+    if (S == 0) return CPPF_OK;
+    CPPF_REQUIRE(robot->d_quad != nullptr, "the handle has no device tables");
+
+    const size_t n_tr = (size_t)S * (size_t)(W - 1);
+    MotionK mk;
+    mk.box_lo = box_lo;
+    mk.box_hi = box_hi;
+    mk.rho = reinterpret_cast<const float*>(static_cast<const uint4*>(robot->d_quad) + kQuadTableRecs);
+    mk.fail = static_cast<uint32_t*>(workspace);
+    mk.clear_key = mk.fail + n_tr;
+    mk.hit = reinterpret_cast<int32_t*>(mk.clear_key + n_tr);
+    mk.nodes = nodes;
+    mk.S = S, mk.W = W, mk.level = level;
+    mk.n_nodes = (int)n_nodes;
+    mk.waves_per_path = (int)((n_nodes - 1 + 62) / 63);
+    mk.n_obs = n_obs;
+    mk.inv_m = 1.f / (float)(1 << level);
+    mk.reach = reach_m;
+    double r_max = 0.0;
+    for (int c = 0; c < CPPF_MAX_CAPSULES; ++c) mk.cull2[c] = 0.f;
+    for (int c = 0; c < robot->coll.ncaps; ++c) {
+        r_max = std::max(r_max, (double)robot->desc.cap_r[c]);
+        mk.cull2[c] = cull_threshold(cap_half_length(robot->desc, c) + (double)robot->desc.cap_r[c] + (double)reach_m);
+    }
+    mk.tile_cull2 = cull_threshold(r_max + (double)reach_m);
+    // chunks of cuboids over grid.y, as cppf_scene_env_collisions cuts them (the result does not depend on the cut)
+    const size_t waves = (size_t)S * (size_t)mk.waves_per_path;
+    const unsigned wave_blocks = (unsigned)((waves + kBlock / 64 - 1) / (kBlock / 64));
+    const int groups = (n_obs + 7) / 8;
+    int n_chunks = 1;
+    mk.chunk = 64;
+    if (groups > 0) {
+        const unsigned want_blocks = 4u * (unsigned)(robot->cu_count > 0 ? robot->cu_count : 256);
+        n_chunks = (int)std::min<unsigned>((unsigned)groups, std::max(1u, (want_blocks + wave_blocks - 1) / wave_blocks));
+        const int groups_per_chunk = (groups + n_chunks - 1) / n_chunks;
+        n_chunks = (groups + groups_per_chunk - 1) / groups_per_chunk;
+        mk.chunk = groups_per_chunk * 8;
+    }
+
+    const unsigned tr_blocks = (unsigned)((n_tr + 255) / 256);
+    hipLaunchKernelGGL(motion_init_kernel, dim3(tr_blocks), dim3(256), 0, st, mk.fail, mk.clear_key, mk.hit, n_tr);
+    const int rc = for_robot(robot, [&](auto tag) {
+        using RB = typename decltype(tag)::type;
+        const auto kernel = &motion_kernel<RB>;
+        if (lds > (size_t)64 * 1024)
+            CPPF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(kernel, dim3(wave_blocks, (unsigned)n_chunks), dim3(kBlock), lds, st, robot->chain, robot->coll, mk, q);
+        return CPPF_OK;
+    });
+    if (rc) return rc;
+    if (int rc2 = check_launch()) return rc2;
+    hipLaunchKernelGGL(motion_finish_kernel, dim3(tr_blocks), dim3(256), 0, st, mk.fail, mk.clear_key, mk.hit, n_tr, status, min_clear,
+                       hit_node);
     return check_launch();
 }
 

@@ -297,6 +297,32 @@ class PlanNp:
 
 
 @dataclass
+class MotionClearance:
+    """`Problem.motion_clearance`: the verdict on the MOTION between consecutive waypoints of k paths, all [k, T-1] on the device."""
+
+    certified: torch.Tensor  # bool: no contact anywhere on the straight joint-space move (adaptive-clearance certificate)
+    hit: torch.Tensor  # bool: one of the tested configurations penetrates
+    min_clear: torch.Tensor  # float32: the smallest clearance among the tested configurations (+inf: nothing within reach)
+    hit_node: torch.Tensor  # int32: the lowest penetrating node of the transition (0 .. 2^level), else -1
+    level: int
+    reach_m: float
+
+    @property
+    def undecided(self) -> torch.Tensor:
+        return ~(self.certified | self.hit)
+
+    @property
+    def all_certified(self) -> torch.Tensor:
+        """bool [k]: every transition of the path is certified"""
+        return self.certified.all(dim=1)
+
+    @property
+    def any_hit(self) -> torch.Tensor:
+        """bool [k]: some transition of the path is hit"""
+        return self.hit.any(dim=1)
+
+
+@dataclass
 class PlannerResult:
     plan: Plan
     timing: TimingData
@@ -401,6 +427,18 @@ class Problem:
         """`Robot.scene_env_collisions` of q [k, T, d] (or [n, d]) against ALL of this problem's cuboids."""
         sc = self.scene(q.device)
         return self.robot.scene_env_collisions(q, sc.lo, sc.hi, reach=reach_m, want=want)
+
+    def motion_clearance(self, q_paths: torch.Tensor, level: int = 6, reach_m: float = 0.05) -> "MotionClearance":
+        """Certify the motion BETWEEN the waypoints of q_paths [k, T, d] (or one path [T, d]) against the robot itself and ALL of
+        this problem's cuboids, however many (`Robot.motion_clearance` on `scene()`; a rotated cuboid raises there).  Joint values
+        are taken as stored: unwrap continuous joints first."""
+        from cppflow_amd import _hip
+
+        q = q_paths.unsqueeze(0) if q_paths.dim() == 2 else q_paths
+        sc = self.scene(q.device)
+        r = self.robot.motion_clearance(q, sc.lo, sc.hi, level=level, reach=reach_m)
+        return MotionClearance(certified=(r["status"] & _hip.MOTION_CERTIFIED) != 0, hit=(r["status"] & _hip.MOTION_HIT) != 0,
+                               min_clear=r["min_clear"], hit_node=r["hit_node"], level=int(level), reach_m=float(reach_m))  # fmt: skip
 
     def choose_active_obstacles(self, q: torch.Tensor, reach_m: float, first=None) -> List[int]:
         """Pick the <= 8 cuboids the handle's kernels get from the configurations q: those that come closest to any row of q

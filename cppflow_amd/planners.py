@@ -51,6 +51,15 @@ def add_search_path_mjac(debug_info: Dict, problem: Problem, qpath_search: torch
     debug_info["search_path_min_dist_to_jlim_deg"] = min(float(torch.rad2deg(rest.min())), 10000) if rest.numel() else 10000
 
 
+def add_motion_certificate(debug_info: Dict, problem: Problem, qpath: torch.Tensor, level: int) -> None:
+    """`Problem.motion_clearance` of the path [T, d] about to be returned -> debug_info: is every transition certified collision-free,
+    and which transitions are hit / left undecided (indices t: the move from waypoint t to t + 1)."""
+    mc = problem.motion_clearance(qpath.detach().contiguous(), level=level)
+    debug_info["motion_certified"] = bool(mc.all_certified[0])
+    debug_info["motion_hit_transitions"] = torch.nonzero(mc.hit[0]).flatten().tolist()
+    debug_info["motion_undecided_transitions"] = torch.nonzero(mc.undecided[0]).flatten().tolist()
+
+
 class LmIkSeedProvider:
     """k candidate joint-space paths for a problem by numerical IK (stand-in for IKFlow, see module docstring)."""
 
@@ -149,7 +158,8 @@ class TrackingSeedProvider:
 class Planner:
     def __init__(self, settings: PlannerSettings, robot, seed_provider: Optional[SeedProvider] = None, process_group=None,
                  candidate_lm_steps: int = 0, device_optimizer: bool = False, n_search_paths: int = 1,
-                 search_path_separation_rad: float = 0.5, pin_initial_configuration: bool = False, scene_optimizer: bool = False):
+                 search_path_separation_rad: float = 0.5, pin_initial_configuration: bool = False, scene_optimizer: bool = False,
+                 certify_motion_level: Optional[int] = None):
         """`process_group` / `candidate_lm_steps`: the sharded candidate stage (module docstring); with `candidate_lm_steps` > 0 every
         (candidate, waypoint) row takes that many fused pose-only LM iterations before the masks are evaluated (one launch).
         `device_optimizer`: the LM optimiser's loop is decided on the device (`run_lm_optimization(device_loop=True)`); same plan.
@@ -161,7 +171,12 @@ class Planner:
         configuration bit for bit and the transition out of it is one the optimiser saw, instead of accepting any start within
         SUCCESS_THRESHOLD_initial_q_norm_dist of it or swapping it in afterwards.  Off: the reference's behaviour.
         `scene_optimizer`: for a problem with more than 8 cuboids `CppFlowPlanner`'s optimiser steps against the whole scene
-        (`run_lm_optimization(scene_in_step=True)`) instead of an active set of 8; not together with `device_optimizer`."""
+        (`run_lm_optimization(scene_in_step=True)`) instead of an active set of 8; not together with `device_optimizer`.
+        `certify_motion_level` (0 .. 6; default None = off): `CppFlowPlanner` checks the MOTION between the waypoints of the plan
+        it returns once (`Problem.motion_clearance` at 2^level intervals per transition) and reports `motion_certified`,
+        `motion_hit_transitions` and `motion_undecided_transitions` in `debug_info`.  The plan and `Plan.is_valid` are unchanged."""
+        assert certify_motion_level is None or 0 <= int(certify_motion_level) <= 6, "certify_motion_level must be None or 0 .. 6"
+        self._certify_motion_level = None if certify_motion_level is None else int(certify_motion_level)
         assert not (device_optimizer and scene_optimizer), (
             "scene_optimizer=True is not combined with device_optimizer=True: the device loop's gated mask and step launches take "
             "their cuboids from the robot handle"
@@ -281,6 +296,8 @@ class CppFlowPlanner(Planner):
             return time() - t0 > self._cfg.tmax_sec
 
         def result(qpath) -> PlannerResult:
+            if self._certify_motion_level is not None:
+                add_motion_certificate(debug_info, problem, qpath, self._certify_motion_level)
             return PlannerResult(
                 plan_from_qpath(qpath, problem),
                 TimingData(time() - t0, td.ikflow, td.coll_checking, td.batch_opt, td.dp_search, td.optimizer), [], [],

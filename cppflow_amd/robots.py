@@ -543,6 +543,63 @@ class Robot:
         res["env_mask"] = res["env_mask"].view(torch.bool)
         return res
 
+    def motion_travel_table(self) -> np.ndarray:
+        """rho [d, n_capsules] fp32: the travel bounds `motion_clearance` certifies with (`cppf_motion_rho`; include/cppflow_hip.h).
+        Host only: needs no device."""
+        rho = np.zeros((_hip.MAX_DOF, _hip.MAX_CAPSULES), dtype=np.float32)
+        if self._handles:  # (any handle of this robot holds the same table)
+            _hip.check(_hip.lib().cppf_motion_rho(next(iter(self._handles.values())), _hip.fptr(rho)))
+            return rho[: self.ndof, : self.n_capsules].copy()
+        out = ctypes.c_void_p()
+        _hip.check(_hip.lib().cppf_robot_create(ctypes.byref(self._desc), -12345, ctypes.byref(out)))  # (a host-only handle)
+        try:
+            _hip.check(_hip.lib().cppf_motion_rho(out, _hip.fptr(rho)))
+        finally:
+            _hip.lib().cppf_robot_destroy(out)
+        return rho[: self.ndof, : self.n_capsules].copy()
+
+    def motion_clearance(self, q: torch.Tensor, box_lo: torch.Tensor, box_hi: torch.Tensor, level: int = 6, reach: float = 0.05,
+                         want: Sequence[str] = ("status", "min_clear", "hit_node")) -> Dict[str, torch.Tensor]:
+        """The motion between the waypoints of q [S, W, d] (W >= 2; straight joint-space lines in the stored values, no wrapping)
+        against the self pairs and the O <= 4096 axis-aligned cuboids box_lo / box_hi [O, 3] (device, world-frame corners; O = 0: self
+        only), by the adaptive-clearance test on 2^level intervals per transition (`cppf_motion_clearance`, csrc/kernels_motion.h).
+        status (uint8 [S, W-1], always returned): bit 0 certified collision-free, bit 1 hit (a node penetrates), neither: undecided.
+        min_clear (float [S, W-1]): the smallest node clearance (cuboids beyond `reach` do not count); hit_node (int32 [S, W-1]):
+        the lowest penetrating node, else -1; nodes (float [S, W-1, 2^level + 1, d], only when asked for): the configurations tested."""
+        q = _require_device_tensor(q, "q")
+        assert q.dim() == 3 and q.shape[2] == self.ndof, f"q must be [k, ntimesteps, {self.ndof}], is {tuple(q.shape)}"
+        S, W, _ = q.shape
+        dev = q.device
+        box_lo, box_hi = _require_device_tensor(box_lo, "box_lo"), _require_device_tensor(box_hi, "box_hi")
+        assert box_lo.dim() == 2 and box_lo.shape[1] == 3 and box_hi.shape == box_lo.shape, (tuple(box_lo.shape), tuple(box_hi.shape))
+        assert box_lo.device == dev and box_hi.device == dev, "q, box_lo and box_hi must be on one device"
+        O = int(box_lo.shape[0])
+        want = tuple(want)
+        assert set(want) <= {"status", "min_clear", "hit_node", "nodes"}, want
+        level = int(level)
+        assert 0 <= level <= _hip.MOTION_MAX_LEVEL and W >= 2, (level, W)
+        res: Dict[str, torch.Tensor] = {"status": torch.empty((S, W - 1), dtype=torch.uint8, device=dev)}
+        if "min_clear" in want:
+            res["min_clear"] = torch.empty((S, W - 1), dtype=torch.float32, device=dev)
+        if "hit_node" in want:
+            res["hit_node"] = torch.empty((S, W - 1), dtype=torch.int32, device=dev)
+        if "nodes" in want:
+            res["nodes"] = torch.empty((S, W - 1, (1 << level) + 1, self.ndof), dtype=torch.float32, device=dev)
+        nbytes = ctypes.c_size_t()
+        _hip.check(_hip.lib().cppf_motion_workspace_bytes(S, W, ctypes.byref(nbytes)))
+        work = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+
+        def ptr(k):
+            return res[k].data_ptr() if k in res else None
+
+        _hip.check(
+            _hip.lib().cppf_motion_clearance(
+                self._handle(dev), q.data_ptr(), S, W, level, box_lo.data_ptr(), box_hi.data_ptr(), O, float(reach), ptr("status"),
+                ptr("min_clear"), ptr("hit_node"), ptr("nodes"), work.data_ptr(), nbytes.value, _stream_ptr(dev),
+            )  # fmt: skip
+        )
+        return res
+
     def pose_error_metrics(self, x: torch.Tensor, target: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """(positional error [n] in metres, rotational error [n] in radians); target [W,7], n % W == 0."""
         x = self._x2d(x)

@@ -279,6 +279,48 @@ int cppf_scene_env_collisions(const cppf_robot* robot, const float* q, int S, in
                               float reach_m, uint8_t* env_mask, float* min_env, int32_t* nearest_obs, float* obs_min, void* workspace,
                               size_t workspace_bytes, void* stream);
 
+/* The MOTION between the waypoints of q [S, W, d] (W >= 2), certified collision-free or not: the adaptive-clearance test (Schwarzer,
+ * Saha, Latombe) on M = 2^level equal intervals per transition, level in 0 .. CPPF_MOTION_MAX_LEVEL, against the robot's self pairs and
+ * a scene box_lo / box_hi [n_obs, 3] exactly as cppf_scene_env_collisions takes it (DEVICE memory, 0 <= n_obs <=
+ * CPPF_MAX_SCENE_OBSTACLES; the handle's own cuboids are neither read nor changed; n_obs = 0: self only).  The reference has no
+ * counterpart: everything it calls collision-free is decided at the waypoints (cppflow/collision_detection.py:27-69).
+ *   Nodes.  Transition t of path s goes from a = q[s,t] to b = q[s,t+1] on the straight line in the STORED joint values -- there is no
+ *   wrapping: a caller with continuous joints unwraps first.  Node 0 is a itself, node M is b itself, node i in between is
+ *   fmaf(i / M, b - a, a) per joint (the subtraction in fp32; i / M is exact).  `nodes` [S, W-1, M+1, d] (may be NULL) returns them.
+ *   Clearances at a node.  For a self pair: the value cppf_self_collision_distances gives.  For (capsule c, cuboid o):
+ *   min(sqrt_rn(seg_box_dist2) - cap_r[c], reach_m), reach_m in [0, +inf]: the truncation keeps the scene kernel's culling legal and can
+ *   only make a certificate harder.
+ *   Travel bound.  A table built by cppf_robot_create in double precision and rounded UP to fp32 (cppf_motion_rho reads it):
+ *   with l = cap_link[c], for a revolute joint j <= l
+ *       rho[j][c] = sum_{i=j+1..l} |t_i| + sum_{prismatic i in (j, l]} max(|lo_i|, |hi_i|) + max(|p0_c|, |p1_c|) + r_c
+ *   (t_i the translation of F_i: the distance of any point of the capsule from joint j's origin, hence from its axis); 1 for a prismatic
+ *   joint j <= l; 0 for j > l.  Against a cuboid lambda_c = sum_j |b_j - a_j| rho[j][c]; for a self pair (c1, c2) on links l1 <= l2 only
+ *   the joints in between count, lambda_p = sum_{l1 < j <= l2} |b_j - a_j| rho[j][c2] (0 for a pair on one link); fp32, joints
+ *   ascending, one fmaf each.  One interval's bound is lambda / M.
+ *   Verdict per transition, status [S, W-1]:
+ *     CPPF_MOTION_CERTIFIED  every interval (i, i+1), every self pair and every (capsule, cuboid) has
+ *                            (clear_i + clear_{i+1}) - lambda / M > 1e-6 (the micrometre covers the fp32 accumulation of lambda), both
+ *                            waypoints lie inside the joint limits (outside them the prismatic term is no bound) and no node is hit;
+ *     CPPF_MOTION_HIT        some node has a clearance < 0;
+ *     neither bit            undecided.  The two bits are never set together.
+ *   min_clear [S, W-1] (may be NULL): the minimum over the transition's nodes of min(min_self, min_env) as cppf_collision_masks and
+ *   cppf_scene_env_collisions (at the same reach_m: +inf beyond it) report them for the node, bit for bit.  hit_node [S, W-1] (may be
+ *   NULL): the lowest node index with a negative clearance, else -1.
+ * workspace: cppf_motion_workspace_bytes(S, W) bytes, 16-byte aligned, device; scratch on return.  Three launches on `stream`,
+ * asynchronous, no host synchronisation, capturable in a graph; no output depends on the order in which anything arrives.
+ * CPPF_ERR_INVALID, before the device is selected: a NULL / destroyed handle, NULL q / status / corners, level out of range, W < 2,
+ * n_obs out of range, a NaN or negative reach_m, a short or misaligned workspace.  A handle specialised at run time is served by the
+ * generic kernel. */
+#define CPPF_MOTION_MAX_LEVEL 6
+#define CPPF_MOTION_CERTIFIED 1
+#define CPPF_MOTION_HIT 2
+int cppf_motion_workspace_bytes(int S, int W, size_t* bytes);
+int cppf_motion_clearance(const cppf_robot* robot, const float* q, int S, int W, int level, const float* box_lo, const float* box_hi,
+                          int n_obs, float reach_m, uint8_t* status, float* min_clear, int32_t* hit_node, float* nodes, void* workspace,
+                          size_t workspace_bytes, void* stream);
+/* the travel-bound table of the handle, HOST rho[CPPF_MAX_DOF][CPPF_MAX_CAPSULES] (needs no device) */
+int cppf_motion_rho(const cppf_robot* robot, float* rho);
+
 /* Robot.self_collision_distances(x) -> [n, n_pairs] (call site cppflow/collision_detection.py:65) */
 int cppf_self_collision_distances(const cppf_robot* robot, const float* x, int n, float* dists, void* stream);
 
