@@ -412,12 +412,17 @@ __device__ __forceinline__ float seg_seg_closest2(const float (&C1)[3], const fl
     const float c = dot3(H1[0], H1[1], H1[2], rr[0], rr[1], rr[2]);
     const float f = dot3(H2[0], H2[1], H2[2], rr[0], rr[1], rr[2]);
     const float denom = CPPF_FMA(-b, b, a * e);
-    float s = clamp11(CPPF_FMA(b, f, -(c * e)) * rcp_rn_pos(denom));  // parallel segments (denom < 2^-100): s = 0, the centre
+    // exactly parallel segments with a length (denom < 2^-100): s = 0, the first segment's centre, and t follows from it
+    float s = clamp11(CPPF_FMA(b, f, -(c * e)) * rcp_rn_pos(denom));
     float t = CPPF_FMA(b, s, f) * ie;
     // branch-free form of { t < -1: t = -1, s = clamp((-b - c) / a) ; t > 1: t = 1, s = clamp((b - c) / a) } -- lanes of a wave
     // disagree on these cases all the time, so both candidates are always computed and selected
     const float s_lo = clamp11(-(b + c) * ia), s_hi = clamp11((b - c) * ia);
     s = t < -1.f ? s_lo : (t > 1.f ? s_hi : s);
+    // the second capsule is a sphere (ie == 0: e = b = f = 0, so denom < 2^-100 and t = 0 whatever s is): s = 0 would measure from
+    // the first segment's centre; the closest point of the first segment to the sphere's centre is s = clamp(-c / a).  Where ie is
+    // a compile-time constant (the generated tables, hipRTC) the select folds away
+    s = ie == 0.f ? clamp11(-c * ia) : s;
     t = clamp11(t);
     float df[3];
 #pragma unroll

@@ -674,7 +674,7 @@ static REAL seg_seg_closest(const REAL* C1, const REAL* H1, const REAL* C2, cons
     for (int i = 0; i < 3; ++i) rr[i] = C1[i] - C2[i];
     const REAL b = dot3(H1, H2), c = dot3(H1, rr), f = dot3(H2, rr);
     const REAL denom = FMA(-b, b, a * e);
-    REAL s = clamp11(FMA(b, f, -(c * e)) * rcp_rn_pos(denom)); /* parallel: s = 0, the centre */
+    REAL s = clamp11(FMA(b, f, -(c * e)) * rcp_rn_pos(denom)); /* exactly parallel, both with a length: s = 0, the centre */
     REAL t = FMA(b, s, f) * ie;
     if (t < -1) {
         t = -1;
@@ -683,6 +683,9 @@ static REAL seg_seg_closest(const REAL* C1, const REAL* H1, const REAL* C2, cons
         t = 1;
         s = clamp11((b - c) * ia);
     }
+    /* the second capsule is a sphere (ie == 0: e = b = f = 0, so t = 0 whatever s is): the closest point of the first segment
+     * to the sphere's centre, not the first segment's centre */
+    if (ie == 0) s = clamp11(-c * ia);
     REAL df[3];
     for (int i = 0; i < 3; ++i) {
         df[i] = FMA(-t, H2[i], FMA(s, H1[i], rr[i]));

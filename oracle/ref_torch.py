@@ -205,9 +205,15 @@ def _segment_segment_distance(P1, Q1, P2, Q2):
     a, e, f = (d1 * d1).sum(1), (d2 * d2).sum(1), (d2 * r).sum(1)
     c, b = (d1 * r).sum(1), (d1 * d2).sum(1)
     denom = a * e - b * b
-    s = torch.where(denom > 0, torch.clamp((b * f - c * e) / torch.where(denom > 0, denom, torch.ones_like(denom)), 0, 1), torch.zeros_like(denom))
-    t = (b * s + f) / e
-    s = torch.where(t < 0, torch.clamp(-c / a, 0, 1), torch.where(t > 1, torch.clamp((b - c) / a, 0, 1), s))
+    one, zero = torch.ones_like(denom), torch.zeros_like(denom)
+
+    def over(num, den):  # num / den, 0 where den vanishes (a zero-length segment is a point: its parameter stays 0)
+        return torch.where(den > 0, num / torch.where(den > 0, den, one), zero)
+
+    s = torch.clamp(over(b * f - c * e, denom), 0, 1)
+    t = over(b * s + f, e)
+    s = torch.where(t < 0, torch.clamp(over(-c, a), 0, 1), torch.where(t > 1, torch.clamp(over(b - c, a), 0, 1), s))
+    s = torch.where(e > 0, s, torch.clamp(over(-c, a), 0, 1))  # the second segment is a point: its projection on the first
     t = torch.clamp(t, 0, 1)
     diff = (P1 + d1 * s[:, None]) - (P2 + d2 * t[:, None])
     return diff.norm(dim=1)

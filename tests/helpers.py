@@ -210,6 +210,11 @@ SEGMENT_KATS = [
     (((0, 0, 0), (1, 0, 0)), ((0.5, 0.25, 0), (0.5, 2, 0)), 0.25),     # T shape: end point to interior
     (((0.375, 0.5, 0), (0.375, 0.5, 0)), ((0, 0, 0), (0, 0, 0)), 0.625),  # two spheres (zero-length segments)
     (((0, 0, 2), (0, 0, 2)), ((-1, 0, 0), (1, 0, 0)), 2.0),            # sphere to the interior of a segment
+    # a segment and a sphere in BOTH orders (with the sphere second the first segment's parameter used to stay at its centre)
+    (((0.75, 0, 2), (0.75, 0, 2)), ((-1, 0, 0), (1, 0, 0)), 2.0),      # sphere off-centre beside the segment
+    (((-1, 0, 0), (1, 0, 0)), ((0.75, 0, 2), (0.75, 0, 2)), 2.0),      # ... the sphere listed second
+    (((3, 0, 0), (3, 0, 0)), ((-1, 0, 0), (1, 0, 0)), 2.0),            # sphere beyond an end of the segment
+    (((-1, 0, 0), (1, 0, 0)), ((3, 0, 0), (3, 0, 0)), 2.0),            # ... the sphere listed second
 ]
 BOX_KATS = [  # against the unit box [0, 1]^3
     (((2, 0.5, 0.5), (3, 0.5, 0.5)), 1.0),               # along an axis, off a face
