@@ -186,6 +186,9 @@ MAX_BATCH = 16  # CPPF_MAX_BATCH
 MAX_SCENE_OBSTACLES = 4096  # CPPF_MAX_SCENE_OBSTACLES
 MOTION_MAX_LEVEL = 6  # CPPF_MOTION_MAX_LEVEL
 MOTION_CERTIFIED, MOTION_HIT = 1, 2  # cppf_motion_clearance's status bits (CPPF_MOTION_*)
+MOTION_OVERFLOW = 4  # cppf_motion_resolve's third status bit (CPPF_MOTION_OVERFLOW)
+MOTION_RESOLVE_MAX_DEPTH = 16  # CPPF_MOTION_RESOLVE_MAX_DEPTH
+MOTION_RESOLVE_MAX_FRONTIER = 4096  # CPPF_MOTION_RESOLVE_MAX_FRONTIER
 
 
 class LmBatchItem(ctypes.Structure):
@@ -234,6 +237,12 @@ SIGNATURES = {
          ctypes.c_size_t, _vp],
     ),
     "cppf_motion_rho": (ctypes.c_int, [_vp, ctypes.POINTER(_f)]),
+    "cppf_motion_resolve_workspace_bytes": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
+    "cppf_motion_resolve": (
+        ctypes.c_int,
+        [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_float, _vp,
+         _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp],
+    ),
     "cppf_self_collision_distances": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _vp]),
     "cppf_env_collision_distances": (
         ctypes.c_int,

@@ -64,6 +64,7 @@ constexpr int kBlock = CPPF_BLOCK;
 #include "kernels_eval.h"
 #include "kernels_scene.h"  // (ahead of the coupled step: its scene form shares the box / broadcast helpers)
 #include "kernels_motion.h"
+#include "kernels_motion_resolve.h"
 #include "kernels_coupled.h"
 #include "kernels_dp.h"
 #include "kernels_optloop.h"
@@ -1991,6 +1992,88 @@ int cppf_motion_clearance(const cppf_robot* robot, const float* q, int S, int W,
     if (int rc2 = check_launch()) return rc2;
     hipLaunchKernelGGL(motion_finish_kernel, dim3(tr_blocks), dim3(256), 0, st, mk.fail, mk.clear_key, mk.hit, n_tr, status, min_clear,
                        hit_node);
+    return check_launch();
+}
+
+// ---- adaptive bisection of the same test (kernels_motion_resolve.h) -----------------------------------------------------------------
+int cppf_motion_resolve_workspace_bytes(int S, int W, int max_frontier, size_t* bytes) {
+    CPPF_REQUIRE(bytes, "bytes is NULL");
+    CPPF_REQUIRE(S >= 0, "S < 0");
+    CPPF_REQUIRE(W >= 2, "W < 2: a motion needs two waypoints");
+    CPPF_REQUIRE(max_frontier >= 1 && max_frontier <= CPPF_MOTION_RESOLVE_MAX_FRONTIER,
+                 "max_frontier out of range (1 .. CPPF_MOTION_RESOLVE_MAX_FRONTIER)");
+    // two lists of max_frontier 32-bit interval indices per transition; never 0, so that "workspace is NULL" stays a refusal
+    *bytes = ((size_t)S * (size_t)(W - 1) * 2 * (size_t)max_frontier * sizeof(uint32_t) + 15) / 16 * 16 + 16;
+    return CPPF_OK;
+}
+
+int cppf_motion_resolve(const cppf_robot* robot, const float* q, int S, int W, int start_level, int max_depth, int max_frontier,
+                        const float* box_lo, const float* box_hi, int n_obs, float reach_m, const uint8_t* decided, uint8_t* status,
+                        int32_t* depth, int32_t* hit_num, float* min_clear, int32_t* n_tested, void* workspace, size_t workspace_bytes,
+                        void* stream) {
+    // every argument is checked before the device is selected (CPPF_ENTER), so that the checks hold for a host-only handle too
+    CPPF_REQUIRE(robot != nullptr, "robot handle is NULL");
+    CPPF_REQUIRE(!(robot->life.load(std::memory_order_acquire) & kRobotDead), "the robot handle was destroyed");
+    CPPF_REQUIRE(S >= 0, "S < 0");
+    CPPF_REQUIRE(W >= 2, "W < 2: a motion needs two waypoints");
+    CPPF_REQUIRE(start_level >= 0 && start_level <= CPPF_MOTION_MAX_LEVEL, "start_level out of range (0 .. CPPF_MOTION_MAX_LEVEL)");
+    CPPF_REQUIRE(max_depth >= start_level && max_depth <= CPPF_MOTION_RESOLVE_MAX_DEPTH,
+                 "max_depth out of range (start_level .. CPPF_MOTION_RESOLVE_MAX_DEPTH)");
+    CPPF_REQUIRE(max_frontier >= (1 << start_level) && max_frontier <= CPPF_MOTION_RESOLVE_MAX_FRONTIER,
+                 "max_frontier out of range (2^start_level .. CPPF_MOTION_RESOLVE_MAX_FRONTIER)");
+    CPPF_REQUIRE((size_t)S * (size_t)(W - 1) <= 0x7fffffffu, "S * (W-1) exceeds 2^31-1 transitions");
+    CPPF_REQUIRE(n_obs >= 0 && n_obs <= CPPF_MAX_SCENE_OBSTACLES, "n_obs out of range (0 .. CPPF_MAX_SCENE_OBSTACLES)");
+    CPPF_REQUIRE(reach_m >= 0.f, "reach_m must be in [0, +inf] (not NaN, not negative)");
+    CPPF_REQUIRE(S == 0 || (q && status), "q / status is NULL");
+    CPPF_REQUIRE(n_obs == 0 || (box_lo && box_hi), "box_lo / box_hi is NULL");
+    CPPF_REQUIRE(workspace, "workspace is NULL");
+    CPPF_REQUIRE(((uintptr_t)workspace & 15u) == 0, "workspace must be 16-byte aligned");
+    size_t need = 0;
+    if (int rc = cppf_motion_resolve_workspace_bytes(S, W, max_frontier, &need)) return rc;
+    CPPF_REQUIRE(workspace_bytes >= need, "workspace is smaller than cppf_motion_resolve_workspace_bytes(S, W, max_frontier)");
+    const int d = robot->desc.ndof;
+    if (d < 3) return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: kernels are built for ndof in 3..12");
+    const bool table = use_table(robot);  // (a handle specialised at run time takes the generic form: same bits)
+    const size_t lds = table ? 0 : robot->lds_bytes;
+    if (lds > (size_t)160 * 1024 - 1024)
+        return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: the generic motion kernel cannot stage this many capsules");
+    CPPF_ENTER(robot);
+    hipStream_t st = (hipStream_t)stream;
+    if (S == 0) return CPPF_OK;
+    CPPF_REQUIRE(robot->d_quad != nullptr, "the handle has no device tables");
+
+    const size_t n_tr = (size_t)S * (size_t)(W - 1);
+    ResolveK rk;
+    rk.box_lo = box_lo;
+    rk.box_hi = box_hi;
+    rk.rho = reinterpret_cast<const float*>(static_cast<const uint4*>(robot->d_quad) + kQuadTableRecs);
+    rk.decided = decided;
+    rk.status = status;
+    rk.depth = depth;
+    rk.hit_num = hit_num;
+    rk.min_clear = min_clear;
+    rk.n_tested = n_tested;
+    rk.frontier = static_cast<uint32_t*>(workspace);
+    rk.S = S, rk.W = W, rk.start_level = start_level, rk.max_depth = max_depth, rk.max_frontier = max_frontier;
+    rk.n_obs = n_obs;
+    rk.reach = reach_m;
+    double r_max = 0.0;
+    for (int c = 0; c < CPPF_MAX_CAPSULES; ++c) rk.cull2[c] = 0.f;
+    for (int c = 0; c < robot->coll.ncaps; ++c) {
+        r_max = std::max(r_max, (double)robot->desc.cap_r[c]);
+        rk.cull2[c] = cull_threshold(cap_half_length(robot->desc, c) + (double)robot->desc.cap_r[c] + (double)reach_m);
+    }
+    rk.tile_cull2 = cull_threshold(r_max + (double)reach_m);
+    const unsigned blocks = (unsigned)((n_tr + kBlock / 64 - 1) / (kBlock / 64));  // one wavefront per transition
+    const int rc = for_robot(robot, [&](auto tag) {
+        using RB = typename decltype(tag)::type;
+        const auto kernel = &motion_resolve_kernel<RB>;
+        if (lds > (size_t)64 * 1024)
+            CPPF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), lds, st, robot->chain, robot->coll, rk, q);
+        return CPPF_OK;
+    });
+    if (rc) return rc;
     return check_launch();
 }
 

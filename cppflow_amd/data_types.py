@@ -306,10 +306,22 @@ class MotionClearance:
     hit_node: torch.Tensor  # int32: the lowest penetrating node of the transition (0 .. 2^level), else -1
     level: int
     reach_m: float
+    # with `resolve_depth` only (adaptive bisection, `Robot.motion_resolve`); hit_node then holds hit_num, a node of level `depth`
+    depth: Optional[torch.Tensor] = None  # int32: the level at which the transition ended (level .. resolve_depth)
+    n_tested: Optional[torch.Tensor] = None  # int32: interval tests spent on the transition
+    overflow: Optional[torch.Tensor] = None  # bool: undecided because the frontier did not fit
 
     @property
     def undecided(self) -> torch.Tensor:
         return ~(self.certified | self.hit)
+
+    @property
+    def hit_param(self) -> torch.Tensor:
+        """float32: where on the transition (0 at its first waypoint, 1 at its second) the lowest penetrating node sits; NaN where
+        nothing was hit"""
+        shift = self.depth if self.depth is not None else torch.full_like(self.hit_node, self.level)
+        t = torch.ldexp(self.hit_node.to(torch.float32), -shift)
+        return torch.where(self.hit_node >= 0, t, torch.full_like(t, float("nan")))
 
     @property
     def all_certified(self) -> torch.Tensor:
@@ -428,14 +440,21 @@ class Problem:
         sc = self.scene(q.device)
         return self.robot.scene_env_collisions(q, sc.lo, sc.hi, reach=reach_m, want=want)
 
-    def motion_clearance(self, q_paths: torch.Tensor, level: int = 6, reach_m: float = 0.05) -> "MotionClearance":
+    def motion_clearance(self, q_paths: torch.Tensor, level: int = 6, reach_m: float = 0.05,
+                         resolve_depth: Optional[int] = None) -> "MotionClearance":
         """Certify the motion BETWEEN the waypoints of q_paths [k, T, d] (or one path [T, d]) against the robot itself and ALL of
         this problem's cuboids, however many (`Robot.motion_clearance` on `scene()`; a rotated cuboid raises there).  Joint values
-        are taken as stored: unwrap continuous joints first."""
+        are taken as stored: unwrap continuous joints first.  `resolve_depth` (level .. 16): bisect what the uniform test at `level`
+        leaves undecided down to that depth (`Robot.motion_resolve`, which subsumes the uniform test at its start level)."""
         from cppflow_amd import _hip
 
         q = q_paths.unsqueeze(0) if q_paths.dim() == 2 else q_paths
         sc = self.scene(q.device)
+        if resolve_depth is not None:
+            r = self.robot.motion_resolve(q, sc.lo, sc.hi, start_level=level, max_depth=resolve_depth, reach=reach_m)
+            return MotionClearance(certified=(r["status"] & _hip.MOTION_CERTIFIED) != 0, hit=(r["status"] & _hip.MOTION_HIT) != 0,
+                                   min_clear=r["min_clear"], hit_node=r["hit_num"], level=int(level), reach_m=float(reach_m),
+                                   depth=r["depth"], n_tested=r["n_tested"], overflow=(r["status"] & _hip.MOTION_OVERFLOW) != 0)  # fmt: skip
         r = self.robot.motion_clearance(q, sc.lo, sc.hi, level=level, reach=reach_m)
         return MotionClearance(certified=(r["status"] & _hip.MOTION_CERTIFIED) != 0, hit=(r["status"] & _hip.MOTION_HIT) != 0,
                                min_clear=r["min_clear"], hit_node=r["hit_node"], level=int(level), reach_m=float(reach_m))  # fmt: skip

@@ -51,10 +51,15 @@ def add_search_path_mjac(debug_info: Dict, problem: Problem, qpath_search: torch
     debug_info["search_path_min_dist_to_jlim_deg"] = min(float(torch.rad2deg(rest.min())), 10000) if rest.numel() else 10000
 
 
-def add_motion_certificate(debug_info: Dict, problem: Problem, qpath: torch.Tensor, level: int) -> None:
+def add_motion_certificate(debug_info: Dict, problem: Problem, qpath: torch.Tensor, level: int, depth: Optional[int] = None) -> None:
     """`Problem.motion_clearance` of the path [T, d] about to be returned -> debug_info: is every transition certified collision-free,
-    and which transitions are hit / left undecided (indices t: the move from waypoint t to t + 1)."""
-    mc = problem.motion_clearance(qpath.detach().contiguous(), level=level)
+    and which transitions are hit / left undecided (indices t: the move from waypoint t to t + 1).  With `depth` the certificate is
+    taken by adaptive bisection from `level` down to `depth`, and the deepest level any transition ended at and the mean number of
+    interval tests per transition are reported as well."""
+    mc = problem.motion_clearance(qpath.detach().contiguous(), level=level, resolve_depth=depth)
+    if depth is not None:
+        debug_info["motion_resolve_depth"] = int(mc.depth.max())
+        debug_info["motion_tests_per_transition"] = float(mc.n_tested.to(torch.float64).mean())
     debug_info["motion_certified"] = bool(mc.all_certified[0])
     debug_info["motion_hit_transitions"] = torch.nonzero(mc.hit[0]).flatten().tolist()
     debug_info["motion_undecided_transitions"] = torch.nonzero(mc.undecided[0]).flatten().tolist()
@@ -159,7 +164,7 @@ class Planner:
     def __init__(self, settings: PlannerSettings, robot, seed_provider: Optional[SeedProvider] = None, process_group=None,
                  candidate_lm_steps: int = 0, device_optimizer: bool = False, n_search_paths: int = 1,
                  search_path_separation_rad: float = 0.5, pin_initial_configuration: bool = False, scene_optimizer: bool = False,
-                 certify_motion_level: Optional[int] = None):
+                 certify_motion_level: Optional[int] = None, certify_motion_depth: Optional[int] = None):
         """`process_group` / `candidate_lm_steps`: the sharded candidate stage (module docstring); with `candidate_lm_steps` > 0 every
         (candidate, waypoint) row takes that many fused pose-only LM iterations before the masks are evaluated (one launch).
         `device_optimizer`: the LM optimiser's loop is decided on the device (`run_lm_optimization(device_loop=True)`); same plan.
@@ -174,9 +179,17 @@ class Planner:
         (`run_lm_optimization(scene_in_step=True)`) instead of an active set of 8; not together with `device_optimizer`.
         `certify_motion_level` (0 .. 6; default None = off): `CppFlowPlanner` checks the MOTION between the waypoints of the plan
         it returns once (`Problem.motion_clearance` at 2^level intervals per transition) and reports `motion_certified`,
-        `motion_hit_transitions` and `motion_undecided_transitions` in `debug_info`.  The plan and `Plan.is_valid` are unchanged."""
+        `motion_hit_transitions` and `motion_undecided_transitions` in `debug_info`.  The plan and `Plan.is_valid` are unchanged.
+        `certify_motion_depth` (certify_motion_level .. 16; default None = off; needs `certify_motion_level`): the certificate is
+        taken by adaptive bisection (`Problem.motion_clearance(resolve_depth=)`): what the uniform test at the level leaves undecided
+        is bisected down to this depth, and `debug_info` gains `motion_resolve_depth` (the deepest level any transition ended at)
+        and `motion_tests_per_transition` (the mean number of interval tests)."""
         assert certify_motion_level is None or 0 <= int(certify_motion_level) <= 6, "certify_motion_level must be None or 0 .. 6"
         self._certify_motion_level = None if certify_motion_level is None else int(certify_motion_level)
+        assert certify_motion_depth is None or (
+            self._certify_motion_level is not None and self._certify_motion_level <= int(certify_motion_depth) <= 16
+        ), "certify_motion_depth needs certify_motion_level and must be None or certify_motion_level .. 16"
+        self._certify_motion_depth = None if certify_motion_depth is None else int(certify_motion_depth)
         assert not (device_optimizer and scene_optimizer), (
             "scene_optimizer=True is not combined with device_optimizer=True: the device loop's gated mask and step launches take "
             "their cuboids from the robot handle"
@@ -297,7 +310,7 @@ class CppFlowPlanner(Planner):
 
         def result(qpath) -> PlannerResult:
             if self._certify_motion_level is not None:
-                add_motion_certificate(debug_info, problem, qpath, self._certify_motion_level)
+                add_motion_certificate(debug_info, problem, qpath, self._certify_motion_level, self._certify_motion_depth)
             return PlannerResult(
                 plan_from_qpath(qpath, problem),
                 TimingData(time() - t0, td.ikflow, td.coll_checking, td.batch_opt, td.dp_search, td.optimizer), [], [],

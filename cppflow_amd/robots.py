@@ -600,6 +600,59 @@ class Robot:
         )
         return res
 
+    def motion_resolve(self, q: torch.Tensor, box_lo: torch.Tensor, box_hi: torch.Tensor, start_level: int = 0, max_depth: int = 16,
+                       max_frontier: int = 512, reach: float = 0.05, decided: Optional[torch.Tensor] = None,
+                       want: Sequence[str] = ("status", "depth", "hit_num", "min_clear", "n_tested")) -> Dict[str, torch.Tensor]:
+        """`motion_clearance` made adaptive (`cppf_motion_resolve`, csrc/kernels_motion_resolve.h): from 2^start_level intervals per
+        transition only the intervals whose test fails are bisected, breadth first, until they pass (certified), a node penetrates
+        (hit), `max_depth` is reached (undecided) or more than `max_frontier` intervals are open at one level (status bit 2,
+        overflow).  status (uint8 [S, W-1], always returned); depth (int32): the level at which the transition ended; hit_num
+        (int32): the lowest penetrating node of that level, at parameter hit_num / 2^depth, else -1; min_clear (float): the smallest
+        clearance of any node evaluated; n_tested (int32): interval tests spent.  `decided` (uint8 or bool [S, W-1]): transitions
+        where it is non-zero are not examined; given a uint8 tensor, it is ALSO the status output, so that a status from an earlier
+        call is completed in place and the other outputs of such transitions keep what they held (here: zeros)."""
+        q = _require_device_tensor(q, "q")
+        assert q.dim() == 3 and q.shape[2] == self.ndof, f"q must be [k, ntimesteps, {self.ndof}], is {tuple(q.shape)}"
+        S, W, _ = q.shape
+        dev = q.device
+        box_lo, box_hi = _require_device_tensor(box_lo, "box_lo"), _require_device_tensor(box_hi, "box_hi")
+        assert box_lo.dim() == 2 and box_lo.shape[1] == 3 and box_hi.shape == box_lo.shape, (tuple(box_lo.shape), tuple(box_hi.shape))
+        assert box_lo.device == dev and box_hi.device == dev, "q, box_lo and box_hi must be on one device"
+        O = int(box_lo.shape[0])
+        want = tuple(want)
+        assert set(want) <= {"status", "depth", "hit_num", "min_clear", "n_tested"}, want
+        start_level, max_depth, max_frontier = int(start_level), int(max_depth), int(max_frontier)
+        assert 0 <= start_level <= _hip.MOTION_MAX_LEVEL and start_level <= max_depth <= _hip.MOTION_RESOLVE_MAX_DEPTH, (start_level, max_depth)
+        assert (1 << start_level) <= max_frontier <= _hip.MOTION_RESOLVE_MAX_FRONTIER and W >= 2, (max_frontier, W)
+        skipping = decided is not None
+        if skipping:
+            assert isinstance(decided, torch.Tensor) and decided.dtype in (torch.uint8, torch.bool), "decided must be a uint8 or bool tensor"
+            decided = _require_device_tensor(decided, "decided", dtype=decided.dtype)
+            assert decided.shape == (S, W - 1) and decided.device == dev, (tuple(decided.shape), decided.device)
+            assert decided.is_contiguous(), "decided must be contiguous"
+        in_place = skipping and decided.dtype == torch.uint8
+        # with `decided` the skipped transitions are not written: their outputs must not be uninitialised memory
+        new = torch.zeros if skipping else torch.empty
+        res: Dict[str, torch.Tensor] = {"status": decided if in_place else new((S, W - 1), dtype=torch.uint8, device=dev)}
+        for k, dtype in (("depth", torch.int32), ("hit_num", torch.int32), ("min_clear", torch.float32), ("n_tested", torch.int32)):
+            if k in want:
+                res[k] = new((S, W - 1), dtype=dtype, device=dev)
+        nbytes = ctypes.c_size_t()
+        _hip.check(_hip.lib().cppf_motion_resolve_workspace_bytes(S, W, max_frontier, ctypes.byref(nbytes)))
+        work = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+
+        def ptr(k):
+            return res[k].data_ptr() if k in res else None
+
+        _hip.check(
+            _hip.lib().cppf_motion_resolve(
+                self._handle(dev), q.data_ptr(), S, W, start_level, max_depth, max_frontier, box_lo.data_ptr(), box_hi.data_ptr(), O,
+                float(reach), decided.data_ptr() if skipping else None, ptr("status"), ptr("depth"), ptr("hit_num"), ptr("min_clear"),
+                ptr("n_tested"), work.data_ptr(), nbytes.value, _stream_ptr(dev),
+            )  # fmt: skip
+        )
+        return res
+
     def pose_error_metrics(self, x: torch.Tensor, target: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """(positional error [n] in metres, rotational error [n] in radians); target [W,7], n % W == 0."""
         x = self._x2d(x)

@@ -321,6 +321,46 @@ int cppf_motion_clearance(const cppf_robot* robot, const float* q, int S, int W,
 /* the travel-bound table of the handle, HOST rho[CPPF_MAX_DOF][CPPF_MAX_CAPSULES] (needs no device) */
 int cppf_motion_rho(const cppf_robot* robot, float* rho);
 
+/* The same test made ADAPTIVE, as Schwarzer, Saha and Latombe state it: only the intervals whose test fails are bisected, until they
+ * pass, a node penetrates, or a resolution floor is reached.  q, the scene, reach_m, the clearances and their truncation at reach_m,
+ * rho, lambda_c, lambda_p, the 1e-6 slack, the joint-limit rule and "no wrapping" are those of cppf_motion_clearance.
+ *   Nodes and intervals.  Node (L, i), 0 <= i <= 2^L, is a itself for i = 0, b itself for i = 2^L, otherwise fmaf(i 2^-L, b - a, a) per
+ *   joint (the subtraction in fp32): (L, i) and (L+1, 2i) are the same bits.  Interval (L, i) lies between the nodes (L, i) and
+ *   (L, i+1).  It PASSES when every self pair and every (capsule, cuboid) has (clear_i + clear_{i+1}) - lambda 2^-L > 1e-6 (fp32, in
+ *   that order); a cuboid beyond reach_m at both ends counts with reach_m at both ends, whatever the kernel's culling skips.
+ *   Per transition tr of [S, W-1], breadth first -- no output depends on any order of arrival:
+ *     0. decided != NULL and decided[tr] != 0: the transition is not examined and none of its outputs is written (decided may
+ *        alias status: resolve what an earlier call left undecided, in place).
+ *     1. L = start_level, F = all 2^L intervals, n_tested = 0, min_clear = +inf.
+ *     2. |F| > max_frontier: status = CPPF_MOTION_OVERFLOW, depth = L, stop.
+ *     3. Both end nodes of every interval of F are evaluated.  n_tested += |F|; min_clear = min over every evaluated node of
+ *        min(min_self, min_env), the per-node value behind cppf_motion_clearance's min_clear (+inf beyond reach_m).
+ *     4. An evaluated node has a clearance < 0: status = CPPF_MOTION_HIT, depth = L, hit_num = the lowest such i (the hit sits at
+ *        parameter hit_num / 2^depth), stop.
+ *     5. A waypoint lies outside the joint limits: status = 0, depth = L, stop.
+ *     6. F' = the children (L+1, 2i) and (L+1, 2i+1) of every interval of F that does not pass.  F' empty: status =
+ *        CPPF_MOTION_CERTIFIED, depth = L, stop.
+ *     7. L == max_depth: status = 0 (undecided), depth = L, stop.  Otherwise F = F', L = L + 1, back to 2.
+ *   status u8 [S, W-1]; depth, hit_num (-1 unless HIT), n_tested int32 [S, W-1] and min_clear float [S, W-1] may each be NULL.
+ *   CPPF_MOTION_OVERFLOW (bit 2) is never set together with bit 0 or 1.
+ * With start_level == max_depth == L and decided == NULL, status and min_clear equal cppf_motion_clearance(level = L) bit for bit and
+ * hit_num equals its hit_node.
+ * start_level in 0 .. CPPF_MOTION_MAX_LEVEL, max_depth in start_level .. CPPF_MOTION_RESOLVE_MAX_DEPTH, max_frontier in
+ * 2^start_level .. CPPF_MOTION_RESOLVE_MAX_FRONTIER, W >= 2, n_obs and reach_m as above.  workspace:
+ * cppf_motion_resolve_workspace_bytes(S, W, max_frontier) bytes, 16-byte aligned, device; scratch on return.  One launch on `stream`,
+ * asynchronous, no host synchronisation, capturable in a graph; two runs give the same bits.  CPPF_ERR_INVALID, before the device is
+ * selected: a NULL / destroyed handle, NULL q / status / corners, start_level, max_depth or max_frontier out of range, W < 2, S < 0,
+ * n_obs out of range, a NaN or negative reach_m, a short or misaligned workspace.  A handle specialised at run time is served by the
+ * generic kernel. */
+#define CPPF_MOTION_RESOLVE_MAX_DEPTH 16
+#define CPPF_MOTION_RESOLVE_MAX_FRONTIER 4096
+#define CPPF_MOTION_OVERFLOW 4 /* status bit: undecided because the frontier did not fit; never with bit 0 or 1 */
+int cppf_motion_resolve_workspace_bytes(int S, int W, int max_frontier, size_t* bytes);
+int cppf_motion_resolve(const cppf_robot* robot, const float* q, int S, int W, int start_level, int max_depth, int max_frontier,
+                        const float* box_lo, const float* box_hi, int n_obs, float reach_m, const uint8_t* decided,
+                        uint8_t* status, int32_t* depth, int32_t* hit_num, float* min_clear, int32_t* n_tested,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 /* Robot.self_collision_distances(x) -> [n, n_pairs] (call site cppflow/collision_detection.py:65) */
 int cppf_self_collision_distances(const cppf_robot* robot, const float* x, int n, float* dists, void* stream);
 
