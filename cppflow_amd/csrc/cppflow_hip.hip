@@ -571,7 +571,10 @@ int cppf_debug_rtc_compile(const cppf_robot_desc* desc, const char* cache_dir) {
     rb->device = kNoDevice;
     const int rc = cppf_robot_specialize(rb, cache_dir);
     delete rb;
-    // without a device the last stage (loading the code object) fails by design; the compile + cache stages have run
+    // without a device the last stage (loading the code object) fails by design; the compile + cache stages have run.  That failure
+    // (selecting a device that does not exist) stays behind as the calling thread's last HIP error, and the next launch check of that
+    // thread -- this library's or torch's -- would report it as its own: take it back here.
+    (void)hipGetLastError();
     return rc;
 }
 

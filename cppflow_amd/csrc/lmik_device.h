@@ -175,8 +175,11 @@ struct StaRobot {
 
 // ---- sin / cos ------------------------------------------------------------------------------------------------------------
 // Cody-Waite reduction by pi/2 in three exact pieces + Cephes single-precision minimax polynomials on [-pi/4, pi/4].
-// ~24 VALU instructions, no slow path: joint angles are bounded by the joint limits (|q| < 2^10 is ample; the magic-number
-// rounding needs |x * 2/pi| < 2^22).
+// ~24 VALU instructions, no slow path.  DOMAIN (tests/angle_domain.py sweeps it through FK on the device): against true sin / cos
+// the absolute error stays below 1.2e-7 and |s^2 + c^2 - 1| below 1.7 * 2^-23 for every |x| <= 2^20, the largest |x| swept (measured
+// 9.2e-8: the three pieces of pi/2 are good for the whole range).  Up to 2^22 pi/2 = 6.59e6 the magic-number rounding still finds
+// the quadrant (1e-6 there).  Beyond that the result is UNSPECIFIED: 1.3 off at 1e7, entries of 1e18 at 1e10, inf / NaN at 1e30; it
+// stays inside its own row.  +-inf and NaN give NaN.  No instruction is spent on inputs outside the domain.
 // The fp32 oracle build uses the identical formula, so FK agrees bit for bit.
 __device__ __forceinline__ void sincos_cw(float x, float& s, float& c) {
     // k = round-to-nearest-even(x * 2/pi) by the magic-number trick: adding 1.5 * 2^23 leaves the integer in the low mantissa
@@ -215,8 +218,12 @@ __device__ __forceinline__ void sincos_hw(float x, float& s, float& c) {
 // rounding of the alternating terms near +-pi, not the truncation), 13 multiply-adds where sincos_cw takes 23 instructions of which
 // eight are the integer quadrant logic.  FOLD says how the argument gets into [-pi, pi]: 0 it is there (the joint's limits say so:
 // every joint of the shipped robots but Panda's sixth), +1 / -1 one conditional turn down / up (limits within [-pi, 3 pi] /
-// [-3 pi, pi]), 2 the general reduction by whole turns.  Like sincos_hw only for the leading iterations of a fused K-step launch
-// (CPPF_LEAD_SINCOS = 2, kernels_fused.h), whose iterates nobody sees; never in the bit-exact set.
+// [-3 pi, pi]), 2 the general reduction by whole turns.  The figures above are FOLD 0's; measured over each fold's own domain
+// (tests/angle_domain.py) the larger of the two errors is 4.9e-7 (0), 6.5e-7 (+-1: the fp32 value of 2 pi is 1.7e-7 off) and
+// 5.6e-7 / 6.6e-7 / 2.5e-6 (2, for |x| <= 2^10 / 2^16 / 2^20: two pieces of 2 pi, not three).  These hold with every fused
+// multiply-add rounded ONCE, as the device rounds it; evaluated with separate multiplies and adds FOLD 0 reaches 6.2e-7.
+// Like sincos_hw only for the leading iterations of a fused K-step launch (CPPF_LEAD_SINCOS = 2, kernels_fused.h), whose
+// iterates nobody sees; never in the bit-exact set.
 constexpr float kPiF = 3.14159274101257324f, kTwoPiF = 6.28318548202514648f;
 template <int FOLD>
 __device__ __forceinline__ void sincos_pi(float x, float& s, float& c) {
@@ -540,7 +547,9 @@ __device__ __forceinline__ float wrap_pi(float dq) {
 // redoes the set through wrap_pi when any |dq + pi| >= 4 pi or is NaN.  Same results bit for bit; what it saves is a divergent
 // branch with the fmodf expansion behind it PER VALUE (a (min, max) product step of dp_search wraps 7 .. 12 differences per
 // candidate pair: 1 179 instructions per source and two destinations, 442 of them scalar branch bookkeeping, became ~300).
-template <int N>
+// NAN_TO_INF: a value that wraps to NaN (a NaN or +-inf difference) comes back as +inf instead -- behind the rare branch, which is
+// taken for exactly those inputs, so the straight-line path is the same instructions either way.
+template <int N, bool NAN_TO_INF = false>
 __device__ __forceinline__ void wrap_pi_all(float (&dq)[N]) {
     const float pi = 3.14159265358979323846f, p2 = 2.f * pi;
     float out[N];
@@ -556,16 +565,18 @@ __device__ __forceinline__ void wrap_pi_all(float (&dq)[N]) {
     }
     if (__builtin_expect(far, 0)) {
 #pragma unroll
-        for (int j = 0; j < N; ++j) out[j] = wrap_pi(dq[j]);
+        for (int j = 0; j < N; ++j) out[j] = NAN_TO_INF ? nan_to_inf(wrap_pi(dq[j])) : wrap_pi(dq[j]);
     }
 #pragma unroll
     for (int j = 0; j < N; ++j) dq[j] = out[j];
 }
 
-// max_j |wrap_pi(dq[j])|: the joint-change measure of dp_search and the trajectory metrics (search.py:115-125)
+// max_j |wrap_pi(dq[j])|: the joint-change measure of dp_search and the trajectory metrics (search.py:115-125).  A NaN or +-inf
+// difference makes it +inf -- fmaxf would drop the NaN and the joint would count as not having moved -- which is the convention of
+// the per-seed maxima (nan_to_inf above); torch's remainder -> max gives NaN there.
 template <int N>
 __device__ __forceinline__ float max_wrapped_change(float (&dq)[N]) {
-    wrap_pi_all<N>(dq);
+    wrap_pi_all<N, true>(dq);
     float m = 0.f;
 #pragma unroll
     for (int j = 0; j < N; ++j) m = fmaxf(m, fabsf(dq[j]));

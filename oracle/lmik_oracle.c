@@ -892,6 +892,10 @@ static REAL wrap_pi(REAL dq) {
     return m - pi;
 }
 
+/* What the maxima of the joint changes take: a NaN (a NaN or +-inf joint: fmod(inf) is NaN) counts as +inf, the device's nan_to_inf,
+ * where torch's remainder -> max would hold NaN and a plain `v > m` scan would drop the joint as if it had not moved */
+static REAL nan_to_inf(REAL v) { return v != v ? (REAL)INFINITY : v; }
+
 /* angular_changes: qpath[T,c] -> [T-1,c] */
 void orc_angular_changes(const double* qpath, int T, int c, double* out) {
     for (int t = 0; t + 1 < T; ++t)
@@ -921,10 +925,10 @@ void orc_seed_validity(const void* h, const double* x, const double* target, int
             for (int j = 0; j < d; ++j) {
                 const REAL dq = (REAL)xs[(size_t)(w + 1) * d + j] - (REAL)xs[(size_t)w * d + j];
                 if (rb->jtype[j] == 0) {
-                    const REAL v = FABS(rad2deg * wrap_pi(dq));
+                    const REAL v = nan_to_inf(FABS(rad2deg * wrap_pi(dq)));
                     if (v > mrev) mrev = v;
                 } else {
-                    const REAL v = FABS((REAL)100 * dq);
+                    const REAL v = nan_to_inf(FABS((REAL)100 * dq));
                     if (v > mpri) mpri = v;
                 }
             }
@@ -974,11 +978,11 @@ void orc_plan_metrics(const void* h, const double* x, const double* target, int 
                 const REAL dq = (REAL)xs[(size_t)(w + 1) * d + j] - (REAL)xs[(size_t)w * d + j];
                 if (rb->jtype[j] == 0) {
                     const REAL v = FABS(wrap_pi(dq));
-                    if (rad2deg * v > mrev) mrev = rad2deg * v;
+                    if (nan_to_inf(rad2deg * v) > mrev) mrev = nan_to_inf(rad2deg * v);
                     lrad += v;
                 } else {
                     const REAL v = FABS(dq);
-                    if ((REAL)100 * v > mpri) mpri = (REAL)100 * v;
+                    if (nan_to_inf((REAL)100 * v) > mpri) mpri = nan_to_inf((REAL)100 * v);
                     lm += v;
                 }
             }
@@ -1022,7 +1026,7 @@ void orc_dp_search(const void* h, const double* q, const double* ext, int k, int
                 for (int j = 0; j < d; ++j) {
                     REAL dq = (REAL)q[((size_t)b * T + t) * d + j] - (REAL)q[((size_t)a * T + t - 1) * d + j];
                     if (rb->jtype[j] == 1) dq *= (REAL)prismatic_scaling;
-                    const REAL v = FABS(wrap_pi(dq));
+                    const REAL v = nan_to_inf(FABS(wrap_pi(dq)));
                     if (v > m) m = v;
                 }
                 const REAL c = costs[(size_t)a * T + t - 1];

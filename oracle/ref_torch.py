@@ -338,7 +338,9 @@ def _get_mjacs(q: torch.Tensor, robot, prismatic_joint_scaling: float = 5.0) -> 
     if len(robot.prismatic_joint_idxs) > 0:
         dqs = dqs.clone()
         dqs[:, :, :, robot.prismatic_joint_idxs] *= prismatic_joint_scaling
-    return torch.abs(torch.remainder(dqs + math.pi, 2 * math.pi) - math.pi).amax(dim=3)
+    m = torch.abs(torch.remainder(dqs + math.pi, 2 * math.pi) - math.pi).amax(dim=3)
+    # a NaN or +-inf joint: torch holds NaN here; the library's convention is +inf, so that no search walks through it
+    return torch.where(torch.isnan(m), torch.full_like(m, math.inf), m)
 
 
 def dp_search(robot, q: torch.Tensor, q_costs_external: torch.Tensor) -> torch.Tensor:
