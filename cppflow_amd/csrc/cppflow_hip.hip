@@ -24,6 +24,7 @@
 #include <new>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/cppflow_hip_debug.h"
@@ -360,6 +361,83 @@ struct DeviceGuard {
     if (device_guard__.err != hipSuccess)                                                                            \
         return fail(CPPF_ERR_HIP, std::string("cppflow_hip: selecting the robot's device failed: ") +               \
                                       hipGetErrorString(device_guard__.err))
+
+// a launch with `lds` bytes of dynamic LDS: beyond 64 KB the kernel's own limit is raised first (per device: set whenever it is
+// needed, a host-side table update)
+template <class K, class... A>
+int launch_lds(K kernel, dim3 grid, size_t lds, hipStream_t st, const A&... args) {
+    if (lds > (size_t)64 * 1024)
+        CPPF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), lds, st, args...);
+    return CPPF_OK;
+}
+
+// ---- what the calls over a scene in device memory share (kernels_scene.h) ----------------------------------------------------------
+// the culling block of a walk over the scene's cuboids at this reach (reach = 0: cull2[c] is cull_threshold of the same double sum
+// as cap_cull[c], i.e. cap_cull[c] itself, and tile_cull2 the coupled step's)
+float tile_cull_threshold(const cppf_robot* robot, float reach) {  // wavefront box vs cuboid: the widest capsule decides
+    double r_max = 0.0;
+    for (int c = 0; c < robot->coll.ncaps; ++c) r_max = std::max(r_max, (double)robot->desc.cap_r[c]);
+    return cull_threshold(r_max + (double)reach);
+}
+SceneCullK scene_cull_setup(const cppf_robot* robot, const float* box_lo, const float* box_hi, int n_obs, float reach) {
+    SceneCullK sc;
+    sc.box_lo = box_lo;
+    sc.box_hi = box_hi;
+    sc.n_obs = n_obs;
+    sc.reach = reach;
+    for (int c = 0; c < CPPF_MAX_CAPSULES; ++c) sc.cull2[c] = 0.f;
+    for (int c = 0; c < robot->coll.ncaps; ++c)
+        sc.cull2[c] = cull_threshold(cap_half_length(robot->desc, c) + (double)robot->desc.cap_r[c] + (double)reach);
+    sc.tile_cull2 = tile_cull_threshold(robot, reach);
+    return sc;
+}
+
+// Chunks of cuboids (grid.y) for a launch of `blocks` workgroups along grid.x: enough workgroups for four per compute unit (four
+// wavefronts per SIMD) where those alone do not give them, in groups of 8 cuboids -- a lone wavefront per SIMD issues at a fraction
+// of the rate, and one plan's rows are a single workgroup (measured: 1 x 256 rows, 64 cuboids, reach = inf, one chunk of 64: 253 us).
+// A chunk repeats the capsule FK of its rows, which is small beside 8 cuboids x every capsule.  The result does not depend on the
+// cut (integer min over keys).
+struct CuboidChunks {
+    int n_chunks, chunk;  // chunk: cuboids per blockIdx.y, a multiple of 8
+};
+CuboidChunks cut_cuboid_chunks(const cppf_robot* robot, unsigned blocks, int n_obs) {
+    const int groups = (n_obs + 7) / 8;
+    if (groups == 0 || blocks == 0) return {1, 64};
+    const unsigned want_blocks = 4u * (unsigned)(robot->cu_count > 0 ? robot->cu_count : 256);
+    int n_chunks = (int)std::min<unsigned>((unsigned)groups, std::max(1u, (want_blocks + blocks - 1) / blocks));
+    const int groups_per_chunk = (groups + n_chunks - 1) / n_chunks;
+    n_chunks = (groups + groups_per_chunk - 1) / groups_per_chunk;
+    return {n_chunks, groups_per_chunk * 8};
+}
+
+// The argument rules of cppf_scene_env_collisions, cppf_motion_clearance and cppf_motion_resolve, in the order a caller meets them.
+// The call's own rules sit between the shared ones: `shape` (its sizes), `io_ok` (q and its first output), `need` (its workspace
+// size); `kernel` names its generic kernel.  Every argument is checked before the device is selected (CPPF_ENTER), so that the checks
+// hold for a host-only handle too.  *lds: the dynamic LDS of the launch (a handle specialised at run time takes the generic form:
+// same bits).
+template <class Shape, class Need>
+int check_scene_call(const cppf_robot* robot, Shape&& shape, int n_obs, float reach_m, bool io_ok, const char* io_msg, const float* box_lo,
+                     const float* box_hi, const void* workspace, size_t workspace_bytes, Need&& need, const char* need_msg,
+                     const char* kernel, size_t* lds) {
+    CPPF_REQUIRE(robot != nullptr, "robot handle is NULL");
+    CPPF_REQUIRE(!(robot->life.load(std::memory_order_acquire) & kRobotDead), "the robot handle was destroyed");
+    if (int rc = shape()) return rc;
+    CPPF_REQUIRE(n_obs >= 0 && n_obs <= CPPF_MAX_SCENE_OBSTACLES, "n_obs out of range (0 .. CPPF_MAX_SCENE_OBSTACLES)");
+    CPPF_REQUIRE(reach_m >= 0.f, "reach_m must be in [0, +inf] (not NaN, not negative)");
+    CPPF_REQUIRE(io_ok, io_msg);
+    CPPF_REQUIRE(n_obs == 0 || (box_lo && box_hi), "box_lo / box_hi is NULL");
+    CPPF_REQUIRE(workspace, "workspace is NULL");
+    CPPF_REQUIRE(((uintptr_t)workspace & 15u) == 0, "workspace must be 16-byte aligned");
+    size_t bytes = 0;
+    if (int rc = need(&bytes)) return rc;
+    CPPF_REQUIRE(workspace_bytes >= bytes, need_msg);
+    if (robot->desc.ndof < 3) return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: kernels are built for ndof in 3..12");
+    *lds = use_table(robot) ? 0 : robot->lds_bytes;
+    if (*lds > (size_t)160 * 1024 - 1024)
+        return fail(CPPF_ERR_UNSUPPORTED, std::string("cppflow_hip: the generic ") + kernel + " kernel cannot stage this many capsules");
+    return CPPF_OK;
+}
 
 }  // namespace
 
@@ -973,9 +1051,7 @@ int lm_full_step_gated(const cppf_robot* robot, const float* x_in, const float* 
             // which the occupancy-bound build of the handle form pays.  (A handle specialised at run time takes the generic form,
             // like every coupled step: for_robot.)
             SceneStepK sc = *scene;
-            double r_max = 0.0;
-            for (int c = 0; c < robot->coll.ncaps; ++c) r_max = std::max(r_max, (double)robot->desc.cap_r[c]);
-            sc.tile_cull2 = cull_threshold(r_max);
+            sc.tile_cull2 = tile_cull_threshold(robot, 0.f);
             // (dynamic LDS as for the handle form beside it: chain12's 13 capsules are 78 KB in both)
             hipLaunchKernelGGL((full_blocks_kernel<RB, 0, true>), dim3(grid_for(n)), dim3(kBlock), robot->lds_bytes, st, robot->chain,
                                robot->coll, prm, x_in, target, virtual_configs, work_blocks, w2next, sc);
@@ -1812,64 +1888,31 @@ int cppf_scene_workspace_bytes(int n_rows, int n_obs, size_t* bytes) {
 int cppf_scene_env_collisions(const cppf_robot* robot, const float* q, int S, int W, const float* box_lo, const float* box_hi, int n_obs,
                               float reach_m, uint8_t* env_mask, float* min_env, int32_t* nearest_obs, float* obs_min, void* workspace,
                               size_t workspace_bytes, void* stream) {
-    // every argument is checked before the device is selected (CPPF_ENTER), so that the checks hold for a host-only handle too
-    CPPF_REQUIRE(robot != nullptr, "robot handle is NULL");
-    CPPF_REQUIRE(!(robot->life.load(std::memory_order_acquire) & kRobotDead), "the robot handle was destroyed");
-    CPPF_REQUIRE(S >= 0 && W >= 0, "S / W < 0");
     const size_t n = (size_t)S * W;
-    CPPF_REQUIRE(n <= 0x7fffffffu, "S*W exceeds 2^31-1 rows");
-    CPPF_REQUIRE(n_obs >= 0 && n_obs <= CPPF_MAX_SCENE_OBSTACLES, "n_obs out of range (0 .. CPPF_MAX_SCENE_OBSTACLES)");
-    CPPF_REQUIRE(reach_m >= 0.f, "reach_m must be in [0, +inf] (not NaN, not negative)");
-    CPPF_REQUIRE(n == 0 || (q && env_mask), "q / env_mask is NULL");
-    CPPF_REQUIRE(n_obs == 0 || (box_lo && box_hi), "box_lo / box_hi is NULL");
-    CPPF_REQUIRE(workspace, "workspace is NULL");
-    CPPF_REQUIRE(((uintptr_t)workspace & 15u) == 0, "workspace must be 16-byte aligned");
-    size_t need = 0;
-    if (int rc = cppf_scene_workspace_bytes((int)n, n_obs, &need)) return rc;
-    CPPF_REQUIRE(workspace_bytes >= need, "workspace is smaller than cppf_scene_workspace_bytes(S*W, n_obs)");
-    const int d = robot->desc.ndof;
-    if (d < 3) return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: kernels are built for ndof in 3..12");
-    const bool table = use_table(robot);  // (a handle specialised at run time takes the generic form: same bits)
-    const size_t lds = table ? 0 : robot->lds_bytes;
-    if (lds > (size_t)160 * 1024 - 1024)
-        return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: the generic scene kernel cannot stage this many capsules");
+    const auto shape = [&]() -> int {
+        CPPF_REQUIRE(S >= 0 && W >= 0, "S / W < 0");
+        CPPF_REQUIRE(n <= 0x7fffffffu, "S*W exceeds 2^31-1 rows");
+        return CPPF_OK;
+    };
+    size_t lds = 0;
+    if (int rc = check_scene_call(robot, shape, n_obs, reach_m, n == 0 || (q && env_mask), "q / env_mask is NULL", box_lo, box_hi, workspace,
+                                  workspace_bytes, [&](size_t* bytes) { return cppf_scene_workspace_bytes((int)n, n_obs, bytes); },
+                                  "workspace is smaller than cppf_scene_workspace_bytes(S*W, n_obs)", "scene", &lds))
+        return rc;
     CPPF_ENTER(robot);
     hipStream_t st = (hipStream_t)stream;
     if (n == 0 && (n_obs == 0 || !obs_min)) return CPPF_OK;
 
     const bool want_min = min_env || nearest_obs || obs_min;
     SceneK sc;
-    sc.box_lo = box_lo;
-    sc.box_hi = box_hi;
+    sc.cull = scene_cull_setup(robot, box_lo, box_hi, n_obs, want_min ? reach_m : 0.f);
     sc.row_key = static_cast<unsigned long long*>(workspace);
     uint32_t* const obs_key = reinterpret_cast<uint32_t*>(sc.row_key + n);
     sc.obs_key = obs_min ? obs_key : nullptr;
     sc.n = (int)n;
-    sc.n_obs = n_obs;
-    sc.reach = want_min ? reach_m : 0.f;
-    double r_max = 0.0;
-    for (int c = 0; c < CPPF_MAX_CAPSULES; ++c) sc.cull2[c] = 0.f;
-    for (int c = 0; c < robot->coll.ncaps; ++c) {
-        r_max = std::max(r_max, (double)robot->desc.cap_r[c]);
-        // (reach = 0: cull_threshold of the same double sum as cap_cull[c], i.e. cap_cull[c] itself)
-        sc.cull2[c] = cull_threshold(cap_half_length(robot->desc, c) + (double)robot->desc.cap_r[c] + (double)sc.reach);
-    }
-    sc.tile_cull2 = cull_threshold(r_max + (double)sc.reach);
-    // chunks of cuboids (grid.y): enough workgroups for four per compute unit (four wavefronts per SIMD) where the rows alone do not
-    // give them, in groups of 8 cuboids -- a lone wavefront per SIMD issues at a fraction of the rate, and one plan's rows are a
-    // single workgroup (measured: 1 x 256 rows, 64 cuboids, reach = inf, one chunk of 64: 253 us).  A chunk repeats the capsule FK
-    // of its rows, which is small beside 8 cuboids x every capsule.  The result does not depend on the cut (integer min over keys).
     const unsigned row_blocks = grid_for(n);
-    const int groups = (n_obs + 7) / 8;
-    int n_chunks = 1;
-    sc.chunk = 64;
-    if (groups > 0 && row_blocks > 0) {
-        const unsigned want_blocks = 4u * (unsigned)(robot->cu_count > 0 ? robot->cu_count : 256);
-        n_chunks = (int)std::min<unsigned>((unsigned)groups, std::max(1u, (want_blocks + row_blocks - 1) / row_blocks));
-        const int groups_per_chunk = (groups + n_chunks - 1) / n_chunks;
-        n_chunks = (groups + groups_per_chunk - 1) / groups_per_chunk;
-        sc.chunk = groups_per_chunk * 8;
-    }
+    const CuboidChunks cut = cut_cuboid_chunks(robot, row_blocks, n_obs);
+    sc.chunk = cut.chunk;
 
     {
         // (a launch, not a memset node: a captured hipMemsetAsync of this odd byte count did not take effect on replay)
@@ -1880,10 +1923,7 @@ int cppf_scene_env_collisions(const cppf_robot* robot, const float* q, int S, in
         const int rc = for_robot(robot, [&](auto tag) {
             using RB = typename decltype(tag)::type;
             const auto launch = [&](auto kernel) {
-                if (lds > (size_t)64 * 1024)
-                    CPPF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                hipLaunchKernelGGL(kernel, dim3(row_blocks, (unsigned)n_chunks), dim3(kBlock), lds, st, robot->chain, robot->coll, sc, q);
-                return CPPF_OK;
+                return launch_lds(kernel, dim3(row_blocks, (unsigned)cut.n_chunks), lds, st, robot->chain, robot->coll, sc, q);
             };
             return want_min ? launch(&scene_kernel<RB, true>) : launch(&scene_kernel<RB, false>);
         });
@@ -1917,29 +1957,20 @@ int cppf_motion_workspace_bytes(int S, int W, size_t* bytes) {
 int cppf_motion_clearance(const cppf_robot* robot, const float* q, int S, int W, int level, const float* box_lo, const float* box_hi,
                           int n_obs, float reach_m, uint8_t* status, float* min_clear, int32_t* hit_node, float* nodes, void* workspace,
                           size_t workspace_bytes, void* stream) {
-    // every argument is checked before the device is selected (CPPF_ENTER), so that the checks hold for a host-only handle too
-    CPPF_REQUIRE(robot != nullptr, "robot handle is NULL");
-    CPPF_REQUIRE(!(robot->life.load(std::memory_order_acquire) & kRobotDead), "the robot handle was destroyed");
-    CPPF_REQUIRE(S >= 0, "S < 0");
-    CPPF_REQUIRE(W >= 2, "W < 2: a motion needs two waypoints");
-    CPPF_REQUIRE(level >= 0 && level <= CPPF_MOTION_MAX_LEVEL, "level out of range (0 .. CPPF_MOTION_MAX_LEVEL)");
-    const size_t n_nodes = ((size_t)(W - 1) << level) + 1;  // per path
-    CPPF_REQUIRE((size_t)S * (n_nodes + 64) <= 0x7fffffffu, "S * ((W-1) * 2^level + 1) exceeds 2^31-1 nodes");
-    CPPF_REQUIRE(n_obs >= 0 && n_obs <= CPPF_MAX_SCENE_OBSTACLES, "n_obs out of range (0 .. CPPF_MAX_SCENE_OBSTACLES)");
-    CPPF_REQUIRE(reach_m >= 0.f, "reach_m must be in [0, +inf] (not NaN, not negative)");
-    CPPF_REQUIRE(S == 0 || (q && status), "q / status is NULL");
-    CPPF_REQUIRE(n_obs == 0 || (box_lo && box_hi), "box_lo / box_hi is NULL");
-    CPPF_REQUIRE(workspace, "workspace is NULL");
-    CPPF_REQUIRE(((uintptr_t)workspace & 15u) == 0, "workspace must be 16-byte aligned");
-    size_t need = 0;
-    if (int rc = cppf_motion_workspace_bytes(S, W, &need)) return rc;
-    CPPF_REQUIRE(workspace_bytes >= need, "workspace is smaller than cppf_motion_workspace_bytes(S, W)");
-    const int d = robot->desc.ndof;
-    if (d < 3) return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: kernels are built for ndof in 3..12");
-    const bool table = use_table(robot);  // (a handle specialised at run time takes the generic form: same bits)
-    const size_t lds = table ? 0 : robot->lds_bytes;
-    if (lds > (size_t)160 * 1024 - 1024)
-        return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: the generic motion kernel cannot stage this many capsules");
+    size_t n_nodes = 0;  // per path
+    const auto shape = [&]() -> int {
+        CPPF_REQUIRE(S >= 0, "S < 0");
+        CPPF_REQUIRE(W >= 2, "W < 2: a motion needs two waypoints");
+        CPPF_REQUIRE(level >= 0 && level <= CPPF_MOTION_MAX_LEVEL, "level out of range (0 .. CPPF_MOTION_MAX_LEVEL)");
+        n_nodes = ((size_t)(W - 1) << level) + 1;
+        CPPF_REQUIRE((size_t)S * (n_nodes + 64) <= 0x7fffffffu, "S * ((W-1) * 2^level + 1) exceeds 2^31-1 nodes");
+        return CPPF_OK;
+    };
+    size_t lds = 0;
+    if (int rc = check_scene_call(robot, shape, n_obs, reach_m, S == 0 || (q && status), "q / status is NULL", box_lo, box_hi, workspace,
+                                  workspace_bytes, [&](size_t* bytes) { return cppf_motion_workspace_bytes(S, W, bytes); },
+                                  "workspace is smaller than cppf_motion_workspace_bytes(S, W)", "motion", &lds))
+        return rc;
     CPPF_ENTER(robot);
     hipStream_t st = (hipStream_t)stream;
     if (S == 0) return CPPF_OK;
@@ -1947,8 +1978,7 @@ int cppf_motion_clearance(const cppf_robot* robot, const float* q, int S, int W,
 
     const size_t n_tr = (size_t)S * (size_t)(W - 1);
     MotionK mk;
-    mk.box_lo = box_lo;
-    mk.box_hi = box_hi;
+    mk.cull = scene_cull_setup(robot, box_lo, box_hi, n_obs, reach_m);
     mk.rho = reinterpret_cast<const float*>(static_cast<const uint4*>(robot->d_quad) + kQuadTableRecs);
     mk.fail = static_cast<uint32_t*>(workspace);
     mk.clear_key = mk.fail + n_tr;
@@ -1957,39 +1987,17 @@ int cppf_motion_clearance(const cppf_robot* robot, const float* q, int S, int W,
     mk.S = S, mk.W = W, mk.level = level;
     mk.n_nodes = (int)n_nodes;
     mk.waves_per_path = (int)((n_nodes - 1 + 62) / 63);
-    mk.n_obs = n_obs;
     mk.inv_m = 1.f / (float)(1 << level);
-    mk.reach = reach_m;
-    double r_max = 0.0;
-    for (int c = 0; c < CPPF_MAX_CAPSULES; ++c) mk.cull2[c] = 0.f;
-    for (int c = 0; c < robot->coll.ncaps; ++c) {
-        r_max = std::max(r_max, (double)robot->desc.cap_r[c]);
-        mk.cull2[c] = cull_threshold(cap_half_length(robot->desc, c) + (double)robot->desc.cap_r[c] + (double)reach_m);
-    }
-    mk.tile_cull2 = cull_threshold(r_max + (double)reach_m);
-    // chunks of cuboids over grid.y, as cppf_scene_env_collisions cuts them (the result does not depend on the cut)
     const size_t waves = (size_t)S * (size_t)mk.waves_per_path;
     const unsigned wave_blocks = (unsigned)((waves + kBlock / 64 - 1) / (kBlock / 64));
-    const int groups = (n_obs + 7) / 8;
-    int n_chunks = 1;
-    mk.chunk = 64;
-    if (groups > 0) {
-        const unsigned want_blocks = 4u * (unsigned)(robot->cu_count > 0 ? robot->cu_count : 256);
-        n_chunks = (int)std::min<unsigned>((unsigned)groups, std::max(1u, (want_blocks + wave_blocks - 1) / wave_blocks));
-        const int groups_per_chunk = (groups + n_chunks - 1) / n_chunks;
-        n_chunks = (groups + groups_per_chunk - 1) / groups_per_chunk;
-        mk.chunk = groups_per_chunk * 8;
-    }
+    const CuboidChunks cut = cut_cuboid_chunks(robot, wave_blocks, n_obs);
+    mk.chunk = cut.chunk;
 
     const unsigned tr_blocks = (unsigned)((n_tr + 255) / 256);
     hipLaunchKernelGGL(motion_init_kernel, dim3(tr_blocks), dim3(256), 0, st, mk.fail, mk.clear_key, mk.hit, n_tr);
     const int rc = for_robot(robot, [&](auto tag) {
         using RB = typename decltype(tag)::type;
-        const auto kernel = &motion_kernel<RB>;
-        if (lds > (size_t)64 * 1024)
-            CPPF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kernel, dim3(wave_blocks, (unsigned)n_chunks), dim3(kBlock), lds, st, robot->chain, robot->coll, mk, q);
-        return CPPF_OK;
+        return launch_lds(&motion_kernel<RB>, dim3(wave_blocks, (unsigned)cut.n_chunks), lds, st, robot->chain, robot->coll, mk, q);
     });
     if (rc) return rc;
     if (int rc2 = check_launch()) return rc2;
@@ -2014,32 +2022,23 @@ int cppf_motion_resolve(const cppf_robot* robot, const float* q, int S, int W, i
                         const float* box_lo, const float* box_hi, int n_obs, float reach_m, const uint8_t* decided, uint8_t* status,
                         int32_t* depth, int32_t* hit_num, float* min_clear, int32_t* n_tested, void* workspace, size_t workspace_bytes,
                         void* stream) {
-    // every argument is checked before the device is selected (CPPF_ENTER), so that the checks hold for a host-only handle too
-    CPPF_REQUIRE(robot != nullptr, "robot handle is NULL");
-    CPPF_REQUIRE(!(robot->life.load(std::memory_order_acquire) & kRobotDead), "the robot handle was destroyed");
-    CPPF_REQUIRE(S >= 0, "S < 0");
-    CPPF_REQUIRE(W >= 2, "W < 2: a motion needs two waypoints");
-    CPPF_REQUIRE(start_level >= 0 && start_level <= CPPF_MOTION_MAX_LEVEL, "start_level out of range (0 .. CPPF_MOTION_MAX_LEVEL)");
-    CPPF_REQUIRE(max_depth >= start_level && max_depth <= CPPF_MOTION_RESOLVE_MAX_DEPTH,
-                 "max_depth out of range (start_level .. CPPF_MOTION_RESOLVE_MAX_DEPTH)");
-    CPPF_REQUIRE(max_frontier >= (1 << start_level) && max_frontier <= CPPF_MOTION_RESOLVE_MAX_FRONTIER,
-                 "max_frontier out of range (2^start_level .. CPPF_MOTION_RESOLVE_MAX_FRONTIER)");
-    CPPF_REQUIRE((size_t)S * (size_t)(W - 1) <= 0x7fffffffu, "S * (W-1) exceeds 2^31-1 transitions");
-    CPPF_REQUIRE(n_obs >= 0 && n_obs <= CPPF_MAX_SCENE_OBSTACLES, "n_obs out of range (0 .. CPPF_MAX_SCENE_OBSTACLES)");
-    CPPF_REQUIRE(reach_m >= 0.f, "reach_m must be in [0, +inf] (not NaN, not negative)");
-    CPPF_REQUIRE(S == 0 || (q && status), "q / status is NULL");
-    CPPF_REQUIRE(n_obs == 0 || (box_lo && box_hi), "box_lo / box_hi is NULL");
-    CPPF_REQUIRE(workspace, "workspace is NULL");
-    CPPF_REQUIRE(((uintptr_t)workspace & 15u) == 0, "workspace must be 16-byte aligned");
-    size_t need = 0;
-    if (int rc = cppf_motion_resolve_workspace_bytes(S, W, max_frontier, &need)) return rc;
-    CPPF_REQUIRE(workspace_bytes >= need, "workspace is smaller than cppf_motion_resolve_workspace_bytes(S, W, max_frontier)");
-    const int d = robot->desc.ndof;
-    if (d < 3) return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: kernels are built for ndof in 3..12");
-    const bool table = use_table(robot);  // (a handle specialised at run time takes the generic form: same bits)
-    const size_t lds = table ? 0 : robot->lds_bytes;
-    if (lds > (size_t)160 * 1024 - 1024)
-        return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: the generic motion kernel cannot stage this many capsules");
+    const auto shape = [&]() -> int {
+        CPPF_REQUIRE(S >= 0, "S < 0");
+        CPPF_REQUIRE(W >= 2, "W < 2: a motion needs two waypoints");
+        CPPF_REQUIRE(start_level >= 0 && start_level <= CPPF_MOTION_MAX_LEVEL, "start_level out of range (0 .. CPPF_MOTION_MAX_LEVEL)");
+        CPPF_REQUIRE(max_depth >= start_level && max_depth <= CPPF_MOTION_RESOLVE_MAX_DEPTH,
+                     "max_depth out of range (start_level .. CPPF_MOTION_RESOLVE_MAX_DEPTH)");
+        CPPF_REQUIRE(max_frontier >= (1 << start_level) && max_frontier <= CPPF_MOTION_RESOLVE_MAX_FRONTIER,
+                     "max_frontier out of range (2^start_level .. CPPF_MOTION_RESOLVE_MAX_FRONTIER)");
+        CPPF_REQUIRE((size_t)S * (size_t)(W - 1) <= 0x7fffffffu, "S * (W-1) exceeds 2^31-1 transitions");
+        return CPPF_OK;
+    };
+    size_t lds = 0;
+    if (int rc = check_scene_call(robot, shape, n_obs, reach_m, S == 0 || (q && status), "q / status is NULL", box_lo, box_hi, workspace,
+                                  workspace_bytes,
+                                  [&](size_t* bytes) { return cppf_motion_resolve_workspace_bytes(S, W, max_frontier, bytes); },
+                                  "workspace is smaller than cppf_motion_resolve_workspace_bytes(S, W, max_frontier)", "motion", &lds))
+        return rc;
     CPPF_ENTER(robot);
     hipStream_t st = (hipStream_t)stream;
     if (S == 0) return CPPF_OK;
@@ -2047,8 +2046,7 @@ int cppf_motion_resolve(const cppf_robot* robot, const float* q, int S, int W, i
 
     const size_t n_tr = (size_t)S * (size_t)(W - 1);
     ResolveK rk;
-    rk.box_lo = box_lo;
-    rk.box_hi = box_hi;
+    rk.cull = scene_cull_setup(robot, box_lo, box_hi, n_obs, reach_m);
     rk.rho = reinterpret_cast<const float*>(static_cast<const uint4*>(robot->d_quad) + kQuadTableRecs);
     rk.decided = decided;
     rk.status = status;
@@ -2058,23 +2056,10 @@ int cppf_motion_resolve(const cppf_robot* robot, const float* q, int S, int W, i
     rk.n_tested = n_tested;
     rk.frontier = static_cast<uint32_t*>(workspace);
     rk.S = S, rk.W = W, rk.start_level = start_level, rk.max_depth = max_depth, rk.max_frontier = max_frontier;
-    rk.n_obs = n_obs;
-    rk.reach = reach_m;
-    double r_max = 0.0;
-    for (int c = 0; c < CPPF_MAX_CAPSULES; ++c) rk.cull2[c] = 0.f;
-    for (int c = 0; c < robot->coll.ncaps; ++c) {
-        r_max = std::max(r_max, (double)robot->desc.cap_r[c]);
-        rk.cull2[c] = cull_threshold(cap_half_length(robot->desc, c) + (double)robot->desc.cap_r[c] + (double)reach_m);
-    }
-    rk.tile_cull2 = cull_threshold(r_max + (double)reach_m);
     const unsigned blocks = (unsigned)((n_tr + kBlock / 64 - 1) / (kBlock / 64));  // one wavefront per transition
     const int rc = for_robot(robot, [&](auto tag) {
         using RB = typename decltype(tag)::type;
-        const auto kernel = &motion_resolve_kernel<RB>;
-        if (lds > (size_t)64 * 1024)
-            CPPF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), lds, st, robot->chain, robot->coll, rk, q);
-        return CPPF_OK;
+        return launch_lds(&motion_resolve_kernel<RB>, dim3(blocks), lds, st, robot->chain, robot->coll, rk, q);
     });
     if (rc) return rc;
     return check_launch();

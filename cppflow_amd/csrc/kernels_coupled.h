@@ -294,9 +294,8 @@ constexpr int full_blocks_occ() {
 // segment.  Environment rows of row r: for o = 0 .. n_obs-1 ascending, c = 0 .. ncaps-1 ascending, the same cull_far / seg_box_closest /
 // point_grad / rank1 with the same operands as the loop over co.obs_lo -- a (capsule, cuboid) pair contributes only when it
 // penetrates, so a cuboid that penetrates nothing adds not even a "+ 0", and whenever a handle can hold the penetrating cuboids (in
-// ascending order) the two forms give the same block bit for bit.  In front of it the culling of scene_kernel: 64 cuboids per tile,
-// one per lane, against the wavefront's box (every capsule segment of every row of the wavefront, mask-only threshold: reach = 0), a
-// ballot, a wave-uniform loop over the survivors with their corners broadcast by v_readlane.  A culled cuboid is further than
+// ascending order) the two forms give the same block bit for bit.  In front of it the culling of scene_kernel, by its own scene_walk
+// (kernels_scene.h, "Shape"; mask-only threshold: reach = 0, per capsule co.cap_cull).  A culled cuboid is further than
 // r_max + 1 cm from every segment of the wavefront and cannot penetrate, so the culling changes no bit.  The tile test needs all 64
 // lanes: a lane past the last row stays, works on a copy of the last row and stores nothing (as in scene_kernel); the gate argument
 // does not exist in this form (its place in the argument list holds the scene).
@@ -314,25 +313,6 @@ template <>
 struct FullBlocksTail<true> {
     using type = SceneStepK;
 };
-
-// bit set of the lanes whose cuboid (base + lane, corners loaded into llo / lhi) may come within the tile threshold of the box
-__device__ __forceinline__ unsigned long long scene_step_tile(const SceneStepK& sc, int base, int lane, const float (&blo)[3],
-                                                              const float (&bhi)[3], float (&llo)[3], float (&lhi)[3]) {
-    const int ol = base + lane;
-    const bool have = ol < sc.n_obs;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        llo[k] = have ? sc.box_lo[(size_t)ol * 3 + k] : 0.f;
-        lhi[k] = have ? sc.box_hi[(size_t)ol * 3 + k] : 0.f;
-    }
-    float g2 = 0.f;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float g = fmaxf(fmaxf(llo[k] - bhi[k], blo[k] - lhi[k]), 0.f);
-        g2 = CPPF_FMA(g, g, g2);
-    }
-    return __builtin_amdgcn_ballot_w64(have && !(g2 > sc.tile_cull2));
-}
 
 template <class RB, int OCC = 0, bool SCENE = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(OCC ? OCC : 1, OCC ? OCC : 8))) void full_blocks_kernel(const ChainK ch, const CollK co, const FullK prm,
@@ -375,23 +355,21 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(OCC ? OC
         if constexpr (SCENE) scene_env = prm.use_env && gate.n_obs > 0;
         if (env_bits || !prm.use_env || (SCENE && !scene_env)) near_env = 0ull;
         if (prm.use_self || env_bits || scene_env) {
-            float R[9], p[3], wc[L][3], wh[L][3];
-            capsule_fk_static<RB>(rb, q, R, p, wc, wh);
+            float R[9], p[3];
+            LaneCaps<RB, true> caps(co, tid);
+            caps.fk(rb, co, q, R, p);
+            const float(&wc)[L][3] = caps.wc, (&wh)[L][3] = caps.wh;
             if constexpr (SCENE) {
                 if (scene_env) {
-                    float blo[3] = {INFINITY, INFINITY, INFINITY}, bhi[3] = {-INFINITY, -INFINITY, -INFINITY};
-#pragma unroll
-                    for (int c = 0; c < T::L; ++c) box_add_segment(wc[c], wh[c], blo, bhi);
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) {
-                        blo[k] = wave_min(blo[k]);
-                        bhi[k] = wave_max(bhi[k]);
-                    }
+                    float blo[3], bhi[3];
+                    capsule_box(caps, blo, bhi);
+                    wave_box_reduce(blo, bhi);
                     static_assert(CPPF_MAX_SCENE_OBSTACLES <= 64 * 64, "one bit of near_env per tile of 64 cuboids");
                     near_env = 0ull;
                     for (int base = 0; base < gate.n_obs; base += 64) {
                         float llo[3], lhi[3];
-                        if (scene_step_tile(gate, base, tid & 63, blo, bhi, llo, lhi) != 0ull) near_env |= 1ull << (base >> 6);
+                        if (scene_tile(gate.box_lo, gate.box_hi, gate.n_obs, gate.tile_cull2, base, tid & 63, blo, bhi, llo, lhi) != 0ull)
+                            near_env |= 1ull << (base >> 6);
                     }
                 }
             }
@@ -514,49 +492,33 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(OCC ? OC
     if constexpr (SCENE) {
         if (prm.use_env && near_env != 0ull && gate.n_obs > 0) {  // :685-727 over the scene
             const float w = prm.a_env * prm.a_env;
-            const int lane = tid & 63;
-            // the wavefront's box: every capsule segment of every row of the wavefront (all 64 lanes are here)
-            float blo[3] = {INFINITY, INFINITY, INFINITY}, bhi[3] = {-INFINITY, -INFINITY, -INFINITY};
-            for (int c = 0; c < co.ncaps; ++c) {
-                float wc[3], wh[3];
-                lds_capsule(lds, tid, c, wc, wh);
-                box_add_segment(wc, wh, blo, bhi);
-            }
+            // the wavefront's box over the capsules this pass staged in LDS (all 64 lanes are here)
+            const LaneCaps<RB, false> caps(co, tid);
+            float blo[3], bhi[3];
+            capsule_box(caps, blo, bhi);
+            wave_box_reduce(blo, bhi);
+            // (a tile the pre-screen's box test left empty holds nothing that can penetrate; the generic form: all ones)
+            const auto near = [&](int base) { return ((near_env >> ((base >> 6) & 63)) & 1ull) != 0ull; };
+            scene_walk(gate.box_lo, gate.box_hi, 0, gate.n_obs, gate.tile_cull2, tid & 63, blo, bhi, near,
+                       [&](int, const float (&lo)[3], const float (&hi)[3]) {
+                caps.each([&](const auto& cap) {
+                    float cs[3], cb[3];
+                    if (cull_far(point_box_dist2(cap.wc, lo, hi), co.cap_cull[cap.c])) return;
+                    const float sd = seg_box_closest(cap.wc, cap.wh, lo, hi, cs, cb);
+                    const float dist = sd - cap.r();
+                    if (dist < 0.f) {
+                        float nrm[3] = {0.f, 0.f, 0.f}, g[D];
+                        if (sd > kTouch) {
 #pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                blo[k] = wave_min(blo[k]);
-                bhi[k] = wave_max(bhi[k]);
-            }
-            for (int base = 0; base < gate.n_obs; base += 64) {
-                // (a tile the pre-screen's box test left empty holds nothing that can penetrate; the generic form: all ones)
-                if (!((near_env >> ((base >> 6) & 63)) & 1ull)) continue;
-                float llo[3], lhi[3];
-                unsigned long long live = scene_step_tile(gate, base, lane, blo, bhi, llo, lhi);
-                while (live != 0ull) {  // the survivors, cuboids ascending, for the whole wavefront
-                    const int j = __builtin_ctzll(live);
-                    live &= live - 1ull;
-                    const float lo[3] = {readlane_f(llo[0], j), readlane_f(llo[1], j), readlane_f(llo[2], j)};
-                    const float hi[3] = {readlane_f(lhi[0], j), readlane_f(lhi[1], j), readlane_f(lhi[2], j)};
-                    for (int c = 0; c < co.ncaps; ++c) {
-                        float wc[3], wh[3], cs[3], cb[3];
-                        lds_capsule(lds, tid, c, wc, wh);
-                        if (cull_far(point_box_dist2(wc, lo, hi), co.cap_cull[c])) continue;
-                        const float sd = seg_box_closest(wc, wh, lo, hi, cs, cb);
-                        const float dist = sd - co.cap_r[c];
-                        if (dist < 0.f) {
-                            float nrm[3] = {0.f, 0.f, 0.f}, g[D];
-                            if (sd > kTouch) {
-#pragma unroll
-                                for (int i = 0; i < 3; ++i) nrm[i] = (cs[i] - cb[i]) / sd;
-                            }
-#pragma unroll
-                            for (int j2 = 0; j2 < D; ++j2) g[j2] = 0.f;
-                            point_grad<RB>(rb, co.cap_link[c], nrm, cs, ax, og, 1.f, g);
-                            rank1<D>(M, m, g, w, -w * dist);
+                            for (int i = 0; i < 3; ++i) nrm[i] = (cs[i] - cb[i]) / sd;
                         }
+#pragma unroll
+                        for (int j2 = 0; j2 < D; ++j2) g[j2] = 0.f;
+                        point_grad<RB>(rb, cap.link(), nrm, cs, ax, og, 1.f, g);
+                        rank1<D>(M, m, g, w, -w * dist);
                     }
-                }
-            }
+                });
+            });
         }
         if (!valid) return;
     }

@@ -1,7 +1,8 @@
 // kernels_motion.h -- certifying the MOTION between the waypoints of q [S, W, d] collision-free (cppf_motion_clearance): the
 // adaptive-clearance test of Schwarzer, Saha and Latombe on 2^level equal intervals per transition, against the robot's self pairs
 // and a scene of up to CPPF_MAX_SCENE_OBSTACLES axis-aligned cuboids in DEVICE memory.  Included inside the anonymous namespace of
-// cppflow_hip.hip behind kernels_scene.h, whose keys, wavefront box and broadcast helpers it shares; gfx950 only.
+// cppflow_hip.hip behind kernels_scene.h, whose keys, capsule iterator, wavefront box and scene_walk it shares; gfx950 only.
+// motion_self, motion_far_fails and motion_node_test below are the ONE definition of a node's test, for motion_resolve_kernel too.
 //
 // Definition.
 //   Nodes.  Transition t of path s goes from a = q[s,t] to b = q[s,t+1] on the straight line in the STORED joint values (no wrapping:
@@ -28,9 +29,9 @@
 // M of one transition and node 0 of the next: the same bits), so an interval's partner is the neighbouring lane -- one __shfl_down
 // per compared value.  Consecutive wavefronts overlap by one node: wavefront k of a path holds nodes 63 k .. 63 k + 63 and decides
 // the 63 intervals between them, so a wavefront needs nobody else (no LDS exchange, no barrier).  Lanes past the last node work on a
-// copy of it and store nothing.  The cuboids are cut into chunks over grid.y and walked as in scene_kernel: 64 cuboids per tile
-// against the wavefront's box, a ballot, the wave-uniform survivor loop with v_readlane corners, cull_far, then the exact test -- and
-// the interval comparison inside that loop, per (capsule, survivor).  Chunk 0 also does the self pairs and the joint limits.
+// copy of it and store nothing.  The cuboids are cut into chunks over grid.y and walked by scene_walk (kernels_scene.h, "Shape");
+// its callback does cull_far, the exact test and the interval comparison, per (capsule, survivor).  Chunk 0 also does the self
+// pairs and the joint limits.
 // Culling.  A culled cuboid has a clearance >= reach at every node of the wavefront, i.e. the truncated value reach itself: its
 // intervals stand or fall by  (reach + reach) - lambda_c / M > 1e-6  alone.  Rounding is monotone, so where that fails every cuboid
 // fails for capsule c, culled or not, and where it holds a culled cuboid passes: the test is made ONCE per capsule ahead of the
@@ -43,19 +44,15 @@
 #pragma once
 
 struct MotionK {
-    const float* box_lo;  // DEVICE [n_obs, 3] world-frame corners
-    const float* box_hi;
+    SceneCullK cull;      // the scene and its culling thresholds (kernels_scene.h)
     const float* rho;     // DEVICE [CPPF_MAX_DOF][CPPF_MAX_CAPSULES] (the handle's table)
     uint32_t* fail;       // workspace [S (W-1)]: non-zero = some interval of the transition is not certified
     uint32_t* clear_key;  // workspace [S (W-1)]: scene_key of the smallest node clearance
     int32_t* hit;         // workspace [S (W-1)]: the lowest node with a negative clearance (INT32_MAX: none)
     float* nodes;         // [S, W-1, M+1, d] or NULL
     int32_t S, W, level, n_nodes, waves_per_path;  // n_nodes = (W-1) 2^level + 1 per path; ceil((n_nodes - 1) / 63) wavefronts
-    int32_t n_obs, chunk;                          // chunk: cuboids per blockIdx.y, a multiple of 8
+    int32_t chunk;                                 // cuboids per blockIdx.y, a multiple of 8
     float inv_m;                                   // 2^-level
-    float reach;
-    float tile_cull2;                 // as SceneK
-    float cull2[CPPF_MAX_CAPSULES];
 };
 
 constexpr float kMotionSlack = 1e-6f;
@@ -76,35 +73,111 @@ __device__ __forceinline__ float motion_lambda(const float* __restrict__ rho, co
     return lam;
 }
 
+// lambda_p of the self pair of capsules a, b on the links la, lb: the joints between the two links, the further capsule's bounds
+template <int D>
+__device__ __forceinline__ float motion_pair_lambda(const float* __restrict__ rho, const float (&dq)[D], int la, int lb, int a, int b) {
+    return la <= lb ? motion_lambda<D>(rho, dq, la, lb, b) : motion_lambda<D>(rho, dq, lb, la, a);
+}
+
 // the self pairs [B, E) of a generated table: capsule and link ids are compile-time.  Ranges of more than 24 pairs are halved: one
 // fully unrolled loop over all 55 pairs of Chain12 is beyond what the compiler unrolls, and a loop it leaves rolled indexes the
 // capsules' registers at run time
 template <class RB, int B, int E>
-__device__ __forceinline__ void motion_self_static(const float (&wc)[SceneCaps<RB>::L][3], const float (&wh)[SceneCaps<RB>::L][3],
-                                                   const float* __restrict__ rho, const float (&dq)[RB::D], float inv_m, float& m,
-                                                   int& fail) {
+__device__ __forceinline__ void motion_self_static(const LaneCaps<RB, true>& caps, const float* __restrict__ rho,
+                                                   const float (&dq)[RB::D], float inv_m, float& m, int& fail) {
     if constexpr (E - B > 24) {
-        motion_self_static<RB, B, (B + E) / 2>(wc, wh, rho, dq, inv_m, m, fail);
-        motion_self_static<RB, (B + E) / 2, E>(wc, wh, rho, dq, inv_m, m, fail);
+        motion_self_static<RB, B, (B + E) / 2>(caps, rho, dq, inv_m, m, fail);
+        motion_self_static<RB, (B + E) / 2, E>(caps, rho, dq, inv_m, m, fail);
     } else {
         using T = typename RB::Table;
 #pragma unroll
         for (int pi = B; pi < E; ++pi) {
             const int a = T::pair_a[pi], b = T::pair_b[pi];
-            const float d2 = seg_seg_dist2(wc[a], wh[a], wc[b], wh[b], T::cap_a[a], T::cap_ia[a], T::cap_a[b], T::cap_ia[b]);
+            const float d2 = seg_seg_dist2(caps.wc[a], caps.wh[a], caps.wc[b], caps.wh[b], T::cap_a[a], T::cap_ia[a], T::cap_a[b], T::cap_ia[b]);
             const float v = __builtin_sqrtf(d2) - (T::cap_r[a] + T::cap_r[b]);
             m = v < m ? v : m;
-            const int la = T::cap_link[a], lb = T::cap_link[b];
-            const float lam = la <= lb ? motion_lambda<RB::D>(rho, dq, la, lb, b) : motion_lambda<RB::D>(rho, dq, lb, la, a);
-            fail |= motion_interval_fails(v, lam, inv_m);
+            fail |= motion_interval_fails(v, motion_pair_lambda<RB::D>(rho, dq, T::cap_link[a], T::cap_link[b], a, b), inv_m);
         }
+    }
+}
+// every self pair of this lane's node: the generated table's, or CollK's over the capsules in LDS
+template <class RB>
+__device__ __forceinline__ void motion_self(const LaneCaps<RB>& caps, const float* __restrict__ rho, const float (&dq)[RB::D],
+                                            float inv_m, float& m, int& fail) {
+    if constexpr (RB::kStatic) {
+        motion_self_static<RB, 0, RB::Table::P>(caps, rho, dq, inv_m, m, fail);
+    } else {
+        extern __shared__ float lds[];
+        const CollK& co = caps.co;
+        for (int pi = 0; pi < co.npairs; ++pi) {
+            const int a = co.pair_a[pi], b = co.pair_b[pi];
+            float ca[3], ha[3], cb[3], hb[3];
+            lds_capsule(lds, caps.tid, a, ca, ha);
+            lds_capsule(lds, caps.tid, b, cb, hb);
+            const float d2 = seg_seg_dist2(ca, ha, cb, hb, co.cap_a[a], co.cap_ia[a], co.cap_a[b], co.cap_ia[b]);
+            const float v = __builtin_sqrtf(d2) - (co.cap_r[a] + co.cap_r[b]);
+            m = v < m ? v : m;
+            fail |= motion_interval_fails(v, motion_pair_lambda<RB::D>(rho, dq, co.cap_link[a], co.cap_link[b], a, b), inv_m);
+        }
+    }
+}
+
+// lambda_c of every capsule against a cuboid.  The specialised form keeps them (slam); the generic one forms each where it is used.
+template <class RB>
+__device__ __forceinline__ void motion_cuboid_lambdas(const float* __restrict__ rho, const float (&dq)[RB::D],
+                                                      float (&slam)[LaneCaps<RB>::L]) {
+    if constexpr (RB::kStatic) {
+        using T = typename RB::Table;
+#pragma unroll
+        for (int c = 0; c < T::L; ++c) slam[c] = motion_lambda<RB::D>(rho, dq, -1, T::cap_link[c], c);
+    }
+}
+template <class RB, class Cap>
+__device__ __forceinline__ float motion_cuboid_lambda(const float* __restrict__ rho, const float (&dq)[RB::D],
+                                                      const float (&slam)[LaneCaps<RB>::L], const Cap& cap) {
+    if constexpr (RB::kStatic)
+        return slam[cap.c];
+    else
+        return motion_lambda<RB::D>(rho, dq, -1, cap.link(), cap.c);
+}
+
+// every cuboid the culling skips (see "Culling"): reach at both ends of the interval.  Depends on the level alone, not on a node:
+// a caller evaluates it once and ORs it into the verdict of every interval (whenever the scene holds a cuboid at all).
+template <class RB>
+__device__ __forceinline__ int motion_far_fails(const LaneCaps<RB>& caps, const float* __restrict__ rho, const float (&dq)[RB::D],
+                                                const float (&slam)[LaneCaps<RB>::L], float reach, float inv_m) {
+    int fail = 0;
+    caps.each([&](const auto& cap) { fail |= !((reach + reach) - motion_cuboid_lambda<RB>(rho, dq, slam, cap) * inv_m > kMotionSlack); });
+    return fail;
+}
+
+// This lane's node (its capsules in `caps`, their box in blo / bhi, not yet reduced) against the self pairs (where `self`) and the
+// cuboids [o_begin, o_end) of the scene: its smallest clearance into m, the verdict of its interval ORed into fail -- which the
+// caller seeds with motion_far_fails.  The ONE definition of the node test: motion_kernel and motion_resolve_kernel agree bit for
+// bit because both call it.
+template <class RB>
+__device__ __forceinline__ void motion_node_test(const LaneCaps<RB>& caps, const SceneCullK& sc, const float* __restrict__ rho,
+                                                 const float (&dq)[RB::D], const float (&slam)[LaneCaps<RB>::L], float inv_m, bool self,
+                                                 int o_begin, int o_end, int lane, float (&blo)[3], float (&bhi)[3], float& m, int& fail) {
+    if (self) motion_self<RB>(caps, rho, dq, inv_m, m, fail);
+    if (sc.n_obs > 0) {
+        wave_box_reduce(blo, bhi);
+        float best = INFINITY;
+        scene_walk(sc, o_begin, o_end, lane, blo, bhi, [&](int, const float (&lo)[3], const float (&hi)[3]) {
+            caps.each([&](const auto& cap) {
+                if (cull_far(point_box_dist2(cap.wc, lo, hi), sc.cull2[cap.c])) return;
+                const float v = __builtin_sqrtf(seg_box_dist2(cap.wc, cap.wh, lo, hi)) - cap.r();
+                best = v < best ? v : best;
+                fail |= motion_interval_fails(v < sc.reach ? v : sc.reach, motion_cuboid_lambda<RB>(rho, dq, slam, cap), inv_m);
+            });
+        });
+        if (best < sc.reach) m = best < m ? best : m;  // (min_env as the scene kernel reports it: nothing beyond reach)
     }
 }
 
 template <class RB>
 __global__ __launch_bounds__(kBlock, CPPF_WAVES_COLL) void motion_kernel(const ChainK ch, const CollK co, const MotionK mk,
                                                                           const float* __restrict__ q) {
-    extern __shared__ float lds[];
     constexpr int D_ = RB::D;
     const RB rb{ch, co};
     const int tid = threadIdx.x, lane = tid & 63;
@@ -121,7 +194,7 @@ __global__ __launch_bounds__(kBlock, CPPF_WAVES_COLL) void motion_kernel(const C
     const bool has_interval = lane < 63 && g0 < last;
     const size_t tr = (size_t)s * (size_t)(mk.W - 1) + (size_t)t;
 
-    float x[D_], dq[D_], R[9], p[3];
+    float x[D_], dq[D_];
     int outside = 0;
     {
         float a[D_], b[D_];
@@ -147,113 +220,22 @@ __global__ __launch_bounds__(kBlock, CPPF_WAVES_COLL) void motion_kernel(const C
         }
     }
 
-    constexpr int LS = SceneCaps<RB>::L;
-    float swc[LS][3], swh[LS][3];
-    float blo[3] = {INFINITY, INFINITY, INFINITY}, bhi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    if constexpr (RB::kStatic) {
-        capsule_fk_static<RB>(rb, x, R, p, swc, swh);
-#pragma unroll
-        for (int c = 0; c < RB::Table::L; ++c) box_add_segment(swc[c], swh[c], blo, bhi);
-    } else {
-        fk_capsules_to_lds<RB>(rb, co, x, lds, tid, R, p);
-        for (int c = 0; c < co.ncaps; ++c) {
-            float wc[3], wh[3];
-            lds_capsule(lds, tid, c, wc, wh);
-            box_add_segment(wc, wh, blo, bhi);
-        }
-    }
+    LaneCaps<RB> caps(co, tid);
+    float R[9], p[3], blo[3], bhi[3];
+    wave_capsule_box<RB>(rb, co, x, caps, R, p, blo, bhi);
 
+    // every chunk: the far-cuboid rule; chunk 0 also the joint limits and the self pairs
     int fail = 0;
     float m = INFINITY;  // the node's smallest clearance, untruncated
-    // ---- chunk 0: joint limits and the self pairs ----------------------------------------------------------------------------------
-    if (blockIdx.y == 0) {
-        fail |= outside;
-        if constexpr (RB::kStatic) {
-            motion_self_static<RB, 0, RB::Table::P>(swc, swh, mk.rho, dq, mk.inv_m, m, fail);
-        } else {
-            for (int pi = 0; pi < co.npairs; ++pi) {
-                const int a = co.pair_a[pi], b = co.pair_b[pi];
-                float ca[3], ha[3], cb[3], hb[3];
-                lds_capsule(lds, tid, a, ca, ha);
-                lds_capsule(lds, tid, b, cb, hb);
-                const float d2 = seg_seg_dist2(ca, ha, cb, hb, co.cap_a[a], co.cap_ia[a], co.cap_a[b], co.cap_ia[b]);
-                const float v = __builtin_sqrtf(d2) - (co.cap_r[a] + co.cap_r[b]);
-                m = v < m ? v : m;
-                const int la = co.cap_link[a], lb = co.cap_link[b];
-                const float lam = la <= lb ? motion_lambda<D_>(mk.rho, dq, la, lb, b) : motion_lambda<D_>(mk.rho, dq, lb, la, a);
-                fail |= motion_interval_fails(v, lam, mk.inv_m);
-            }
-        }
+    float slam[LaneCaps<RB>::L];
+    if (mk.cull.n_obs > 0) {
+        motion_cuboid_lambdas<RB>(mk.rho, dq, slam);
+        fail |= motion_far_fails<RB>(caps, mk.rho, dq, slam, mk.cull.reach, mk.inv_m);
     }
-
-    // ---- this chunk's cuboids ------------------------------------------------------------------------------------------------------
-    if (mk.n_obs > 0) {
-#pragma unroll
-        for (int kk = 0; kk < 3; ++kk) {
-            blo[kk] = wave_min(blo[kk]);
-            bhi[kk] = wave_max(bhi[kk]);
-        }
-        // every cuboid the culling skips (see "Culling"): reach at both ends of the interval
-        float slam[LS];  // (the specialised form keeps lambda_c; the generic one forms it again per survivor)
-        if constexpr (RB::kStatic) {
-            using T = typename RB::Table;
-#pragma unroll
-            for (int c = 0; c < T::L; ++c) {
-                slam[c] = motion_lambda<D_>(mk.rho, dq, -1, T::cap_link[c], c);
-                fail |= !((mk.reach + mk.reach) - slam[c] * mk.inv_m > kMotionSlack);
-            }
-        } else {
-            for (int c = 0; c < co.ncaps; ++c)
-                fail |= !((mk.reach + mk.reach) - motion_lambda<D_>(mk.rho, dq, -1, co.cap_link[c], c) * mk.inv_m > kMotionSlack);
-        }
-        const int o_begin = (int)blockIdx.y * mk.chunk;
-        const int o_end = min(mk.n_obs, o_begin + mk.chunk);
-        float best = INFINITY;
-        for (int base = o_begin; base < o_end; base += 64) {
-            const int ol = base + lane;
-            const bool have = ol < o_end;
-            float llo[3], lhi[3];
-#pragma unroll
-            for (int kk = 0; kk < 3; ++kk) {
-                llo[kk] = have ? mk.box_lo[(size_t)ol * 3 + kk] : 0.f;
-                lhi[kk] = have ? mk.box_hi[(size_t)ol * 3 + kk] : 0.f;
-            }
-            float g2 = 0.f;
-#pragma unroll
-            for (int kk = 0; kk < 3; ++kk) {
-                const float gg = fmaxf(fmaxf(llo[kk] - bhi[kk], blo[kk] - lhi[kk]), 0.f);
-                g2 = CPPF_FMA(gg, gg, g2);
-            }
-            unsigned long long live = __builtin_amdgcn_ballot_w64(have && !(g2 > mk.tile_cull2));
-            while (live != 0ull) {
-                const int jj = __builtin_ctzll(live);
-                live &= live - 1ull;
-                const float lo[3] = {readlane_f(llo[0], jj), readlane_f(llo[1], jj), readlane_f(llo[2], jj)};
-                const float hi[3] = {readlane_f(lhi[0], jj), readlane_f(lhi[1], jj), readlane_f(lhi[2], jj)};
-                if constexpr (RB::kStatic) {
-                    using T = typename RB::Table;
-#pragma unroll
-                    for (int c = 0; c < T::L; ++c) {
-                        if (cull_far(point_box_dist2(swc[c], lo, hi), mk.cull2[c])) continue;
-                        const float v = __builtin_sqrtf(seg_box_dist2(swc[c], swh[c], lo, hi)) - T::cap_r[c];
-                        best = v < best ? v : best;
-                        fail |= motion_interval_fails(v < mk.reach ? v : mk.reach, slam[c], mk.inv_m);
-                    }
-                } else {
-                    for (int c = 0; c < co.ncaps; ++c) {
-                        float wc[3], wh[3];
-                        lds_capsule(lds, tid, c, wc, wh);
-                        if (cull_far(point_box_dist2(wc, lo, hi), mk.cull2[c])) continue;
-                        const float v = __builtin_sqrtf(seg_box_dist2(wc, wh, lo, hi)) - co.cap_r[c];
-                        best = v < best ? v : best;
-                        const float lam = motion_lambda<D_>(mk.rho, dq, -1, co.cap_link[c], c);
-                        fail |= motion_interval_fails(v < mk.reach ? v : mk.reach, lam, mk.inv_m);
-                    }
-                }
-            }
-        }
-        if (best < mk.reach) m = best < m ? best : m;  // (min_env as the scene kernel reports it: nothing beyond reach)
-    }
+    if (blockIdx.y == 0) fail |= outside;
+    const int o_begin = (int)blockIdx.y * mk.chunk;
+    motion_node_test<RB>(caps, mk.cull, mk.rho, dq, slam, mk.inv_m, blockIdx.y == 0, o_begin, min(mk.cull.n_obs, o_begin + mk.chunk), lane,
+                         blo, bhi, m, fail);
 
     // ---- meet the other lanes, wavefronts and chunks of the transition ------------------------------------------------------------------
     // (a lane past the end holds a copy of the last node: what it adds to a minimum the last node adds as well)

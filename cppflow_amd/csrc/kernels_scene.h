@@ -1,5 +1,12 @@
 // kernels_scene.h -- obstacle scenes: all rows against up to CPPF_MAX_SCENE_OBSTACLES axis-aligned cuboids held in DEVICE memory
-// (cppf_scene_env_collisions).  Included inside the anonymous namespace of cppflow_hip.hip; gfx950 only.
+// (cppf_scene_env_collisions), and what EVERY kernel that tests capsules against such a scene shares -- the coupled step's scene form
+// (kernels_coupled.h) and the two motion kernels (kernels_motion.h, kernels_motion_resolve.h) include behind this file:
+//   SceneCullK        the scene and its culling thresholds (host: scene_cull_setup)
+//   LaneCaps          this lane's capsules behind one loop, generated table + registers or CollK + LDS
+//   wave_capsule_box  capsule FK, then the lane's box; wave_box_reduce makes it the wavefront's
+//   scene_tile        "Shape" 1. below;   scene_walk  the tile loop and "Shape" 2.: f(o, lo, hi) per surviving cuboid, ascending
+// The arguments "Shape", "Culling" (the truncation at reach) and "Combining" are stated here once; the other files refer to them.
+// Included inside the anonymous namespace of cppflow_hip.hip; gfx950 only.
 //
 // Every number is the one collide_*<WANT_MIN = true> produces for a (row, capsule, cuboid): the capsule FK is fk_capsules_to_lds /
 // capsule_fk_static, the distance sqrt_rn(seg_box_dist2) - cap_r[c], the mask-only form d2 < cap_thr[c].  With
@@ -31,15 +38,21 @@
 // another.
 #pragma once
 
-struct SceneK {
+// the culling arguments of a walk over a scene (scene_cull_setup in cppflow_hip.hip fills them); embedded in SceneK, MotionK, ResolveK
+struct SceneCullK {
     const float* box_lo;  // DEVICE [n_obs, 3] world-frame corners
     const float* box_hi;
+    int32_t n_obs;
+    float reach;                     // (0 for a mask-only launch)
+    float tile_cull2;                // (r_max + reach + 1 cm)^2 (1 + 1e-4), rounded up: wavefront box vs cuboid
+    float cull2[CPPF_MAX_CAPSULES];  // (h + r + reach + 1 cm)^2 (1 + 1e-4), rounded up: capsule centre vs cuboid
+};
+
+struct SceneK {
+    SceneCullK cull;
     unsigned long long* row_key;  // workspace: [n] 64-bit keys, then [n_obs] 32-bit keys
     uint32_t* obs_key;            // NULL: obs_min was not asked for (no cross-lane reduction)
-    int32_t n, n_obs, chunk;      // chunk: cuboids per blockIdx.y, a multiple of 8
-    float reach;                  // (0 for a mask-only launch)
-    float tile_cull2;             // (r_max + reach + 1 cm)^2 (1 + 1e-4), rounded up: wavefront box vs cuboid
-    float cull2[CPPF_MAX_CAPSULES];  // (h + r + reach + 1 cm)^2 (1 + 1e-4), rounded up: capsule centre vs cuboid
+    int32_t n, chunk;             // chunk: cuboids per blockIdx.y, a multiple of 8
 };
 
 // float -> unsigned key with  a < b  <=>  key(a) < key(b)  (no NaN reaches here: a NaN distance never passes "v < m")
@@ -77,33 +90,153 @@ __device__ __forceinline__ void box_add_segment(const float (&c)[3], const float
 }
 
 // one (capsule, cuboid): bounding-sphere cull on the centre, then the exact test.  WANT_MIN: D = min(D, sqrt(d2) - r); else hit |= d2 < thr
-template <bool WANT_MIN>
-__device__ __forceinline__ void scene_test(const float (&wc)[3], const float (&wh)[3], const float (&lo)[3], const float (&hi)[3],
-                                           float cull2, float r, float thr, float& D, int& hit) {
-    if (cull_far(point_box_dist2(wc, lo, hi), cull2)) return;
-    const float d2 = seg_box_dist2(wc, wh, lo, hi);
+template <bool WANT_MIN, class Cap>
+__device__ __forceinline__ void scene_test(const Cap& cap, const float (&lo)[3], const float (&hi)[3], float cull2, float& D, int& hit) {
+    if (cull_far(point_box_dist2(cap.wc, lo, hi), cull2)) return;
+    const float d2 = seg_box_dist2(cap.wc, cap.wh, lo, hi);
     if constexpr (WANT_MIN) {
-        const float v = __builtin_sqrtf(d2) - r;
+        const float v = __builtin_sqrtf(d2) - cap.r();
         D = v < D ? v : D;
     } else {
-        hit |= d2 < thr;
+        hit |= d2 < cap.thr();
     }
 }
 
-// capsules the specialised form keeps in registers (the generic form stages them in LDS and keeps none)
+// This lane's capsules behind one loop: the specialised form keeps them in registers and reads radius, threshold and link from
+// the generated table, everything indexed at compile time; the generic form (kStatic = false, whatever the robot: it needs CollK
+// and the lane's LDS slots alone) stages them in LDS.  each(f) calls f(cap) for the capsules in ascending order: cap.c the index (a
+// constant expression in the specialised form), cap.wc / cap.wh centre and half-axis, cap.r() / cap.thr() / cap.link() radius,
+// mask threshold and link -- read where they are asked for, as the loops this replaces did.
 template <class RB, bool kStatic = RB::kStatic>
-struct SceneCaps {
-    static constexpr int L = 1;
+struct LaneCaps {
+    static constexpr int L = 1;  // (capsules held in registers: none)
+    struct Cap {
+        const CollK& co;
+        int c;
+        float wc[3], wh[3];
+        __device__ __forceinline__ float r() const { return co.cap_r[c]; }
+        __device__ __forceinline__ float thr() const { return co.cap_thr[c]; }
+        __device__ __forceinline__ int link() const { return co.cap_link[c]; }
+    };
+    const CollK& co;
+    int tid;
+    __device__ __forceinline__ LaneCaps(const CollK& co_, int tid_) : co(co_), tid(tid_) {}
+    __device__ __forceinline__ void fk(const RB& rb, const CollK& co, const float (&q)[RB::D], float (&R)[9], float (&p)[3]) {
+        extern __shared__ float lds[];
+        fk_capsules_to_lds<RB>(rb, co, q, lds, tid, R, p);  // (co: the kernel's own argument -- through this->co the FK costs 4 VGPRs)
+    }
+    template <class F>
+    __device__ __forceinline__ void each(F&& f) const {
+        extern __shared__ float lds[];
+        for (int c = 0; c < co.ncaps; ++c) {
+            Cap cap{co, c};
+            lds_capsule(lds, tid, c, cap.wc, cap.wh);
+            f(cap);
+        }
+    }
 };
 template <class RB>
-struct SceneCaps<RB, true> {
-    static constexpr int L = RB::Table::L > 0 ? RB::Table::L : 1;
+struct LaneCaps<RB, true> {
+    using T = typename RB::Table;
+    static constexpr int L = T::L > 0 ? T::L : 1;
+    template <int C>
+    struct Cap {
+        static constexpr int c = C;
+        const float (&wc)[3];
+        const float (&wh)[3];
+        static __device__ __forceinline__ float r() { return T::cap_r[C]; }
+        static __device__ __forceinline__ float thr() { return T::cap_thr[C]; }
+        static __device__ __forceinline__ int link() { return T::cap_link[C]; }
+    };
+    float wc[L][3], wh[L][3];
+    __device__ __forceinline__ LaneCaps(const CollK&, int) {}
+    __device__ __forceinline__ void fk(const RB& rb, const CollK& co, const float (&q)[RB::D], float (&R)[9], float (&p)[3]) {
+        capsule_fk_static<RB>(rb, q, R, p, wc, wh);
+    }
+    template <class F, int... C>
+    __device__ __forceinline__ void each_of(F&& f, std::integer_sequence<int, C...>) const {
+        (f(Cap<C>{wc[C], wh[C]}), ...);
+    }
+    template <class F>
+    __device__ __forceinline__ void each(F&& f) const {
+        each_of(f, std::make_integer_sequence<int, T::L>{});
+    }
 };
+
+// the box of every capsule segment of this lane ...
+template <class Caps>
+__device__ __forceinline__ void capsule_box(const Caps& caps, float (&blo)[3], float (&bhi)[3]) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) blo[k] = INFINITY, bhi[k] = -INFINITY;
+    caps.each([&](const auto& cap) { box_add_segment(cap.wc, cap.wh, blo, bhi); });
+}
+// ... and of every lane of the wavefront ("Shape", 1.; all 64 lanes must be here)
+__device__ __forceinline__ void wave_box_reduce(float (&blo)[3], float (&bhi)[3]) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        blo[k] = wave_min(blo[k]);
+        bhi[k] = wave_max(bhi[k]);
+    }
+}
+// capsule FK of this lane's configuration into `caps` (R, p: the last link's frame; the caller's, because arrays of this function's
+// own cost the generic kernels 2 .. 4 VGPRs), then the lane's box (a caller reduces it only where it walks a scene)
+template <class RB>
+__device__ __forceinline__ void wave_capsule_box(const RB& rb, const CollK& co, const float (&q)[RB::D], LaneCaps<RB>& caps, float (&R)[9],
+                                                 float (&p)[3], float (&blo)[3], float (&bhi)[3]) {
+    caps.fk(rb, co, q, R, p);
+    capsule_box(caps, blo, bhi);
+}
+
+// "Shape", 1.: the cuboids base + lane < o_end, one per lane (corners into llo / lhi), against the wavefront's box -> the ballot of
+// the lanes whose cuboid may come within the tile threshold of it
+__device__ __forceinline__ unsigned long long scene_tile(const float* __restrict__ box_lo, const float* __restrict__ box_hi, int o_end,
+                                                         float tile_cull2, int base, int lane, const float (&blo)[3],
+                                                         const float (&bhi)[3], float (&llo)[3], float (&lhi)[3]) {
+    const int ol = base + lane;
+    const bool have = ol < o_end;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        llo[k] = have ? box_lo[(size_t)ol * 3 + k] : 0.f;
+        lhi[k] = have ? box_hi[(size_t)ol * 3 + k] : 0.f;
+    }
+    float g2 = 0.f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float g = fmaxf(fmaxf(llo[k] - bhi[k], blo[k] - lhi[k]), 0.f);
+        g2 = CPPF_FMA(g, g, g2);
+    }
+    return __builtin_amdgcn_ballot_w64(have && !(g2 > tile_cull2));
+}
+
+// The walk over the cuboids [o_begin, o_end): 64 at a time through scene_tile (tiles for which near(base) is false are not even
+// read), then "Shape", 2.: f(o, lo, hi) once per surviving cuboid, for the whole wavefront (o, lo, hi are wave-uniform), cuboids
+// ASCENDING -- the tie rule of scene_kernel and the bit-for-bit promise of the coupled step's scene form rest on that order.
+template <class Near, class F>
+__device__ __forceinline__ void scene_walk(const float* __restrict__ box_lo, const float* __restrict__ box_hi, int o_begin, int o_end,
+                                           float tile_cull2, int lane, const float (&blo)[3], const float (&bhi)[3], Near&& near,
+                                           F&& f) {
+    for (int base = o_begin; base < o_end; base += 64) {
+        if (!near(base)) continue;
+        float llo[3], lhi[3];
+        unsigned long long live = scene_tile(box_lo, box_hi, o_end, tile_cull2, base, lane, blo, bhi, llo, lhi);
+        while (live != 0ull) {
+            const int j = __builtin_ctzll(live);
+            live &= live - 1ull;
+            const float lo[3] = {readlane_f(llo[0], j), readlane_f(llo[1], j), readlane_f(llo[2], j)};
+            const float hi[3] = {readlane_f(lhi[0], j), readlane_f(lhi[1], j), readlane_f(lhi[2], j)};
+            f(base + j, lo, hi);
+        }
+    }
+}
+template <class F>
+__device__ __forceinline__ void scene_walk(const SceneCullK& sc, int o_begin, int o_end, int lane, const float (&blo)[3],
+                                           const float (&bhi)[3], F&& f) {
+    scene_walk(sc.box_lo, sc.box_hi, o_begin, o_end, sc.tile_cull2, lane, blo, bhi, [](int) { return true; }, f);
+}
 
 template <class RB, bool WANT_MIN>
 __global__ __launch_bounds__(kBlock, CPPF_WAVES_COLL) void scene_kernel(const ChainK ch, const CollK co, const SceneK sc,
                                                                          const float* __restrict__ x) {
-    extern __shared__ float lds[];
     constexpr int D_ = RB::D;
     const RB rb{ch, co};
     const int tid = threadIdx.x, lane = tid & 63;
@@ -114,87 +247,36 @@ __global__ __launch_bounds__(kBlock, CPPF_WAVES_COLL) void scene_kernel(const Ch
     if (row0 - (size_t)lane >= (size_t)sc.n) return;
     const bool valid = row0 < (size_t)sc.n;
     const size_t row = valid ? row0 : (size_t)sc.n - 1;
-    float q[D_], R[9], p[3];
+    float q[D_];
     load_x<D_>(x, row, q);
 
-    constexpr int LS = SceneCaps<RB>::L;
-    float swc[LS][3], swh[LS][3];  // (the specialised form's capsules: registers, static indices)
-    float blo[3] = {INFINITY, INFINITY, INFINITY}, bhi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    if constexpr (RB::kStatic) {
-        capsule_fk_static<RB>(rb, q, R, p, swc, swh);
-#pragma unroll
-        for (int c = 0; c < RB::Table::L; ++c) box_add_segment(swc[c], swh[c], blo, bhi);
-    } else {
-        fk_capsules_to_lds<RB>(rb, co, q, lds, tid, R, p);
-        for (int c = 0; c < co.ncaps; ++c) {
-            float wc[3], wh[3];
-            lds_capsule(lds, tid, c, wc, wh);
-            box_add_segment(wc, wh, blo, bhi);
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        blo[k] = wave_min(blo[k]);
-        bhi[k] = wave_max(bhi[k]);
-    }
+    LaneCaps<RB> caps(co, tid);
+    float R[9], p[3], blo[3], bhi[3];
+    wave_capsule_box<RB>(rb, co, q, caps, R, p, blo, bhi);
+    wave_box_reduce(blo, bhi);
 
     const int o_begin = (int)blockIdx.y * sc.chunk;
-    const int o_end = min(sc.n_obs, o_begin + sc.chunk);
+    const int o_end = min(sc.cull.n_obs, o_begin + sc.chunk);
     float best = INFINITY;
     int best_o = -1, hit = 0;
-    for (int base = o_begin; base < o_end; base += 64) {
-        // 1. 64 cuboids, one per lane, against the wavefront's box
-        const int ol = base + lane;
-        const bool have = ol < o_end;
-        float llo[3], lhi[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            llo[k] = have ? sc.box_lo[(size_t)ol * 3 + k] : 0.f;
-            lhi[k] = have ? sc.box_hi[(size_t)ol * 3 + k] : 0.f;
-        }
-        float g2 = 0.f;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float g = fmaxf(fmaxf(llo[k] - bhi[k], blo[k] - lhi[k]), 0.f);
-            g2 = CPPF_FMA(g, g, g2);
-        }
-        unsigned long long live = __builtin_amdgcn_ballot_w64(have && !(g2 > sc.tile_cull2));
-        // 2. the survivors, one after the other, for the whole wavefront
-        while (live != 0ull) {
-            const int j = __builtin_ctzll(live);
-            live &= live - 1ull;
-            const int o = base + j;
-            const float lo[3] = {readlane_f(llo[0], j), readlane_f(llo[1], j), readlane_f(llo[2], j)};
-            const float hi[3] = {readlane_f(lhi[0], j), readlane_f(lhi[1], j), readlane_f(lhi[2], j)};
-            float Dro = INFINITY;
-            if constexpr (RB::kStatic) {
-                using T = typename RB::Table;
-#pragma unroll
-                for (int c = 0; c < T::L; ++c)
-                    scene_test<WANT_MIN>(swc[c], swh[c], lo, hi, sc.cull2[c], T::cap_r[c], T::cap_thr[c], Dro, hit);
-            } else {
-                for (int c = 0; c < co.ncaps; ++c) {
-                    float wc[3], wh[3];
-                    lds_capsule(lds, tid, c, wc, wh);
-                    scene_test<WANT_MIN>(wc, wh, lo, hi, sc.cull2[c], co.cap_r[c], co.cap_thr[c], Dro, hit);
-                }
+    scene_walk(sc.cull, o_begin, o_end, lane, blo, bhi, [&](int o, const float (&lo)[3], const float (&hi)[3]) {
+        float Dro = INFINITY;
+        caps.each([&](const auto& cap) { scene_test<WANT_MIN>(cap, lo, hi, sc.cull.cull2[cap.c], Dro, hit); });
+        if constexpr (WANT_MIN) {
+            if (Dro < best) {  // (strict, cuboids ascending: the lowest index among equals)
+                best = Dro;
+                best_o = o;
             }
-            if constexpr (WANT_MIN) {
-                if (Dro < best) {  // (strict, cuboids ascending: the lowest index among equals)
-                    best = Dro;
-                    best_o = o;
-                }
-                if (sc.obs_key != nullptr && __builtin_amdgcn_ballot_w64(Dro < sc.reach) != 0ull) {
-                    const float m = wave_min(Dro);
-                    if (lane == 0 && m < sc.reach) atomicMin(&sc.obs_key[o], scene_key(m));
-                }
+            if (sc.obs_key != nullptr && __builtin_amdgcn_ballot_w64(Dro < sc.cull.reach) != 0ull) {
+                const float m = wave_min(Dro);
+                if (lane == 0 && m < sc.cull.reach) atomicMin(&sc.obs_key[o], scene_key(m));
             }
         }
-    }
+    });
     if (!valid) return;
     if constexpr (WANT_MIN) {
         // (a negative distance is below every legal reach, so the mask read off the key is exact whatever reach is)
-        if (best < sc.reach) atomicMin(&sc.row_key[row], ((unsigned long long)scene_key(best) << 32) | (unsigned long long)(uint32_t)best_o);
+        if (best < sc.cull.reach) atomicMin(&sc.row_key[row], ((unsigned long long)scene_key(best) << 32) | (unsigned long long)(uint32_t)best_o);
     } else {
         if (hit) atomicMin(&sc.row_key[row], 0ull);
     }

@@ -48,6 +48,19 @@ def _stream_ptr(device: torch.device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
+def _scene_boxes(box_lo: torch.Tensor, box_hi: torch.Tensor, dev: torch.device, rows: str = "q"):
+    """The cuboids of a device scene, world-frame corners [O, 3] on the device of the rows (`rows`: their name) -> (box_lo, box_hi, O)."""
+    box_lo, box_hi = _require_device_tensor(box_lo, "box_lo"), _require_device_tensor(box_hi, "box_hi")
+    assert box_lo.dim() == 2 and box_lo.shape[1] == 3 and box_hi.shape == box_lo.shape, (tuple(box_lo.shape), tuple(box_hi.shape))
+    assert box_lo.device == dev and box_hi.device == dev, f"{rows}, box_lo and box_hi must be on one device"
+    return box_lo, box_hi, int(box_lo.shape[0])
+
+
+def _ptr(res: Dict[str, torch.Tensor], k: str) -> Optional[int]:
+    """the pointer of the output res[k], or None where it was not asked for"""
+    return res[k].data_ptr() if k in res else None
+
+
 class Robot:
     PACKED_BYTES_PER_ROW = 15  # 3 x fp32 (ext_cost, pos_err_m, rot_err_rad) + 3 x u8 (self, env, jlim masks)
 
@@ -488,13 +501,10 @@ class Robot:
             if "env" in parts:
                 res["min_env"] = torch.empty((S, W), dtype=torch.float32, device=dev)
 
-        def ptr(k):
-            return res[k].data_ptr() if k in res else None
-
         _hip.check(
             _hip.lib().cppf_collision_masks(
-                self._handle(dev), q.data_ptr(), S, W, ptr("self_mask"), ptr("env_mask"), ptr("jlim_mask"),
-                ptr("ext_cost"), ptr("min_self"), ptr("min_env"), _stream_ptr(dev),
+                self._handle(dev), q.data_ptr(), S, W, _ptr(res, "self_mask"), _ptr(res, "env_mask"), _ptr(res, "jlim_mask"),
+                _ptr(res, "ext_cost"), _ptr(res, "min_self"), _ptr(res, "min_env"), _stream_ptr(dev),
             )  # fmt: skip
         )
         for k in ("self_mask", "env_mask", "jlim_mask"):
@@ -514,10 +524,7 @@ class Robot:
         lead = tuple(q.shape[:-1])
         S, W = (1, lead[0]) if q.dim() == 2 else lead
         dev = q.device
-        box_lo, box_hi = _require_device_tensor(box_lo, "box_lo"), _require_device_tensor(box_hi, "box_hi")
-        assert box_lo.dim() == 2 and box_lo.shape[1] == 3 and box_hi.shape == box_lo.shape, (tuple(box_lo.shape), tuple(box_hi.shape))
-        assert box_lo.device == dev and box_hi.device == dev, "q, box_lo and box_hi must be on one device"
-        O = int(box_lo.shape[0])
+        box_lo, box_hi, O = _scene_boxes(box_lo, box_hi, dev)
         want = tuple(want)
         assert set(want) <= {"env_mask", "min_env", "nearest_obs", "obs_min"}, want
         res: Dict[str, torch.Tensor] = {"env_mask": torch.empty(lead, dtype=torch.uint8, device=dev)}
@@ -531,13 +538,10 @@ class Robot:
         _hip.check(_hip.lib().cppf_scene_workspace_bytes(S * W, O, ctypes.byref(nbytes)))
         work = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
 
-        def ptr(k):
-            return res[k].data_ptr() if k in res else None
-
         _hip.check(
             _hip.lib().cppf_scene_env_collisions(
-                self._handle(dev), q.data_ptr(), S, W, box_lo.data_ptr(), box_hi.data_ptr(), O, float(reach), ptr("env_mask"),
-                ptr("min_env"), ptr("nearest_obs"), ptr("obs_min"), work.data_ptr(), nbytes.value, _stream_ptr(dev),
+                self._handle(dev), q.data_ptr(), S, W, box_lo.data_ptr(), box_hi.data_ptr(), O, float(reach), _ptr(res, "env_mask"),
+                _ptr(res, "min_env"), _ptr(res, "nearest_obs"), _ptr(res, "obs_min"), work.data_ptr(), nbytes.value, _stream_ptr(dev),
             )  # fmt: skip
         )
         res["env_mask"] = res["env_mask"].view(torch.bool)
@@ -570,10 +574,7 @@ class Robot:
         assert q.dim() == 3 and q.shape[2] == self.ndof, f"q must be [k, ntimesteps, {self.ndof}], is {tuple(q.shape)}"
         S, W, _ = q.shape
         dev = q.device
-        box_lo, box_hi = _require_device_tensor(box_lo, "box_lo"), _require_device_tensor(box_hi, "box_hi")
-        assert box_lo.dim() == 2 and box_lo.shape[1] == 3 and box_hi.shape == box_lo.shape, (tuple(box_lo.shape), tuple(box_hi.shape))
-        assert box_lo.device == dev and box_hi.device == dev, "q, box_lo and box_hi must be on one device"
-        O = int(box_lo.shape[0])
+        box_lo, box_hi, O = _scene_boxes(box_lo, box_hi, dev)
         want = tuple(want)
         assert set(want) <= {"status", "min_clear", "hit_node", "nodes"}, want
         level = int(level)
@@ -589,13 +590,10 @@ class Robot:
         _hip.check(_hip.lib().cppf_motion_workspace_bytes(S, W, ctypes.byref(nbytes)))
         work = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
 
-        def ptr(k):
-            return res[k].data_ptr() if k in res else None
-
         _hip.check(
             _hip.lib().cppf_motion_clearance(
-                self._handle(dev), q.data_ptr(), S, W, level, box_lo.data_ptr(), box_hi.data_ptr(), O, float(reach), ptr("status"),
-                ptr("min_clear"), ptr("hit_node"), ptr("nodes"), work.data_ptr(), nbytes.value, _stream_ptr(dev),
+                self._handle(dev), q.data_ptr(), S, W, level, box_lo.data_ptr(), box_hi.data_ptr(), O, float(reach), _ptr(res, "status"),
+                _ptr(res, "min_clear"), _ptr(res, "hit_node"), _ptr(res, "nodes"), work.data_ptr(), nbytes.value, _stream_ptr(dev),
             )  # fmt: skip
         )
         return res
@@ -615,10 +613,7 @@ class Robot:
         assert q.dim() == 3 and q.shape[2] == self.ndof, f"q must be [k, ntimesteps, {self.ndof}], is {tuple(q.shape)}"
         S, W, _ = q.shape
         dev = q.device
-        box_lo, box_hi = _require_device_tensor(box_lo, "box_lo"), _require_device_tensor(box_hi, "box_hi")
-        assert box_lo.dim() == 2 and box_lo.shape[1] == 3 and box_hi.shape == box_lo.shape, (tuple(box_lo.shape), tuple(box_hi.shape))
-        assert box_lo.device == dev and box_hi.device == dev, "q, box_lo and box_hi must be on one device"
-        O = int(box_lo.shape[0])
+        box_lo, box_hi, O = _scene_boxes(box_lo, box_hi, dev)
         want = tuple(want)
         assert set(want) <= {"status", "depth", "hit_num", "min_clear", "n_tested"}, want
         start_level, max_depth, max_frontier = int(start_level), int(max_depth), int(max_frontier)
@@ -641,14 +636,11 @@ class Robot:
         _hip.check(_hip.lib().cppf_motion_resolve_workspace_bytes(S, W, max_frontier, ctypes.byref(nbytes)))
         work = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
 
-        def ptr(k):
-            return res[k].data_ptr() if k in res else None
-
         _hip.check(
             _hip.lib().cppf_motion_resolve(
                 self._handle(dev), q.data_ptr(), S, W, start_level, max_depth, max_frontier, box_lo.data_ptr(), box_hi.data_ptr(), O,
-                float(reach), decided.data_ptr() if skipping else None, ptr("status"), ptr("depth"), ptr("hit_num"), ptr("min_clear"),
-                ptr("n_tested"), work.data_ptr(), nbytes.value, _stream_ptr(dev),
+                float(reach), decided.data_ptr() if skipping else None, _ptr(res, "status"), _ptr(res, "depth"), _ptr(res, "hit_num"), _ptr(res, "min_clear"),
+                _ptr(res, "n_tested"), work.data_ptr(), nbytes.value, _stream_ptr(dev),
             )  # fmt: skip
         )
         return res
@@ -762,10 +754,7 @@ class Robot:
         if x_out is None:
             x_out = torch.empty_like(x)
         if scene is not None:
-            box_lo, box_hi = (_require_device_tensor(t, name) for t, name in zip(scene, ("box_lo", "box_hi")))
-            assert box_lo.dim() == 2 and box_lo.shape[1] == 3 and box_hi.shape == box_lo.shape, (tuple(box_lo.shape), tuple(box_hi.shape))
-            assert box_lo.device == dev and box_hi.device == dev, "x, box_lo and box_hi must be on one device"
-            O = int(box_lo.shape[0])
+            box_lo, box_hi, O = _scene_boxes(*scene, dev, rows="x")
             _hip.check(
                 _hip.lib().cppf_lm_full_step_scene(
                     self._handle(dev), x.data_ptr(), target.data_ptr(), xv.data_ptr() if xv is not None else None, n // W, W,
