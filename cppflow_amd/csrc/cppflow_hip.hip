@@ -29,6 +29,7 @@
 
 #include "../../include/cppflow_hip_debug.h"
 #include "lmik_device.h"
+#include "obstacle_reach.h"
 #include "robots_gen.h"
 
 using namespace cppf;
@@ -691,6 +692,10 @@ int cppf_set_obstacles(cppf_robot* robot, int n_obs, const float* cuboids, const
         }
     }
     robot->coll.nobs = n_obs;
+    // the capsules that can reach any of these cuboids at all (obstacle_reach.h): the mask-only collision stage skips the others
+    const CapsuleReach live = capsule_reach(robot->desc, robot->coll.cap_c, robot->coll.cap_cull, n_obs, robot->coll.obs_lo, robot->coll.obs_hi);
+    robot->coll.cap_live_any = live.any;
+    robot->coll.cap_live_lim = live.lim;
     return CPPF_OK;
 }
 

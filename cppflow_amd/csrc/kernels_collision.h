@@ -111,11 +111,24 @@ __device__ __forceinline__ uint32_t cuboids_in_reach(const CollK& co, const floa
     return near;
 }
 
-template <class RB, bool WANT_MIN>
+// IN_LIMITS: the caller guarantees that the row's q lies inside the joint limits [lo, hi] (or is NaN, which hits nothing either way).
+// A mask-only stage then drops, at compile time, the self pairs certified never to come within 1 cm of touching anywhere in the
+// joint box (Table::pair_never, cppflow_amd/gen_robots.py): sphere test and exact test both go.
+// `live` (mask-only stages; wave-uniform): bit c clear = capsule c cannot reach any cuboid of the current set (obstacle_reach.h) and
+// is skipped -- co.cap_live_lim for rows inside the limits, co.cap_live_any otherwise (only capsules that do not move are decided there).
+// Both prunings leave every mask bit as it was: a skipped test had 1 cm of slack, the margin the broad phase already relies on
+// (cull_far).  WANT_MIN keeps every test -- the minimum distances need them.
+template <class T>
+constexpr bool has_certified_pairs() {
+    for (int pi = 0; pi < T::P; ++pi)
+        if (T::pair_never[pi]) return true;
+    return false;
+}
+template <class RB, bool WANT_MIN, bool IN_LIMITS = false>
 __device__ __forceinline__ CollOut collide_tests_static(const CollK& co,
                                                         const float (&wc)[(RB::Table::L > 0 ? RB::Table::L : 1)][3],
                                                         const float (&wh)[(RB::Table::L > 0 ? RB::Table::L : 1)][3],
-                                                        bool do_self, bool do_env) {
+                                                        bool do_self, bool do_env, uint32_t live) {
     using T = typename RB::Table;
     // Broad phase of the mask-only launches (see cull_far): one bounding-sphere test per pair / per (capsule, cuboid) on
     // the capsule centres; the exact distance is evaluated only when some lane of the wavefront is within reach.
@@ -127,6 +140,7 @@ __device__ __forceinline__ CollOut collide_tests_static(const CollK& co,
         for (int pi = 0; pi < T::P; ++pi) {
             const int a = T::pair_a[pi], b = T::pair_b[pi];
             if constexpr (!WANT_MIN) {
+                if (IN_LIMITS && T::pair_never[pi]) continue;  // (a literal after unrolling)
                 if (cull_far(mid_dist2(wc[a], wc[b]), T::pair_cull[pi])) continue;
             }
             const float d2 = seg_seg_dist2(wc[a], wh[a], wc[b], wh[b], T::cap_a[a], T::cap_ia[a], T::cap_a[b], T::cap_ia[b]);
@@ -148,6 +162,7 @@ __device__ __forceinline__ CollOut collide_tests_static(const CollK& co,
         for (int c = 0; c < T::L; ++c) {
             uint32_t near = ~0u;
             if constexpr (!WANT_MIN) {
+                if (!((live >> c) & 1u)) continue;  // (one scalar test)
                 near = cuboids_in_reach(co, wc[c], T::cap_cull[c]);
                 if (near == 0u) continue;
             }
@@ -238,7 +253,7 @@ __device__ __forceinline__ CollOut collide_row(const RB& rb, const CollK& co, co
         constexpr int L = RB::Table::L > 0 ? RB::Table::L : 1;
         float wc[L][3], wh[L][3];
         capsule_fk_static<RB>(rb, q, R, p, wc, wh);
-        return collide_tests_static<RB, WANT_MIN>(co, wc, wh, do_self, do_env);
+        return collide_tests_static<RB, WANT_MIN>(co, wc, wh, do_self, do_env, co.cap_live_any);
     } else {
         fk_capsules_to_lds<RB>(rb, co, q, lds, tid, R, p);
         return collide_from_lds<WANT_MIN>(co, lds, tid, do_self, do_env);

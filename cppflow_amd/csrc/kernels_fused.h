@@ -346,7 +346,7 @@ __device__ __forceinline__ bool lm_row_iterate(const RB& rb, const LmK& prm, con
 template <class RB, int COLL>
 __device__ __forceinline__ void lm_row_finish(const RB& rb, const CollK& co, const cppf_lm_outputs& out, float* lds, int tid,
                                               size_t row, const float (&Rt)[9], const float (&tt)[3], const float (&q)[RB::D],
-                                              RowSummary& rs) {
+                                              RowSummary& rs, bool in_limits) {
     constexpr int D = RB::D;
     if (out.x_out) store_x<D>(out.x_out, row, q);
     const bool want_metrics = out.pos_err_m || out.rot_err_rad || out.seed_summary;
@@ -373,7 +373,13 @@ __device__ __forceinline__ void lm_row_finish(const RB& rb, const CollK& co, con
                 capsule_fk_static<RB>(rb, q, R, p, wc, wh);
                 metrics(R, p);
             }
-            c = collide_tests_static<RB, COLL == 2>(co, wc, wh, do_self, do_env);
+            // in_limits (wave-uniform): the capsules that can reach a cuboid at all, and -- one branch, where the table has certified
+            // pairs -- the mask-only stage without the self pairs the joint limits rule out
+            const uint32_t live = in_limits ? co.cap_live_lim : co.cap_live_any;
+            if (COLL == 1 && has_certified_pairs<typename RB::Table>() && in_limits)
+                c = collide_tests_static<RB, false, true>(co, wc, wh, do_self, do_env, live);
+            else
+                c = collide_tests_static<RB, COLL == 2>(co, wc, wh, do_self, do_env, live);
         } else {
             {
                 float R[9], p[3];
@@ -533,7 +539,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(lm_waves
             for (int j = 0; j < D; ++j) q[j] = __builtin_nanf("");
         }
         lm_pace(pace_t0, prm.n_steps, prm.pace_ticks);  // (the finish stage: one more slot of the schedule)
-        lm_row_finish<RB, COLL>(rb, co, out, lds, tid_b, row_b, Rt, tt, q, rs);
+        // q is inside the joint limits (or NaN) exactly when the row's last act was the clamp: the launch clamps, and no row can
+        // leave the loop before its first update (an early-out launch returns a converged row's INPUT untouched)
+        const bool in_limits = prm.clamp != 0 && prm.n_steps >= 1 && !(prm.tol_pos2 > 0.f);
+        lm_row_finish<RB, COLL>(rb, co, out, lds, tid_b, row_b, Rt, tt, q, rs, in_limits);
     }
     if constexpr (COLL != 0) {
         if (out.seed_summary) {

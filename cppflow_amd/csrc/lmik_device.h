@@ -54,6 +54,8 @@ struct CollK {
     float jl_lo[CPPF_MAX_DOF];  // padded limits of search.py:46-51
     float jl_hi[CPPF_MAX_DOF];
     int32_t ncaps, npairs, nobs, has_jl;
+    uint32_t cap_live_any;  // bit c: capsule c can come within broad-phase reach of SOME cuboid of obs_* (cppf_set_obstacles, obstacle_reach.h)
+    uint32_t cap_live_lim;  // the same for rows inside the joint limits: a subset
 };
 
 struct LmK {

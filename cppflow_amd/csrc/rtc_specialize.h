@@ -170,6 +170,10 @@ std::string rtc_table_source(const cppf_robot& rb) {
         for (int p = 0; p < Pm; ++p) o << (p ? ", " : "") << (P ? d.pairs[p][side] : 0);
         o << "};\n";
     }
+    // (no certificate at run time: gen_robots.py's branch and bound is not part of the library, so every pair stays live)
+    o << "    static constexpr bool pair_never[" << Pm << "] = {";
+    for (int p = 0; p < Pm; ++p) o << (p ? ", " : "") << "false";
+    o << "};\n";
     o << "};\n} }\n";
     return o.str();
 }

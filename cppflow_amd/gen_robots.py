@@ -76,6 +76,124 @@ def capsule_centred(cap_p0, cap_p1):
     return c, h, a.astype(np.float32), ia.astype(np.float32), np.sqrt(a)
 
 
+# ---- self pairs that can never touch inside the joint limits ----------------------------------------------------------------------
+# pair_never[pi]: dist(seg_a, seg_b) - (r_a + r_b) >= CERT_MARGIN for EVERY q in [lo, hi], proved (not sampled) by branch and bound in
+# float64 on the canonical chain.  1 cm is the slack the broad phase already relies on (cull_far in csrc/kernels_collision.h): with it
+# the exact fp32 test of such a pair could only have said "no hit", so a mask-only launch whose rows are clamped to the limits drops
+# the pair at compile time.  The distance of a pair depends on the joints between its two links only (joints 0 .. link_b for a base
+# capsule); capsule a is at rest in its own link's frame, and when joint k alone moves by dq every point of capsule b moves by at
+# most |dq| rho_k, rho_k = a bound on the point's distance from joint k's axis (1 per unit for a prismatic joint).  The distance of
+# two segments is 1-Lipschitz in the displacement of one of them, so over a box of half-widths w about a centre c
+#     dist(q) >= dist(c) - sum_k w_k rho_k.
+# A box whose bound clears the margin is accepted, any other is halved along its widest (w rho) side; the search gives up -- the pair
+# stays live -- on a centre below the margin, after CERT_MAX_BOXES boxes, or when more than CERT_MAX_DIMS joints lie between the links
+# (the box count grows with the power of the dimension; generate() runs on every CPU test run and has to stay within seconds).
+CERT_MARGIN = 0.01
+CERT_SLACK = 1e-6  # float64 rounding of the chain and of the distance is below 1e-12; three digits of the margin are not worth arguing
+CERT_MAX_DIMS = 4  # with 100 000 boxes: 1.8 s for the four shipped robots, 0.4 s of it Panda (12 of its 25 pairs certified)
+CERT_MAX_BOXES = 100000
+
+
+def _seg_point_dist2(p, a, d, dd):
+    """squared distance of the points p [N, 3] from the segments a + u d, u in [0, 1] (dd = |d|^2, may be 0)"""
+    u = np.clip(np.einsum("ij,ij->i", p - a, d) / np.where(dd > 0, dd, 1.0), 0.0, 1.0) * (dd > 0)
+    e = p - (a + u[:, None] * d)
+    return np.einsum("ij,ij->i", e, e)
+
+
+def segment_distance(p1, q1, p2, q2):
+    """Distance of the segments p1 q1 and p2 q2 ([N, 3] each, float64): the interior critical point where the segments are not
+    parallel (Ericson 5.1.9), and the four end-point-to-segment distances, whichever is smallest -- the minimum is always one of them."""
+    d1, d2, r = q1 - p1, q2 - p2, p1 - p2
+    a, e = np.einsum("ij,ij->i", d1, d1), np.einsum("ij,ij->i", d2, d2)
+    b, c, f = np.einsum("ij,ij->i", d1, d2), np.einsum("ij,ij->i", d1, r), np.einsum("ij,ij->i", d2, r)
+    den = a * e - b * b
+    ok = den > 1e-12 * np.maximum(a * e, 1e-300)
+    s = np.clip(np.where(ok, (b * f - c * e) / np.where(ok, den, 1.0), 0.0), 0.0, 1.0)
+    t = np.clip(np.where(e > 0, (b * s + f) / np.where(e > 0, e, 1.0), 0.0), 0.0, 1.0)
+    g = (p1 + s[:, None] * d1) - (p2 + t[:, None] * d2)
+    best = np.einsum("ij,ij->i", g, g)
+    for v in (_seg_point_dist2(p1, p2, d2, e), _seg_point_dist2(q1, p2, d2, e), _seg_point_dist2(p2, p1, d1, a), _seg_point_dist2(q2, p1, d1, a)):
+        best = np.minimum(best, v)
+    return np.sqrt(best)
+
+
+def pair_joints(ch: CanonicalChain, a: int, b: int):
+    """(the capsule on the nearer link, the one on the farther link, the joints between them) of the pair (a, b)"""
+    if ch.cap_link[a] > ch.cap_link[b]:
+        a, b = b, a
+    return a, b, list(range(int(ch.cap_link[a]) + 1, int(ch.cap_link[b]) + 1))
+
+
+def _pair_clearance(ch: CanonicalChain, a: int, b: int, joints, q):
+    """clearance of the pair at the configurations q [N, len(joints)] of the joints between its links (capsule a's link frame)"""
+    n = q.shape[0]
+    R = np.broadcast_to(np.eye(3), (n, 3, 3))
+    p = np.zeros((n, 3))
+    for i, j in enumerate(joints):
+        F = ch.F[j]
+        p = p + R @ F[9:12]
+        R = R @ F[:9].reshape(3, 3)
+        if ch.jtype[j] == 1:
+            p = p + R[:, :, 2] * q[:, i : i + 1]
+        else:
+            cs, sn = np.cos(q[:, i]), np.sin(q[:, i])
+            M = np.zeros((n, 3, 3))
+            M[:, 0, 0], M[:, 0, 1], M[:, 1, 0], M[:, 1, 1], M[:, 2, 2] = cs, -sn, sn, cs, 1.0
+            R = R @ M
+    b0, b1 = p + R @ ch.cap_p0[b], p + R @ ch.cap_p1[b]
+    a0, a1 = np.broadcast_to(ch.cap_p0[a], (n, 3)), np.broadcast_to(ch.cap_p1[a], (n, 3))
+    return segment_distance(a0, a1, b0, b1) - (ch.cap_r[a] + ch.cap_r[b])
+
+
+def pair_travel_bounds(ch: CanonicalChain, b: int, joints):
+    """rho_k for each of `joints` (the last of them carries capsule b): how far a point of the capsule moves per unit of joint k"""
+    reach = max(np.linalg.norm(ch.cap_p0[b]), np.linalg.norm(ch.cap_p1[b]))  # bound on |point| in the frame of the link
+    rho = []
+    for j in reversed(joints):
+        rho.append(1.0 if ch.jtype[j] == 1 else reach)
+        if ch.jtype[j] == 1:
+            reach += max(abs(ch.lo[j]), abs(ch.hi[j]))
+        reach += np.linalg.norm(ch.F[j][9:12])
+    return np.array(rho[::-1])
+
+
+def certify_pair(ch: CanonicalChain, a: int, b: int, margin: float = CERT_MARGIN, max_dims: int = CERT_MAX_DIMS,
+                 max_boxes: int = CERT_MAX_BOXES) -> bool:
+    """True only with a proof that the pair keeps `margin` of clearance over the whole joint box (see above); deterministic."""
+    a, b, joints = pair_joints(ch, a, b)
+    if not joints:  # same link: a constant
+        return bool(_pair_clearance(ch, a, b, joints, np.zeros((1, 0)))[0] >= margin + CERT_SLACK)
+    if len(joints) > max_dims or not np.all(ch.hi[joints] >= ch.lo[joints]):
+        return False
+    rho = pair_travel_bounds(ch, b, joints)
+    c = 0.5 * (ch.lo[joints] + ch.hi[joints])[None]
+    w = 0.5 * (ch.hi[joints] - ch.lo[joints])[None]
+    done = 0
+    while c.shape[0]:
+        done += c.shape[0]
+        if done > max_boxes:
+            return False
+        d = _pair_clearance(ch, a, b, joints, c)
+        if np.any(d < margin + CERT_SLACK):
+            return False
+        open_ = d - (w * rho).sum(axis=1) < margin + CERT_SLACK
+        c, w = c[open_], w[open_]
+        k = np.argmax(w * rho, axis=1)
+        rows = np.arange(c.shape[0])
+        w[rows, k] *= 0.5
+        lo_half, hi_half = c.copy(), c.copy()
+        lo_half[rows, k] -= w[rows, k]
+        hi_half[rows, k] += w[rows, k]
+        c, w = np.concatenate([lo_half, hi_half]), np.concatenate([w, w])
+    return True
+
+
+def pair_never(ch: CanonicalChain):
+    """the certificate of every pair of the chain, in pair order (the table's pair_never)"""
+    return [certify_pair(ch, int(a), int(b)) for a, b in ch.pairs]
+
+
 def emit_robot(name: str, ch: CanonicalChain) -> str:
     d, L, P = ch.ndof, ch.n_capsules, ch.n_pairs
     cname = "".join(p.capitalize() for p in name.split("_"))
@@ -111,6 +229,8 @@ def emit_robot(name: str, ch: CanonicalChain) -> str:
     s.append(f"    static constexpr float cap_cull[{Lm}] = {_arr(cap_cull)};  // broad phase, capsule vs cuboid")
     s.append(f"    static constexpr int pair_a[{Pm}] = {{" + ", ".join(str(int(v)) for v in (ch.pairs[:, 0] if P else [0])) + "};")
     s.append(f"    static constexpr int pair_b[{Pm}] = {{" + ", ".join(str(int(v)) for v in (ch.pairs[:, 1] if P else [0])) + "};")
+    never = pair_never(ch) if P else [False]
+    s.append(f"    static constexpr bool pair_never[{Pm}] = {{" + ", ".join("true" if v else "false" for v in never) + "};  // certified: never within 1 cm inside [lo, hi]")
     s.append("};")
     return "\n".join(s)
 
