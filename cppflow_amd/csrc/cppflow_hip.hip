@@ -942,23 +942,29 @@ int collision_masks_gated(const cppf_robot* robot, const float* q, int S, int W,
 }
 
 // Which elimination a coupled step of S trajectories of W waypoints resolves to on this handle (see the comments at the launches
-// in lm_full_step_gated): the parallel-in-time form, the row-per-lane form, or neither (the one-wavefront / one-lane kernels).
-// Depends on the sizes, the parameters and the handle's tuning only, so a caller can know it before it launches anything.
-struct FullStepForm {
-    bool use_pcr, use_rows;
+// in lm_full_step_gated).  Depends on the sizes, the parameters and the handle's tuning only, so a caller can know it before it
+// launches anything.
+enum class FullStepForm {
+    LaneVar,  // individually weighted differencing rows: one lane per trajectory, couplings read from memory
+    Pcr,      // parallel in time
+    Rows,     // one block row per lane
+    Wave,     // one wavefront per trajectory (takes no pinned end)
+    Lane,     // one lane per trajectory
 };
 FullStepForm full_step_form(const cppf_robot* robot, size_t n, int W, bool use_pose, bool var_coupling) {
+    const int ndof = robot->desc.ndof;
     const int t_pcr_rows = tune(robot, CPPF_TUNE_PCR_MAX_ROWS);
     const bool g_pcr_lds = tune(robot, CPPF_TUNE_PCR_LDS) != 0;
     const bool g_rows_pose = tune(robot, CPPF_TUNE_ROWS_POSE) != 0, g_full_rows = tune(robot, CPPF_TUNE_FULL_ROWS) != 0;
     const size_t pcr_rows = t_pcr_rows >= 0 ? (size_t)t_pcr_rows : (size_t)((W <= 256 && g_pcr_lds) ? kPcrMaxRowsLds : kPcrMaxRowsGlobal);
-    const size_t pcr_limit = pcr_rows * (robot->desc.ndof <= 7 ? 100 : 50) / 100;
-    FullStepForm f;
-    f.use_pcr = !var_coupling && !use_pose && W <= 512 && n <= pcr_limit && robot->desc.ndof >= 3 && robot->desc.ndof <= 8;
-    f.use_rows = !var_coupling && !f.use_pcr && (!use_pose || g_rows_pose) && g_full_rows && robot->desc.ndof >= 3 &&
-                 robot->desc.ndof <= 12 && W <= (1 << 19);
-    return f;
+    const size_t pcr_limit = pcr_rows * (ndof <= 7 ? 100 : 50) / 100;
+    if (var_coupling) return FullStepForm::LaneVar;
+    if (!use_pose && W <= 512 && n <= pcr_limit && ndof >= 3 && ndof <= 8) return FullStepForm::Pcr;
+    if ((!use_pose || g_rows_pose) && g_full_rows && ndof >= 3 && ndof <= 12 && W <= (1 << 19)) return FullStepForm::Rows;
+    // with the pose block the one-lane kernel keeps the case (see lm_full_step_gated); 9 .. 12 joints have no one-wavefront form
+    return ndof <= 8 && !use_pose ? FullStepForm::Wave : FullStepForm::Lane;
 }
+inline bool full_step_gateable(FullStepForm form) { return form == FullStepForm::Pcr || form == FullStepForm::Rows; }
 const char* const kGatedFormRefusal =
     "cppflow_hip: the device-side optimiser loop gates the parallel-in-time and the row-per-lane "
     "elimination only (no pose block, no individually weighted differencing rows, CPPF_TUNE_FULL_ROWS on)";
@@ -973,16 +979,14 @@ int full_step_pin_check(const cppf_robot* robot, int S, int W, const cppf_full_p
     if (params->differencing_mode != 0 || params->pose_do_scale_down_satisfied)
         return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: a pinned end waypoint is not combined with the \"satisfied\" row options "
                                           "(differencing_mode != 0, pose_do_scale_down_satisfied)");
-    // Every route to full_solve_wave_kernel, restated from the end of lm_full_step_gated (keep the two in step): up to 8 joints,
-    // no pose block, and neither the parallel-in-time nor the row-per-lane form -- which is CPPF_TUNE_FULL_ROWS = 0 beyond the
-    // parallel-in-time sizes, and also fewer than 3 joints or more than 2^19 waypoints, where the row-per-lane form does not exist.
-    if (S >= 1 && W >= 1 && (size_t)S * W <= 0x7fffffffu && !params->use_pose && robot->desc.ndof <= 8) {
-        const FullStepForm form = full_step_form(robot, (size_t)S * W, W, false, false);
-        if (!form.use_pcr && !form.use_rows)
-            return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: the one-wavefront-per-trajectory elimination (what a step resolves to under "
-                                              "CPPF_TUNE_FULL_ROWS = 0, with fewer than 3 joints or beyond 2^19 waypoints) takes no "
-                                              "pinned end waypoint");
-    }
+    // full_solve_wave_kernel: up to 8 joints, no pose block, and neither the parallel-in-time nor the row-per-lane form -- which is
+    // CPPF_TUNE_FULL_ROWS = 0 beyond the parallel-in-time sizes, and also fewer than 3 joints or more than 2^19 waypoints, where the
+    // row-per-lane form does not exist.
+    if (S >= 1 && W >= 1 && (size_t)S * W <= 0x7fffffffu &&
+        full_step_form(robot, (size_t)S * W, W, params->use_pose != 0, false) == FullStepForm::Wave)
+        return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: the one-wavefront-per-trajectory elimination (what a step resolves to under "
+                                          "CPPF_TUNE_FULL_ROWS = 0, with fewer than 3 joints or beyond 2^19 waypoints) takes no "
+                                          "pinned end waypoint");
     return CPPF_OK;
 }
 
@@ -1045,9 +1049,8 @@ int lm_full_step_gated(const cppf_robot* robot, const float* x_in, const float* 
     const int t_pcr_lds = tune(robot, CPPF_TUNE_PCR_LDS);
     const bool g_pcr_lds = t_pcr_lds != 0, g_pcr_split = t_pcr_lds != 1;
     const FullStepForm form = full_step_form(robot, n, W, prm.use_pose != 0, var_coupling);
-    const bool use_pcr = form.use_pcr, use_rows = form.use_rows;
-    prm.fold = use_rows || var_coupling;
-    if (gate.ctl != nullptr && !use_pcr && !use_rows) return fail(CPPF_ERR_UNSUPPORTED, kGatedFormRefusal);
+    prm.fold = form != FullStepForm::Pcr;  // (the parallel-in-time kernel assembles the terms itself: FullK::fold)
+    if (gate.ctl != nullptr && !full_step_gateable(form)) return fail(CPPF_ERR_UNSUPPORTED, kGatedFormRefusal);
     hipStream_t st = (hipStream_t)stream;
     const int rc = for_robot(robot, [&](auto tag) {
         using RB = typename decltype(tag)::type;
@@ -1069,44 +1072,6 @@ int lm_full_step_gated(const cppf_robot* robot, const float* x_in, const float* 
         return CPPF_OK;
     });
     if (rc) return rc;
-    // Trajectories are eliminated one per wavefront (8 x 8 lane tile) up to 8 joints, one per lane beyond.  With the pose
-    // block the d x d blocks are J^T J + a small diagonal (rank 6 of 7, cond ~1e7): the per-lane kernel's Cholesky with
-    // floored pivots copes with that better than the explicit Gauss-Jordan inverse, so it keeps that case.
-    // Up to ~128k rows (the planner's cadence is one trajectory): parallel cyclic reduction, one workgroup per trajectory, one
-    // lane per waypoint; beyond that its O(T log T) work and traffic lose against the waypoint-after-waypoint kernels
-    if (var_coupling) {
-        return for_ndof(robot->desc.ndof, [&](auto dof) {
-            hipLaunchKernelGGL((full_solve_kernel<decltype(dof)::D, true>), dim3((unsigned)((S + 63) / 64)), dim3(64), 0, st, robot->chain,
-                               prm, x_in, virtual_configs, work_blocks, work_G, work_y, x_out, w2next);
-            return check_launch();
-        });
-    }
-    if (use_pcr) {
-        return for_ndof(robot->desc.ndof, [&](auto dof) {
-            constexpr int D = decltype(dof)::D;
-            if constexpr (D <= 8) {  // (full_step_form: the parallel-in-time form exists for 3 .. 8 joints)
-                if (W <= 256 && g_pcr_lds) {  // the state in LDS: 256 x ((d(d+1)/2 + d + d^2) | 1) floats
-                    constexpr size_t kState = 256 * (size_t)((D * (D + 1) / 2 + D + D * D) | 1) * sizeof(float);
-                    CPPF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&full_solve_pcr_kernel<D, 256, true>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)kState));
-                    if (g_pcr_split && (D <= kPcrSplitMaxD || t_pcr_lds == 3)) {  // see kPcrSplitMaxD; 3 forces the split form
-                        CPPF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&full_solve_pcr_kernel<D, 512, true, true>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)kState));
-                        hipLaunchKernelGGL((full_solve_pcr_kernel<D, 512, true, true>), dim3((unsigned)S), dim3(512), kState, st,
-                                           robot->chain, prm, x_in, virtual_configs, work_blocks, work_G, x_out, gate);
-                    } else
-                        hipLaunchKernelGGL((full_solve_pcr_kernel<D, 256, true>), dim3((unsigned)S), dim3(256), kState, st,
-                                           robot->chain, prm, x_in, virtual_configs, work_blocks, work_G, x_out, gate);
-                } else if (W <= 256)
-                    hipLaunchKernelGGL((full_solve_pcr_kernel<D, 256>), dim3((unsigned)S), dim3(256), 0, st, robot->chain, prm, x_in,
-                                       virtual_configs, work_blocks, work_G, x_out, gate);
-                else
-                    hipLaunchKernelGGL((full_solve_pcr_kernel<D, 512>), dim3((unsigned)S), dim3(512), 0, st, robot->chain, prm, x_in,
-                                       virtual_configs, work_blocks, work_G, x_out, gate);
-            }
-            return check_launch();
-        });
-    }
     // row-per-lane kernels: 8 trajectories per one-wavefront workgroup and two workgroups (the two ends of the path) per 8
     // trajectories; the LDS reservation caps the workgroups per compute unit at ceil(#workgroups / 256) (160 KB per compute
     // unit), which spreads a small launch over distinct compute units
@@ -1114,31 +1079,64 @@ int lm_full_step_gated(const cppf_robot* robot, const float* x_in, const float* 
     const unsigned rows_wgs = 2u * (unsigned)((S + rows_tpw - 1) / rows_tpw);
     const unsigned rows_per_cu = (rows_wgs + 255) / 256;
     const size_t rows_lds = rows_per_cu == 1 ? 96 * 1024 : rows_per_cu == 2 ? 64 * 1024 : rows_per_cu == 3 ? 48 * 1024 : 0;
+    const uint32_t pris_mask = robot->chain.pris_mask;
+    const dim3 lane_grid((unsigned)((S + 63) / 64));
     return for_ndof(robot->desc.ndof, [&](auto dof) {
         constexpr int D = decltype(dof)::D;
-        if (use_rows) {  // (every ndof; sixteen lanes per trajectory at 9 .. 12 joints, see rows_tpw)
-            if (rows_lds > 64 * 1024) {  // per device: set whenever it is needed, a host-side table update
-                CPPF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&full_rows_eliminate_kernel<D>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-                CPPF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&full_rows_substitute_kernel<D>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-            }
-            hipLaunchKernelGGL((full_rows_eliminate_kernel<D>), dim3(rows_wgs), dim3(64), rows_lds, st, prm, robot->chain.pris_mask,
-                               work_blocks, work_G, work_y, gate);
-            hipLaunchKernelGGL((full_rows_substitute_kernel<D>), dim3(rows_wgs), dim3(64), rows_lds, st, prm, robot->chain.pris_mask,
-                               x_in, work_blocks, work_G, work_y, x_out, gate);
-            return check_launch();
+        switch (form) {
+            case FullStepForm::LaneVar:
+                hipLaunchKernelGGL((full_solve_kernel<D, true>), lane_grid, dim3(64), 0, st, prm, pris_mask, x_in, work_blocks, work_G,
+                                   work_y, x_out, w2next);
+                break;
+            case FullStepForm::Pcr:
+                // Up to ~128k rows (the planner's cadence is one trajectory): parallel cyclic reduction, one workgroup per
+                // trajectory, one lane per waypoint; beyond that its O(T log T) work and traffic lose against the
+                // waypoint-after-waypoint kernels.
+                if constexpr (D <= 8) {  // (full_step_form: the parallel-in-time form exists for 3 .. 8 joints)
+                    if (W <= 256 && g_pcr_lds) {  // the state in LDS: 256 x ((d(d+1)/2 + d + d^2) | 1) floats
+                        constexpr size_t kState = 256 * (size_t)((D * (D + 1) / 2 + D + D * D) | 1) * sizeof(float);
+                        CPPF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&full_solve_pcr_kernel<D, 256, true>),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)kState));
+                        if (g_pcr_split && (D <= kPcrSplitMaxD || t_pcr_lds == 3)) {  // see kPcrSplitMaxD; 3 forces the split form
+                            CPPF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&full_solve_pcr_kernel<D, 512, true, true>),
+                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)kState));
+                            hipLaunchKernelGGL((full_solve_pcr_kernel<D, 512, true, true>), dim3((unsigned)S), dim3(512), kState, st, robot->chain, prm, x_in,
+                                           virtual_configs, work_blocks, work_G, x_out, gate);
+                        } else
+                            hipLaunchKernelGGL((full_solve_pcr_kernel<D, 256, true>), dim3((unsigned)S), dim3(256), kState, st, robot->chain, prm, x_in,
+                                           virtual_configs, work_blocks, work_G, x_out, gate);
+                    } else if (W <= 256)
+                        hipLaunchKernelGGL((full_solve_pcr_kernel<D, 256>), dim3((unsigned)S), dim3(256), 0, st, robot->chain, prm, x_in,
+                                           virtual_configs, work_blocks, work_G, x_out, gate);
+                    else
+                        hipLaunchKernelGGL((full_solve_pcr_kernel<D, 512>), dim3((unsigned)S), dim3(512), 0, st, robot->chain, prm, x_in,
+                                           virtual_configs, work_blocks, work_G, x_out, gate);
+                }
+                break;
+            case FullStepForm::Rows:  // (every ndof; sixteen lanes per trajectory at 9 .. 12 joints, see rows_tpw)
+                if (rows_lds > 64 * 1024) {  // per device: set whenever it is needed, a host-side table update
+                    CPPF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&full_rows_eliminate_kernel<D>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+                    CPPF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&full_rows_substitute_kernel<D>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+                }
+                hipLaunchKernelGGL((full_rows_eliminate_kernel<D>), dim3(rows_wgs), dim3(64), rows_lds, st, prm, pris_mask, work_blocks,
+                                   work_G, work_y, gate);
+                hipLaunchKernelGGL((full_rows_substitute_kernel<D>), dim3(rows_wgs), dim3(64), rows_lds, st, prm, pris_mask, x_in,
+                                   work_blocks, work_G, work_y, x_out, gate);
+                break;
+            case FullStepForm::Wave:  // one trajectory per wavefront (8 x 8 lane tile), up to 8 joints
+                if constexpr (D <= 8)
+                    hipLaunchKernelGGL((full_solve_wave_kernel<D>), dim3((unsigned)S), dim3(64), 0, st, prm, pris_mask, x_in, work_blocks,
+                                       work_G, work_y, x_out);
+                break;
+            case FullStepForm::Lane:
+                // With the pose block the d x d blocks are J^T J + a small diagonal (rank 6 of 7, cond ~1e7): this kernel's Cholesky
+                // with floored pivots copes with that better than the explicit Gauss-Jordan inverse, so it keeps that case.
+                hipLaunchKernelGGL((full_solve_kernel<D>), lane_grid, dim3(64), 0, st, prm, pris_mask, x_in, work_blocks, work_G, work_y,
+                                   x_out, nullptr);
+                break;
         }
-        if constexpr (D <= 8) {  // one trajectory per wavefront; with the pose block the one-lane kernel keeps the case (see above)
-            if (!prm.use_pose) {
-                hipLaunchKernelGGL((full_solve_wave_kernel<D>), dim3((unsigned)S), dim3(64), 0, st, robot->chain, prm, x_in,
-                                   virtual_configs, work_blocks, work_G, work_y, x_out);
-                return check_launch();
-            }
-        }
-        // (9 .. 12 joints have no one-wavefront-per-trajectory form)
-        hipLaunchKernelGGL((full_solve_kernel<D>), dim3((unsigned)((S + 63) / 64)), dim3(64), 0, st, robot->chain, prm, x_in,
-                           virtual_configs, work_blocks, work_G, work_y, x_out, nullptr);
         return check_launch();
     });
 }
@@ -1638,8 +1636,7 @@ int cppf_lm_optimize_enqueue_pinned(const cppf_robot* robot, float* x, const flo
     if (params->diff.use_pose || params->diff.differencing_mode != 0)
         return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: the device-side optimiser loop takes a coupled step without pose block and without weighted differencing rows");
     // ... and so is the elimination of the coupled step: decided here, before the pose step's launch writes x_new
-    const FullStepForm form = full_step_form(robot, n, W, false, false);
-    if (!form.use_pcr && !form.use_rows) return fail(CPPF_ERR_UNSUPPORTED, kGatedFormRefusal);
+    if (!full_step_gateable(full_step_form(robot, n, W, false, false))) return fail(CPPF_ERR_UNSUPPORTED, kGatedFormRefusal);
     if (n_iterations == 0) return CPPF_OK;
     CPPF_ENTER(robot);
     prm.n = (int)n;

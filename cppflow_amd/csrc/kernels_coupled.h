@@ -8,12 +8,13 @@
 // A = J^T J + lambda I is block-tridiagonal with d x d blocks: pose and collision rows only touch their own waypoint's
 // block, the differencing row (t,j) = a_j * wrap(x[t+1,j] - x[t,j]) couples (t,j) with (t+1,j) through -a_j^2 on the
 // off-diagonal, virtual-config rows and lambda add to the diagonal.  So:
-//   full_blocks_kernel  (one lane per (seed, waypoint) row): the waypoint-local part  M_t = sum Js^T Js + sum alpha^2 g g^T,
-//                        m_t = Js^T es - sum alpha^2 dist g   (g = gradient of a colliding capsule distance)
-//   full_solve_kernel   (one lane per seed): adds the analytic differencing / virtual-config / lambda terms and runs the
-//                        block-tridiagonal elimination D'_t = A_tt - E G_{t-1} E,  G_t = D'_t^-1  (E = -diag(a^2)) forward and
-//                        back -- O(T d^3) per trajectory, any number of trajectories at once (the reference: one, :128).
-//                        Used when the pose block is on (rank-deficient blocks: Cholesky with floored pivots).
+//   full_blocks_kernel  (one lane per (seed, waypoint) row): the whole waypoint-local part, A_tt | b_t ready for elimination:
+//                        M_t = sum Js^T Js + sum alpha^2 g g^T,  m_t = Js^T es - sum alpha^2 dist g   (g = gradient of a colliding
+//                        capsule distance), plus (FullK::fold) the analytic differencing / virtual-config / lambda terms
+//                        (full_block_store): every elimination below but the parallel-in-time one only reads the blocks
+//   full_solve_kernel   (one lane per seed): the block-tridiagonal elimination D'_t = A_tt - E G_{t-1} E,  G_t = D'_t^-1
+//                        (E = -diag(a^2)) forward and back -- O(T d^3) per trajectory, any number of trajectories at once (the
+//                        reference: one, :128).  Used when the pose block is on (rank-deficient blocks: Cholesky with floored pivots).
 //   full_rows_eliminate_kernel + full_rows_substitute_kernel  (8 or 16 lanes per trajectory, one block row per lane, DPP
 //                        Gauss-Jordan, both ends of the path at once): the default beyond ~512 trajectories x 256 waypoints.
 //   full_solve_pcr_kernel (one workgroup per trajectory, parallel cyclic reduction over the waypoints, state in LDS for
@@ -24,8 +25,9 @@ struct FullK {
     float lm_lambda, a_pos, a_rot, a_diff, a_diff_pris, a_vq, a_self, a_env;
     int32_t use_pose, use_diff, use_vq, n_vq, use_self, use_env;
     int32_t S, W;
-    int32_t fold;  // full_blocks_kernel also adds the differencing / virtual-config / lambda terms of its own waypoint (what
-                   // full_rows_eliminate_kernel expects ready-made; the other elimination kernels add them in their own loops)
+    int32_t fold;  // full_blocks_kernel also adds the differencing / virtual-config / lambda terms of its own waypoint: every elimination
+                   // but the parallel-in-time one, which assembles them itself beside its block loads (one trajectory x 256 waypoints
+                   // is 1.3 us slower with the terms added at the end of the lone full_blocks_kernel workgroup)
     // The "satisfied" row options of LmResidualFns.get_r_and_J (cppflow/optimization_utils.py:514-533, 548-606; off in both
     // presets).  Every one of them is a per-row weight (and, for rows left at full weight, a shift of the residual towards zero by
     // the threshold): pose rows whose |error| is below the threshold are scaled down (:288-333); differencing rows whose |joint
@@ -49,6 +51,52 @@ template <int D>
 __device__ __forceinline__ void copy_row(const float* __restrict__ x, float* __restrict__ x_out, size_t row) {
 #pragma unroll
     for (int j = 0; j < D; ++j) x_out[row * D + j] = x[row * D + j];
+}
+// a_j^2 = (alpha_differencing * prismatic scaling)^2  (optimization_utils.py:607-612): the weight of joint j's differencing rows on
+// the diagonal, and E = -diag(a^2) the coupling of neighbouring waypoints; 0 without differencing rows
+__device__ __forceinline__ float diff_a2(const FullK& prm, bool pris) {
+    const float a = prm.use_diff ? prm.a_diff * (pris ? prm.a_diff_pris : 1.f) : 0.f;
+    return a * a;
+}
+template <int D>
+__device__ __forceinline__ void diff_a2(const FullK& prm, uint32_t pris_mask, float (&a2)[D]) {
+#pragma unroll
+    for (int j = 0; j < D; ++j) a2[j] = diff_a2(prm, (pris_mask >> j) & 1u);
+}
+
+// a pointer the compiler knows nothing about: loads through it are not merged with earlier loads of the same address (which would
+// keep a whole coupling block in registers between its two uses instead of reading it again where it is needed)
+__device__ __forceinline__ const float* opaque(const float* p) {
+    asm volatile("" : "+v"(p));
+    return p;
+}
+
+// index of element (i, j) in the packed upper triangle (row-major, D(D+1)/2 entries) of a symmetric D x D matrix
+template <int D>
+__device__ __forceinline__ constexpr int sym_index(int i, int j) {
+    const int a = i < j ? i : j, b = i < j ? j : i;
+    return a * D - a * (a - 1) / 2 + (b - a);
+}
+// packed upper triangle <-> full storage
+template <int D>
+__device__ __forceinline__ void load_sym(const float* src, float (&M)[D][D]) {
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int j = i; j < D; ++j) {
+            const float v = src[k++];
+            M[i][j] = v;
+            M[j][i] = v;
+        }
+}
+template <int D>
+__device__ __forceinline__ void store_sym(float* dst, const float (&M)[D][D]) {
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int j = i; j < D; ++j) dst[k++] = M[i][j];
 }
 
 // Weight (squared) and residual of ONE differencing row under the "satisfied" options.  rho = the wrapped joint change of the row,
@@ -194,22 +242,23 @@ __global__ __launch_bounds__(kBlock) void distance_jacobians_kernel(const ChainK
     }
 }
 
-// A_tt's diagonal and b_t's differencing / virtual-config terms (optimization_utils.py:574-640) of one row, in the same
-// operation order as the elimination kernels' own loops (prm.fold), then the row's packed block goes out
+// A_tt's diagonal and b_t's differencing / virtual-config terms (optimization_utils.py:574-640) of one row, then the row's packed
+// block goes out: with prm.fold D_t | y_t ready for elimination.  "Before / after me" is asked on the PATH (FullK::pin).
 template <class RB>
 __device__ __forceinline__ void full_block_store(const RB& rb, const FullK& prm, size_t row, const float (&q)[RB::D],
                                                  const float* __restrict__ x, const float* __restrict__ xv,
                                                  float (&M)[RB::D * (RB::D + 1) / 2], float (&m)[RB::D],
                                                  float* __restrict__ blocks, float* __restrict__ w2next) {
     constexpr int D = RB::D, NT = D * (D + 1) / 2;
+    // (t, has_next ... are declared in each branch: hoisted above the test, the 128-register Fetch build spills 12 B to scratch)
     if (prm.fold && prm.diff_mode != 0) {
-        // differencing rows carry individual weights: the two rows this waypoint is part of, (t, j) with its successor and
-        // (t-1, j) with its predecessor (the latter recomputed here: the same value bit for bit that waypoint t-1 computes), and
-        // the coupling of (t, j) goes to w2next for the elimination (full_solve_kernel<D, true>)
         const int t = (int)(row % (size_t)prm.W), T = prm.W;
         const bool has_next = t + 1 < T, has_prev = t > 0;
         const bool vq = prm.use_vq && (t < prm.n_vq || t >= T - prm.n_vq);
-        const float beta = prm.a_vq * prm.a_diff, beta2 = beta * beta;
+        const float beta = prm.a_vq * prm.a_diff, beta2 = beta * beta;  // r = beta * wrap(x - x_virtual), J = -beta I  (:430-484)
+        // differencing rows carry individual weights: the two rows this waypoint is part of, (t, j) with its successor and
+        // (t-1, j) with its predecessor (the latter recomputed here: the same value bit for bit that waypoint t-1 computes), and
+        // the coupling of (t, j) goes to w2next for the elimination (full_solve_kernel<D, true>)
         int k = 0;
 #pragma unroll
         for (int j = 0; j < D; ++j) {
@@ -230,7 +279,7 @@ __device__ __forceinline__ void full_block_store(const RB& rb, const FullK& prm,
         const int t = (int)(row % (size_t)prm.W), T = prm.W;
         const bool has_next = t + 1 < T, has_prev = t > 0;
         const bool vq = prm.use_vq && (t < prm.n_vq || t >= T - prm.n_vq);
-        const float beta = prm.a_vq * prm.a_diff, beta2 = beta * beta;
+        const float beta = prm.a_vq * prm.a_diff, beta2 = beta * beta;  // r = beta * wrap(x - x_virtual), J = -beta I  (:430-484)
         // the wrapped joint changes to the successor / from the predecessor / from the virtual configuration, each set through
         // wrap_pi_all (one rare branch per set instead of one per joint)
         float wn[D], wp[D], wv[D];
@@ -246,10 +295,10 @@ __device__ __forceinline__ void full_block_store(const RB& rb, const FullK& prm,
         int k = 0;
 #pragma unroll
         for (int j = 0; j < D; ++j) {
-            const float a = prm.use_diff ? prm.a_diff * (rb.pris(j) ? prm.a_diff_pris : 1.f) : 0.f;
-            const float a2 = a * a;
+            const float a2 = diff_a2(prm, rb.pris(j));
             M[k] += ((has_next ? 1.f : 0.f) + (has_prev ? 1.f : 0.f)) * a2 + (vq ? beta2 : 0.f) + prm.lm_lambda;
             k += D - j;
+            // J^T r of the differencing rows: +a^2 w_t at (t,j), -a^2 w_{t-1} at (t,j)   (w = wrapped joint change)
             if (has_next) m[j] = CPPF_FMA(a2, wn[j], m[j]);
             if (has_prev) m[j] = CPPF_FMA(-a2, wp[j], m[j]);
             if (vq && xv) m[j] = CPPF_FMA(-beta2, wv[j], m[j]);
@@ -593,81 +642,33 @@ __device__ __forceinline__ void spd_inverse(const float (&A)[D][D], float floor_
         }
 }
 
-// VAR: the differencing rows carry individual weights (the "satisfied" options): the blocks arrive with every waypoint-local term
-// folded in (full_block_store) and the coupling of waypoints t and t + 1 is -diag(w2next[t]) instead of the constant -diag(a^2).
+// VAR: the differencing rows carry individual weights (the "satisfied" options): the coupling of waypoints t and t + 1 is
+// -diag(w2next[t]) (full_block_store) instead of the constant -diag(a^2).
 template <int D, bool VAR = false>
-__global__ __launch_bounds__(64) void full_solve_kernel(const ChainK ch, const FullK prm, const float* __restrict__ x,
-                                                        const float* __restrict__ xv, const float* __restrict__ blocks,
-                                                        float* __restrict__ workG, float* __restrict__ worky,
-                                                        float* __restrict__ x_out, const float* __restrict__ w2next) {
+__global__ __launch_bounds__(64) void full_solve_kernel(const FullK prm, const uint32_t pris_mask, const float* __restrict__ x,
+                                                        const float* __restrict__ blocks, float* __restrict__ workG,
+                                                        float* __restrict__ worky, float* __restrict__ x_out,
+                                                        const float* __restrict__ w2next) {
     constexpr int NT = D * (D + 1) / 2;
     const int s = blockIdx.x * 64 + threadIdx.x;
     if (s >= prm.S) return;
     const int T = prm.W;
     const size_t base = (size_t)s * T;
-    float a2[D];  // a_j^2 = (alpha_differencing * prismatic scaling)^2  (optimization_utils.py:607-612)
-#pragma unroll
-    for (int j = 0; j < D; ++j) {
-        const float a = prm.use_diff ? prm.a_diff * (((ch.pris_mask >> j) & 1u) ? prm.a_diff_pris : 1.f) : 0.f;
-        a2[j] = a * a;
-    }
-    const float beta = prm.a_vq * prm.a_diff, beta2 = beta * beta;
+    float a2[D];
+    diff_a2<D>(prm, pris_mask, a2);
 
     const int f0 = full_t0(prm), f1 = full_t1(prm);  // the free waypoints (all of them without a pin)
-    float G[D][D], y[D], xp[D], xc[D], xn[D];
-    if (f0 < f1) load_x<D>(x, base + f0, xc);
-    if (f0 > 0 && f0 < f1) load_x<D>(x, base + f0 - 1, xp);
+    float G[D][D], y[D];
     // ---- forward elimination
     for (int t = f0; t < f1; ++t) {
         const float* blk = blocks + (base + t) * (NT + D);
         float A[D][D], b[D];
-        {
-            int k = 0;
+        load_sym<D>(blk, A);
 #pragma unroll
-            for (int i = 0; i < D; ++i)
-#pragma unroll
-                for (int j = i; j < D; ++j) {
-                    const float v = blk[k++];
-                    A[i][j] = v;
-                    A[j][i] = v;
-                }
-#pragma unroll
-            for (int j = 0; j < D; ++j) b[j] = blk[NT + j];
-        }
-        const bool has_next = t + 1 < T, has_prev = t > 0;  // on the path: the waypoint's own terms
-        const bool cpl_prev = t > f0;                       // in the system: the Schur coupling
+        for (int j = 0; j < D; ++j) b[j] = blk[NT + j];
+        const bool cpl_prev = t > f0;  // a predecessor in the SYSTEM: the Schur coupling
         if constexpr (VAR) {
-            if (has_prev) load_x<D>(w2next, base + t - 1, a2);  // the coupling with the predecessor
-        } else {
-            if (has_next) load_x<D>(x, base + t + 1, xn);
-            const float cnt = (has_next ? 1.f : 0.f) + (has_prev ? 1.f : 0.f);
-            const bool vq = prm.use_vq && (t < prm.n_vq || t >= T - prm.n_vq);
-            float wn[D], wp[D];
-#pragma unroll
-            for (int j = 0; j < D; ++j) {
-                wn[j] = has_next ? xn[j] - xc[j] : 0.f;
-                wp[j] = has_prev ? xc[j] - xp[j] : 0.f;
-            }
-            wrap_pi_all<D>(wn);
-            wrap_pi_all<D>(wp);
-#pragma unroll
-            for (int j = 0; j < D; ++j) {
-                A[j][j] += cnt * a2[j] + (vq ? beta2 : 0.f) + prm.lm_lambda;
-                // J^T r of the differencing rows: +a^2 w_t at (t,j), -a^2 w_{t-1} at (t,j)   (w = wrapped joint change)
-                if (has_next) b[j] = CPPF_FMA(a2[j], wn[j], b[j]);
-                if (has_prev) b[j] = CPPF_FMA(-a2[j], wp[j], b[j]);
-            }
-            if (vq) {  // r = beta * wrap(x - x_virtual), J = -beta I  (optimization_utils.py:430-484)
-                float v[D];
-                if (xv) {
-                    load_x<D>(xv, base + t, v);
-#pragma unroll
-                    for (int j = 0; j < D; ++j) v[j] = xc[j] - v[j];
-                    wrap_pi_all<D>(v);
-                }
-#pragma unroll
-                for (int j = 0; j < D; ++j) b[j] = CPPF_FMA(-beta2, xv ? v[j] : 0.f, b[j]);
-            }
+            if (t > 0) load_x<D>(w2next, base + t - 1, a2);  // the coupling with the predecessor (no pin with VAR: f0 = 0)
         }
         if (cpl_prev) {
             // D' = A - E G E ,  y = b - E G y_prev   with E = -diag(a2)
@@ -689,42 +690,19 @@ __global__ __launch_bounds__(64) void full_solve_kernel(const ChainK ch, const F
             for (int i = 0; i < D; ++i) y[i] = b[i];
         }
         spd_inverse<D>(A, prm.lm_lambda, G);
-        float* gout = workG + (base + t) * NT;
+        store_sym<D>(workG + (base + t) * NT, G);
         float* yout = worky + (base + t) * D;
-        {
-            int k = 0;
 #pragma unroll
-            for (int i = 0; i < D; ++i)
-#pragma unroll
-                for (int j = i; j < D; ++j) gout[k++] = G[i][j];
-#pragma unroll
-            for (int j = 0; j < D; ++j) yout[j] = y[j];
-        }
-#pragma unroll
-        for (int j = 0; j < D; ++j) {
-            xp[j] = xc[j];
-            xc[j] = xn[j];
-        }
+        for (int j = 0; j < D; ++j) yout[j] = y[j];
     }
     // ---- back substitution: delta_t = G_t (y_t - E delta_{t+1}) = G_t (y_t + a2 .* delta_{t+1})
     float dl[D];
 #pragma unroll
     for (int j = 0; j < D; ++j) dl[j] = 0.f;
     for (int t = f1 - 1; t >= f0; --t) {
-        const float* gin = workG + (base + t) * NT;
         const float* yin = worky + (base + t) * D;
         float rhs[D], Gt[D][D];
-        {
-            int k = 0;
-#pragma unroll
-            for (int i = 0; i < D; ++i)
-#pragma unroll
-                for (int j = i; j < D; ++j) {
-                    const float v = gin[k++];
-                    Gt[i][j] = v;
-                    Gt[j][i] = v;
-                }
-        }
+        load_sym<D>(workG + (base + t) * NT, Gt);
         if constexpr (VAR) {
             if (t + 1 < T) load_x<D>(w2next, base + t, a2);  // the coupling with the successor
         }
@@ -758,10 +736,10 @@ __global__ __launch_bounds__(64) void full_solve_kernel(const ChainK ch, const F
 // one fused update on all 64 lanes), matrix-vector products are a lane-local multiply plus a 3-step xor-butterfly over the
 // row or column bits.  Operands of step t+1 are requested before step t is computed, so their latency hides behind it.
 template <int D>
-__global__ __launch_bounds__(64) void full_solve_wave_kernel(const ChainK ch, const FullK prm, const float* __restrict__ x,
-                                                             const float* __restrict__ xv,
-                                                             const float* __restrict__ blocks, float* __restrict__ workG,
-                                                             float* __restrict__ worky, float* __restrict__ x_out) {
+__global__ __launch_bounds__(64) void full_solve_wave_kernel(const FullK prm, const uint32_t pris_mask,
+                                                             const float* __restrict__ x, const float* __restrict__ blocks,
+                                                             float* __restrict__ workG, float* __restrict__ worky,
+                                                             float* __restrict__ x_out) {
     static_assert(D <= 8, "one 8x8 tile per wavefront");
     constexpr int NT = D * (D + 1) / 2;
     const int s = blockIdx.x;
@@ -770,44 +748,24 @@ __global__ __launch_bounds__(64) void full_solve_wave_kernel(const ChainK ch, co
     const bool in = i < D && j < D, colv = j < D;
     const int T = prm.W;
     const size_t base = (size_t)s * T;
-    const int ii = i < j ? i : j, jj = i < j ? j : i;
-    const int tri = in ? ii * D - (ii * (ii - 1)) / 2 + (jj - ii) : 0;  // offset of (min, max) in the packed upper triangle
-    auto a2_of = [&](int c) {
-        if (!prm.use_diff || c >= D) return 0.f;
-        const float a = prm.a_diff * (((ch.pris_mask >> c) & 1u) ? prm.a_diff_pris : 1.f);
-        return a * a;
-    };
-    const float a2i = a2_of(i), a2j = a2_of(j);
-    const float beta = prm.a_vq * prm.a_diff, beta2 = beta * beta;
+    const int tri = in ? sym_index<D>(i, j) : 0;
+    const float a2i = i < D ? diff_a2(prm, (pris_mask >> i) & 1u) : 0.f, a2j = colv ? diff_a2(prm, (pris_mask >> j) & 1u) : 0.f;
     const int jc = colv ? j : 0;  // padded lanes read column 0 (their values are never used)
 
     // ---- forward elimination
     float G = 0.f, y_row = 0.f;
-    float xp = 0.f, xc = x[(base + 0) * D + jc], xn = T > 1 ? x[(base + 1) * D + jc] : 0.f;
     float Mij = blocks[(base + 0) * (NT + D) + tri], bj = blocks[(base + 0) * (NT + D) + NT + jc];
-    float vj = xv ? xv[(base + 0) * D + jc] : 0.f;
     for (int t = 0; t < T; ++t) {
         // request the operands of step t+1 now
-        float nM = 0.f, nb = 0.f, nx2 = 0.f, nv = 0.f;
+        float nM = 0.f, nb = 0.f;
         if (t + 1 < T) {
             nM = blocks[(base + t + 1) * (NT + D) + tri];
             nb = blocks[(base + t + 1) * (NT + D) + NT + jc];
-            if (xv) nv = xv[(base + t + 1) * D + jc];
         }
-        if (t + 2 < T) nx2 = x[(base + t + 2) * D + jc];
 
-        const bool has_next = t + 1 < T, has_prev = t > 0;
-        const bool vq = prm.use_vq && (t < prm.n_vq || t >= T - prm.n_vq);
+        const bool has_prev = t > 0;
         float A = in ? Mij : (i == j ? 1.f : 0.f);
-        if (in && i == j) A += ((has_next ? 1.f : 0.f) + (has_prev ? 1.f : 0.f)) * a2j + (vq ? beta2 : 0.f) + prm.lm_lambda;
-        float b = colv ? bj : 0.f;
-        if (colv) {
-            float w3[3] = {has_next ? xn - xc : 0.f, has_prev ? xc - xp : 0.f, (vq && xv) ? xc - vj : 0.f};
-            wrap_pi_all<3>(w3);  // (straight-line; this sits on the critical path of every elimination step)
-            if (has_next) b = CPPF_FMA(a2j, w3[0], b);
-            if (has_prev) b = CPPF_FMA(-a2j, w3[1], b);
-            if (vq && xv) b = CPPF_FMA(-beta2, w3[2], b);
-        }
+        const float b = colv ? bj : 0.f;
         float ycol = b;
         if (has_prev) {
             A = CPPF_FMA(-(a2i * a2j), G, A);  // D' = A - E G E   (padding: a2 = 0)
@@ -834,8 +792,7 @@ __global__ __launch_bounds__(64) void full_solve_wave_kernel(const ChainK ch, co
         if (in && i <= j) workG[(base + t) * NT + tri] = G;
         if (i == 0 && colv) worky[(base + t) * D + j] = ycol;
         y_row = __shfl(ycol, j * 8 + i, 64);  // lane (i,j) takes y_i from column i
-        xp = xc, xc = xn, xn = nx2;
-        Mij = nM, bj = nb, vj = nv;
+        Mij = nM, bj = nb;
     }
     // ---- back substitution: delta_t = G_t (y_t + a2 .* delta_{t+1})
     float dl = 0.f;  // delta_{t+1}, column-replicated
@@ -960,17 +917,10 @@ __device__ __forceinline__ RowsLane<D> rows_lane(const FullK& prm, uint32_t pris
     L.ubase = (size_t)wave * TPW * (size_t)T;
     const unsigned lrow = (unsigned)(s - wave * TPW) * (unsigned)T;
 #pragma unroll
-    for (int c = 0; c < D; ++c) {  // (min(r,c), max(r,c)) in the packed upper triangle
-        const int ii = L.rr < c ? L.rr : c, jj = L.rr < c ? c : L.rr;
-        L.offM[c] = lrow * STRIDE + (unsigned)(ii * D - (ii * (ii - 1)) / 2 + (jj - ii));
-    }
+    for (int c = 0; c < D; ++c) L.offM[c] = lrow * STRIDE + (unsigned)sym_index<D>(L.rr, c);
     L.offb = lrow * STRIDE + NT + L.rr, L.offG = lrow * (D * D) + L.rr * D, L.offy = lrow * D + L.rr;
     float a2c[D];
-#pragma unroll
-    for (int c = 0; c < D; ++c) {
-        const float a = prm.use_diff ? prm.a_diff * (((pris_mask >> c) & 1u) ? prm.a_diff_pris : 1.f) : 0.f;
-        a2c[c] = a * a;
-    }
+    diff_a2<D>(prm, pris_mask, a2c);
     L.a2r = 0.f;
 #pragma unroll
     for (int c = 0; c < D; ++c) L.a2r = L.r == c ? a2c[c] : L.a2r;
@@ -1215,25 +1165,12 @@ __global__ __launch_bounds__(64) void full_rows_substitute_kernel(const FullK pr
 // blocks in registers (250 of them); at 8 joints that form needs 340 and spilled 300 - 372 B per lane in the 512-lane
 // instantiations, so there the blocks are streamed from the state as they are used (236 - 250 registers, nothing spilled; at 7
 // joints the streamed form is 20 % slower than the row form -- 73 vs 59 us -- its loads sit in front of their uses).
-// index of element (i, j) in the packed upper triangle (row-major, D(D+1)/2 entries) of a symmetric D x D matrix
-template <int D>
-__device__ __forceinline__ constexpr int sym_index(int i, int j) {
-    const int a = i < j ? i : j, b = i < j ? j : i;
-    return a * D - a * (a - 1) / 2 + (b - a);
-}
-
 #ifndef CPPF_PCR_FENCE
 #define CPPF_PCR_FENCE() __builtin_amdgcn_sched_barrier(0)
 #endif
 #ifndef CPPF_PCR_LEAN
 #define CPPF_PCR_LEAN(D, BS, kLds, kSplit) ((D) >= 8)
 #endif
-// a pointer the compiler knows nothing about: loads through it are not merged with earlier loads of the same address (which would
-// keep a whole coupling block in registers between its two uses instead of reading it again where it is needed)
-__device__ __forceinline__ const float* opaque(const float* p) {
-    asm volatile("" : "+v"(p));
-    return p;
-}
 
 template <int D, int BS, bool kLds = false, bool kSplit = false>
 __global__ __launch_bounds__(BS) void full_solve_pcr_kernel(const ChainK ch, const FullK prm, const float* __restrict__ x,
@@ -1265,11 +1202,7 @@ __global__ __launch_bounds__(BS) void full_solve_pcr_kernel(const ChainK ch, con
             return workL + (base + u) * DD;
     };
     float a2[D];
-#pragma unroll
-    for (int j = 0; j < D; ++j) {
-        const float a = prm.use_diff ? prm.a_diff * (((ch.pris_mask >> j) & 1u) ? prm.a_diff_pris : 1.f) : 0.f;
-        a2[j] = a * a;
-    }
+    diff_a2<D>(prm, ch.pris_mask, a2);
     const float beta = prm.a_vq * prm.a_diff, beta2 = beta * beta;
 
     // ---- assemble row t in place: D_t = M_t + (cnt a^2 + [vq] beta^2 + lambda) I,  y_t = m_t + analytic J^T r terms
@@ -1308,7 +1241,7 @@ __global__ __launch_bounds__(BS) void full_solve_pcr_kernel(const ChainK ch, con
             for (int j = 0; j < D; ++j) b[j] = CPPF_FMA(-beta2, xo[j], b[j]);
         }
         {
-            int k = 0, kd = 0;
+            int k = 0;
 #pragma unroll
             for (int i = 0; i < D; ++i)
 #pragma unroll
@@ -1317,7 +1250,6 @@ __global__ __launch_bounds__(BS) void full_solve_pcr_kernel(const ChainK ch, con
                     if (j == i) v += cnt * a2[i] + (vq ? beta2 : 0.f) + prm.lm_lambda;  // diagonal of the packed upper triangle
                     dst[k++] = v;
                 }
-            (void)kd;
         }
 #pragma unroll
         for (int j = 0; j < D; ++j) dst[NT + j] = b[j];
@@ -1329,42 +1261,15 @@ __global__ __launch_bounds__(BS) void full_solve_pcr_kernel(const ChainK ch, con
     }
     __syncthreads();
 
-    auto load_sym = [&](const float* src, float (&M)[D][D]) {
-        int k = 0;
-#pragma unroll
-        for (int i = 0; i < D; ++i)
-#pragma unroll
-            for (int j = i; j < D; ++j) {
-                const float v = src[k++];
-                M[i][j] = v;
-                M[j][i] = v;
-            }
-    };
-
     // D_t^-1 is needed by both neighbours of t: every lane inverts its own block once per level and shares it through LDS
     __shared__ float s_P[TW][NT + 1];  // +1: odd row stride, no bank conflicts on the strided neighbour reads
-    auto load_inv = [&](int u, float (&M)[D][D]) {
-        int k = 0;
-#pragma unroll
-        for (int i = 0; i < D; ++i)
-#pragma unroll
-            for (int j = i; j < D; ++j) {
-                const float v = s_P[u][k++];
-                M[i][j] = v;
-                M[j][i] = v;
-            }
-    };
     for (int st = 1; st < f1 - f0; st <<= 1) {
         float nD[D][D], ny[D], nL[D][D];
         if (act && h == 0) {
             float Dn[D][D], P[D][D];
-            load_sym(st_blk(t), Dn);
+            load_sym<D>(st_blk(t), Dn);
             spd_inverse<D>(Dn, prm.lm_lambda, P);
-            int k = 0;
-#pragma unroll
-            for (int i = 0; i < D; ++i)
-#pragma unroll
-                for (int j = i; j < D; ++j) s_P[t][k++] = P[i][j];
+            store_sym<D>(s_P[t], P);
         }
         __syncthreads();
         if (act) {
@@ -1376,7 +1281,7 @@ __global__ __launch_bounds__(BS) void full_solve_pcr_kernel(const ChainK ch, con
             const int tm = do_m && t - st >= f0 ? t - st : -1, tp = do_p && t + st < f1 ? t + st : T;  // neighbours in the system
             if (st == 1) {
                 if (h == 0) {
-                    load_sym(own, nD);
+                    load_sym<D>(own, nD);
                 } else {
 #pragma unroll
                     for (int i = 0; i < D; ++i)
@@ -1398,7 +1303,7 @@ __global__ __launch_bounds__(BS) void full_solve_pcr_kernel(const ChainK ch, con
                 if (tm >= 0) {
                     float P[D][D];
                     const float* nb = st_blk(tm);
-                    load_inv(tm, P);
+                    load_sym<D>(s_P[tm], P);
 #pragma unroll
                     for (int i = 0; i < D; ++i) {
                         float al[D], accy = ny[i];
@@ -1417,7 +1322,7 @@ __global__ __launch_bounds__(BS) void full_solve_pcr_kernel(const ChainK ch, con
                 if (tp < T) {  // L_{t+1} = E (t + 1 > 0)
                     float P[D][D];
                     const float* nb = st_blk(tp);
-                    load_inv(tp, P);
+                    load_sym<D>(s_P[tp], P);
 #pragma unroll
                     for (int i = 0; i < D; ++i) {
                         float ga[D], accy = ny[i];
@@ -1447,7 +1352,7 @@ __global__ __launch_bounds__(BS) void full_solve_pcr_kernel(const ChainK ch, con
                 const int um = m_on ? tm : t, up = p_on ? tp : t;
                 if (m_any) {
                     float P[D][D];
-                    load_inv(um, P);
+                    load_sym<D>(s_P[um], P);
                     const float* Ltp = opaque(st_L(t));
 #pragma unroll
                     for (int i = 0; i < D; ++i) {
@@ -1471,7 +1376,7 @@ __global__ __launch_bounds__(BS) void full_solve_pcr_kernel(const ChainK ch, con
                 }
                 if (p_any) {
                     float P[D][D];
-                    load_inv(up, P);
+                    load_sym<D>(s_P[up], P);
                     const float* Lpp = opaque(st_L(up));
 #pragma unroll
                     for (int i = 0; i < D; ++i) {
@@ -1586,7 +1491,7 @@ __global__ __launch_bounds__(BS) void full_solve_pcr_kernel(const ChainK ch, con
                     // the row-by-row form (faster where its 280 registers are there: one lane per waypoint at <= 7 joints -- 61 vs 73 us
                     // for one Panda trajectory, profiles/r4_pcr_ab.txt): the own block first, nothing assigned conditionally
                     if (h == 0) {
-                        load_sym(own, nD);
+                        load_sym<D>(own, nD);
                     } else {
 #pragma unroll
                         for (int i = 0; i < D; ++i)
@@ -1601,7 +1506,7 @@ __global__ __launch_bounds__(BS) void full_solve_pcr_kernel(const ChainK ch, con
                 float P[D][D], Lt[D][D], Lm[D][D], ym[D];
                 const float* nb = st_blk(tm);
                 const float *Ltp = st_L(t), *Lmp = st_L(tm);
-                load_inv(tm, P);
+                load_sym<D>(s_P[tm], P);
 #pragma unroll
                 for (int i = 0; i < D; ++i)
 #pragma unroll
@@ -1642,7 +1547,7 @@ __global__ __launch_bounds__(BS) void full_solve_pcr_kernel(const ChainK ch, con
                 float P[D][D], Lp[D][D], yp[D];
                 const float* nb = st_blk(tp);
                 const float* Lpp = st_L(tp);
-                load_inv(tp, P);
+                load_sym<D>(s_P[tp], P);
 #pragma unroll
                 for (int i = 0; i < D; ++i)
 #pragma unroll
@@ -1709,7 +1614,7 @@ __global__ __launch_bounds__(BS) void full_solve_pcr_kernel(const ChainK ch, con
     if (act && h == 0) {
         float Dn[D][D], P[D][D], xr[D];
         const float* own = st_blk(t);
-        load_sym(own, Dn);
+        load_sym<D>(own, Dn);
         spd_inverse<D>(Dn, prm.lm_lambda, P);
         load_x<D>(x, base + t, xr);
 #pragma unroll

@@ -10,10 +10,11 @@ constexpr int kBlock = 256;
 #include "kernels_chain.h"
 #include "kernels_collision.h"
 #include "kernels_fused.h"
+#include "kernels_scene.h"
 #include "kernels_coupled.h"
 }
 using namespace dev;
-template __global__ void dev::full_solve_wave_kernel<7>(const ChainK, const FullK, const float*, const float*, const float*, float*, float*, float*);
+template __global__ void dev::full_solve_wave_kernel<7>(const FullK, const uint32_t, const float*, const float*, float*, float*, float*);
 template __global__ void dev::full_blocks_kernel<StaRobot<gen::Panda>>(const ChainK, const CollK, const FullK, const float*, const float*, const float*, float*, float*, const StepGateK);
 template __global__ void dev::full_blocks_kernel<DynRobot<7>>(const ChainK, const CollK, const FullK, const float*, const float*, const float*, float*, float*, const StepGateK);
 template __global__ void dev::full_rows_eliminate_kernel<7>(const FullK, const uint32_t, const float*, float*, float*, const StepGateK);

@@ -11,6 +11,7 @@ constexpr int kBlock = 256;
 #include "kernels_chain.h"
 #include "kernels_collision.h"
 #include "kernels_fused.h"
+#include "kernels_scene.h"
 #include "kernels_coupled.h"
 }
 using namespace dev;
