@@ -193,6 +193,16 @@ float cull_threshold(double reach) {
     return f;
 }
 
+// certain-hit threshold on the centre's squared distance from a cuboid: max(r - 1 cm, 0)^2 (1 - 1e-4), rounded DOWN
+// (gen_robots.py: inside_threshold; env_item_undecided in kernels_collision.h)
+float inside_threshold(float r) {
+    const double m = (double)r - 0.01 > 0.0 ? (double)r - 0.01 : 0.0;
+    const double y = m * m * (1.0 - 1e-4);
+    float f = (float)y;
+    if ((double)f > y) f = std::nextafterf(f, 0.f);
+    return f;
+}
+
 // Travel bounds of cppf_motion_clearance (kernels_motion.h): rho[j][c] >= the distance of any point of capsule c from the axis of
 // revolute joint j <= cap_link[c] -- the translations of the fixed transforms between joint j and the capsule's link, the largest
 // excursion of every prismatic joint in between, and the capsule's own extent from its link's origin; 1 for a prismatic joint
@@ -525,6 +535,8 @@ int cppf_robot_create(const cppf_robot_desc* desc, int device, cppf_robot** out)
         co.cap_link[c] = (int8_t)desc->cap_link[c];
         co.cap_thr[c] = sqrt_threshold(desc->cap_r[c]);
         co.cap_cull[c] = cull_threshold(cap_half_length(*desc, c) + (double)desc->cap_r[c]);
+        co.cap_in[c] = inside_threshold(desc->cap_r[c]);
+        co.cap_box[c] = cull_threshold((double)desc->cap_r[c]);
     }
     // cap_begin[l+1] = first capsule whose link >= l
     for (int l = -1; l <= d; ++l) {

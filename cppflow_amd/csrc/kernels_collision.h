@@ -111,6 +111,66 @@ __device__ __forceinline__ uint32_t cuboids_in_reach(const CollK& co, const floa
     return near;
 }
 
+// ---- lane classification (mask-only environment loop) ---------------------------------------------------------------------------
+// The exact capsule-cuboid test runs for a whole wavefront, so one lane within the bounding sphere used to buy it for all 64.  The
+// env bit of a row is an OR over its (capsule, cuboid) items, which lets every lane be DECIDED for an item before the exact
+// arithmetic, from the centre distance pd = point_box_dist2(centre) the sphere test computes anyway:
+//   already hit    the lane's bit is set by an earlier item: nothing later can change it;
+//   certain miss   pd > cap_cull = (h + r + 1 cm)^2 (1 + 1e-4)                      (the bounding sphere, as before);
+//   certain hit    pd < cap_in = max(r - 1 cm, 0)^2 (1 - 1e-4): the segment contains its centre, so its distance is at most
+//                  sqrt(pd), 1 cm inside the exact test's threshold; the lane's bit is set.  r <= 1 cm: cap_in = 0, never;
+//                  (its lanes are within reach, so it is asked for only where some lane is within reach and not yet hit);
+//   certain miss   (second level, behind the same ballot)  the squared distance between the cuboid and the
+//                  segment's bounding box [C - |H|, C + |H|], per axis max(|e_i| - |H_i|, 0) with e = C - clamp(C, lo, hi) of pd,
+//                  exceeds cap_box = (r + 1 cm)^2 (1 + 1e-4): a lower bound of the segment's distance.
+// The exact test runs only if the ballot of UNDECIDED lanes is non-zero, unchanged, and its bit is OR-ed into every lane as before:
+// a decided lane gets from it the bit it already has (the 1 cm is the margin cull_far relies on; tests/test_capsule_box_bounds.py
+// checks every rule against the exact function), so no mask bit changes.  The lane state is kept as ballots -- wave-uniform
+// 64-bit masks in SGPRs: `hit` (lanes whose env bit is set) costs no VGPR and the rules one v_cmp each, the rest is scalar.
+// NaN: the exact test reports no hit as soon as ONE component of C or H is NaN (its closest point is fma(H, u, C) per axis).  Both
+// miss rules agree with that whatever they compare; pd < cap_in implies an ordered C, so the hit rule also asks for an ordered H
+// (behind the ballot of the lanes it fires for).  A NaN pd fails both comparisons: the lane stays undecided and the exact test runs, as it did.
+// Returns the ballot of the lanes still undecided for this item.
+__device__ __forceinline__ uint64_t env_item_undecided(const float (&c)[3], const float (&h)[3], const float* __restrict__ lo,
+                                                       const float* __restrict__ hi, float cull2, float in2, float box2,
+                                                       uint64_t& hit) {
+    const float ex = c[0] - clampf(c[0], lo[0], hi[0]), ey = c[1] - clampf(c[1], lo[1], hi[1]),
+                ez = c[2] - clampf(c[2], lo[2], hi[2]);
+    const float pd = CPPF_FMA(ez, ez, CPPF_FMA(ey, ey, ex * ex));  // == point_box_dist2(c, lo, hi)
+    const uint64_t reach = __builtin_amdgcn_ballot_w64(!(pd > cull2));
+    uint64_t und = reach & ~hit;
+    if (und) {  // (a certain hit lies within reach, so nothing is lost by asking for it only here)
+        uint64_t in = __builtin_amdgcn_ballot_w64(pd < in2);
+        if (in) in &= __builtin_amdgcn_ballot_w64((h[0] + h[1]) + h[2] == (h[0] + h[1]) + h[2]);
+        hit |= in;
+        const float gx = fmaxf(fabsf(ex) - fabsf(h[0]), 0.f), gy = fmaxf(fabsf(ey) - fabsf(h[1]), 0.f),
+                    gz = fmaxf(fabsf(ez) - fabsf(h[2]), 0.f);
+        und &= ~(in | __builtin_amdgcn_ballot_w64(CPPF_FMA(gz, gz, CPPF_FMA(gy, gy, gx * gx)) > box2));
+    }
+    return und;
+}
+
+// The mask-only form of cuboids_in_reach: bit o set when some lane is still undecided for (this capsule, cuboid o).  `hit` gains
+// the certain hits; `open` returns the lanes undecided for ANY cuboid of this capsule -- once they are all hit the remaining
+// exact tests of the capsule have nobody left to ask for them.
+__device__ __forceinline__ uint32_t cuboids_undecided(const CollK& co, const float (&c)[3], const float (&h)[3], float cull2,
+                                                      float in2, float box2, uint64_t& hit, uint64_t& open) {
+    uint32_t near = 0u;
+    open = 0ull;
+    for (int o = 0; o < co.nobs; ++o) {
+        const uint64_t und = env_item_undecided(c, h, co.obs_lo[o], co.obs_hi[o], cull2, in2, box2, hit);
+        if (und) near |= 1u << o;
+        open |= und;
+    }
+    return near;
+}
+
+// this lane's bit of a ballot
+__device__ __forceinline__ int lane_bit(uint64_t mask) {
+    const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    return (int)((lane < 32u ? (uint32_t)mask >> lane : (uint32_t)(mask >> 32) >> (lane - 32u)) & 1u);
+}
+
 // IN_LIMITS: the caller guarantees that the row's q lies inside the joint limits [lo, hi] (or is NaN, which hits nothing either way).
 // A mask-only stage then drops, at compile time, the self pairs certified never to come within 1 cm of touching anywhere in the
 // joint box (Table::pair_never, cppflow_amd/gen_robots.py): sphere test and exact test both go.
@@ -158,26 +218,33 @@ __device__ __forceinline__ CollOut collide_tests_static(const CollK& co,
     r.min_env = INFINITY;
     r.env_hit = 0;
     if (do_env) {
+        uint64_t hit = 0ull, open = ~0ull;  // mask-only: the lanes whose env bit is set / still undecided for this capsule (env_item_undecided)
 #pragma unroll
         for (int c = 0; c < T::L; ++c) {
             uint32_t near = ~0u;
             if constexpr (!WANT_MIN) {
                 if (!((live >> c) & 1u)) continue;  // (one scalar test)
-                near = cuboids_in_reach(co, wc[c], T::cap_cull[c]);
+                near = cuboids_undecided(co, wc[c], wh[c], T::cap_cull[c], T::cap_in[c], T::cap_box[c], hit, open);
                 if (near == 0u) continue;
             }
             for (int o = 0; o < co.nobs; ++o) {
                 if (!((near >> o) & 1u)) continue;
+                if constexpr (!WANT_MIN) {
+                    if ((open & ~hit) == 0ull) break;
+                }
                 const float d2 = seg_box_dist2(wc[c], wh[c], co.obs_lo[o], co.obs_hi[o]);
                 if constexpr (WANT_MIN) {
                     const float v = __builtin_sqrtf(d2) - T::cap_r[c];
                     r.min_env = v < r.min_env ? v : r.min_env;
                 } else {
-                    r.env_hit |= d2 < T::cap_thr[c];
+                    hit |= __builtin_amdgcn_ballot_w64(d2 < T::cap_thr[c]);
                 }
             }
         }
-        if constexpr (WANT_MIN) r.env_hit = r.min_env < 0.f;
+        if constexpr (WANT_MIN)
+            r.env_hit = r.min_env < 0.f;
+        else
+            r.env_hit = lane_bit(hit);
     }
     return r;
 }
@@ -221,26 +288,33 @@ __device__ __forceinline__ CollOut collide_from_lds(const CollK& co, const float
     r.min_env = INFINITY;
     r.env_hit = 0;
     if (do_env) {
+        uint64_t hit = 0ull, open = ~0ull;  // mask-only: as in collide_tests_static
         for (int c = 0; c < co.ncaps; ++c) {
             float wc[3], wh[3];
             lds_capsule(lds, tid, c, wc, wh);
             uint32_t near = ~0u;
             if constexpr (!WANT_MIN) {
-                near = cuboids_in_reach(co, wc, co.cap_cull[c]);
+                near = cuboids_undecided(co, wc, wh, co.cap_cull[c], co.cap_in[c], co.cap_box[c], hit, open);
                 if (near == 0u) continue;
             }
             for (int o = 0; o < co.nobs; ++o) {
                 if (!((near >> o) & 1u)) continue;
+                if constexpr (!WANT_MIN) {
+                    if ((open & ~hit) == 0ull) break;
+                }
                 const float d2 = seg_box_dist2(wc, wh, co.obs_lo[o], co.obs_hi[o]);
                 if constexpr (WANT_MIN) {
                     const float v = __builtin_sqrtf(d2) - co.cap_r[c];
                     r.min_env = v < r.min_env ? v : r.min_env;
                 } else {
-                    r.env_hit |= d2 < co.cap_thr[c];
+                    hit |= __builtin_amdgcn_ballot_w64(d2 < co.cap_thr[c]);
                 }
             }
         }
-        if constexpr (WANT_MIN) r.env_hit = r.min_env < 0.f;  // collision_detection.py:39-43 (an OR over cuboids of min < 0)
+        if constexpr (WANT_MIN)
+            r.env_hit = r.min_env < 0.f;  // collision_detection.py:39-43 (an OR over cuboids of min < 0)
+        else
+            r.env_hit = lane_bit(hit);
     }
     return r;
 }

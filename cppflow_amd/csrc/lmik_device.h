@@ -47,6 +47,8 @@ struct CollK {
     float cap_thr[CPPF_MAX_CAPSULES];     // the same for r alone (capsule vs cuboid)
     float pair_cull[CPPF_MAX_PAIRS];      // broad phase: (h_a + h_b + r_a + r_b + 1 cm)^2 (1 + 1e-4), h = half length
     float cap_cull[CPPF_MAX_CAPSULES];    // broad phase: (h + r + 1 cm)^2 (1 + 1e-4)
+    float cap_in[CPPF_MAX_CAPSULES];      // certain hit of a cuboid by the centre's distance: max(r - 1 cm, 0)^2 (1 - 1e-4), rounded down
+    float cap_box[CPPF_MAX_CAPSULES];     // certain miss by the segment's bounding box: (r + 1 cm)^2 (1 + 1e-4)  (kernels_collision.h)
     uint8_t pair_a[CPPF_MAX_PAIRS];
     uint8_t pair_b[CPPF_MAX_PAIRS];
     float obs_lo[CPPF_MAX_OBSTACLES][3];  // world-frame box corners

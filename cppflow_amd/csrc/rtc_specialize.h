@@ -154,9 +154,9 @@ std::string rtc_table_source(const cppf_robot& rb) {
     vec3s("cap_p1", d.cap_p1);
     vec3s("cap_c", co.cap_c);
     vec3s("cap_h", co.cap_h);
-    std::vector<float> cap_r(Lm, 0.f), cap_thr(Lm, 0.f), cap_cull(Lm, 0.f), pair_thr(Pm, 0.f), pair_cull(Pm, 0.f), cap_a(Lm, 0.f), cap_ia(Lm, 0.f);
+    std::vector<float> cap_r(Lm, 0.f), cap_thr(Lm, 0.f), cap_cull(Lm, 0.f), cap_in(Lm, 0.f), cap_box(Lm, 0.f), pair_thr(Pm, 0.f), pair_cull(Pm, 0.f), cap_a(Lm, 0.f), cap_ia(Lm, 0.f);
     for (int c = 0; c < L; ++c)
-        cap_r[c] = d.cap_r[c], cap_thr[c] = co.cap_thr[c], cap_cull[c] = co.cap_cull[c], cap_a[c] = co.cap_a[c], cap_ia[c] = co.cap_ia[c];
+        cap_r[c] = d.cap_r[c], cap_thr[c] = co.cap_thr[c], cap_cull[c] = co.cap_cull[c], cap_in[c] = co.cap_in[c], cap_box[c] = co.cap_box[c], cap_a[c] = co.cap_a[c], cap_ia[c] = co.cap_ia[c];
     for (int p = 0; p < P; ++p) pair_thr[p] = co.pair_thr[p], pair_cull[p] = co.pair_cull[p];
     o << "    static constexpr float cap_a[" << Lm << "] = " << rtc_array(cap_a.begin(), cap_a.end()) << ";\n";
     o << "    static constexpr float cap_ia[" << Lm << "] = " << rtc_array(cap_ia.begin(), cap_ia.end()) << ";\n";
@@ -165,6 +165,8 @@ std::string rtc_table_source(const cppf_robot& rb) {
     o << "    static constexpr float cap_thr[" << Lm << "] = " << rtc_array(cap_thr.begin(), cap_thr.end()) << ";\n";
     o << "    static constexpr float pair_cull[" << Pm << "] = " << rtc_array(pair_cull.begin(), pair_cull.end()) << ";\n";
     o << "    static constexpr float cap_cull[" << Lm << "] = " << rtc_array(cap_cull.begin(), cap_cull.end()) << ";\n";
+    o << "    static constexpr float cap_in[" << Lm << "] = " << rtc_array(cap_in.begin(), cap_in.end()) << ";\n";
+    o << "    static constexpr float cap_box[" << Lm << "] = " << rtc_array(cap_box.begin(), cap_box.end()) << ";\n";
     for (int side = 0; side < 2; ++side) {
         o << "    static constexpr int pair_" << (side ? "b" : "a") << "[" << Pm << "] = {";
         for (int p = 0; p < Pm; ++p) o << (p ? ", " : "") << (P ? d.pairs[p][side] : 0);

@@ -62,6 +62,17 @@ def cull_threshold(reach: float) -> np.float32:
     return f
 
 
+def inside_threshold(r) -> np.float32:
+    """Certain-hit threshold on the squared distance of a capsule's CENTRE from a cuboid: max(r - 1 cm, 0)^2 (1 - 1e-4), rounded down
+    to fp32 -- the mirror image of cull_threshold.  The segment contains its centre, so a centre closer than r - 1 cm puts the exact
+    test 1 cm inside its threshold; r <= 1 cm gives 0 and `d2 < 0` never holds (env_item_undecided in csrc/kernels_collision.h)."""
+    y = max(float(r) - 0.01, 0.0) ** 2 * (1.0 - 1e-4)
+    f = np.float32(y)
+    if float(f) > y:
+        f = np.nextafter(f, np.float32(0.0))
+    return f
+
+
 def capsule_centred(cap_p0, cap_p1):
     """(centre, half-axis, |h|^2, 1 / |h|^2) of every capsule as the kernels use them: double arithmetic on the fp32 end points,
     each rounded to fp32 once -- c = 0.5 (p0 + p1), h = 0.5 (p1 - p0), a = (h0 h0 + h1 h1) + h2 h2 over the ROUNDED h, 1 / a (0 when a < 2^-100).
@@ -227,6 +238,10 @@ def emit_robot(name: str, ch: CanonicalChain) -> str:
     cap_cull = [cull_threshold(half[c] + float(r32[c])) for c in range(L)] if L else [0]
     s.append(f"    static constexpr float pair_cull[{Pm}] = {_arr(pair_cull)};  // broad phase, pairs")
     s.append(f"    static constexpr float cap_cull[{Lm}] = {_arr(cap_cull)};  // broad phase, capsule vs cuboid")
+    cap_in = [inside_threshold(r) for r in r32] if L else [0]
+    cap_box = [cull_threshold(float(r)) for r in r32] if L else [0]
+    s.append(f"    static constexpr float cap_in[{Lm}] = {_arr(cap_in)};  // certain hit: the centre within r - 1 cm of a cuboid")
+    s.append(f"    static constexpr float cap_box[{Lm}] = {_arr(cap_box)};  // certain miss: the segment's bounding box beyond r + 1 cm")
     s.append(f"    static constexpr int pair_a[{Pm}] = {{" + ", ".join(str(int(v)) for v in (ch.pairs[:, 0] if P else [0])) + "};")
     s.append(f"    static constexpr int pair_b[{Pm}] = {{" + ", ".join(str(int(v)) for v in (ch.pairs[:, 1] if P else [0])) + "};")
     never = pair_never(ch) if P else [False]

@@ -72,3 +72,70 @@ saved_self = never.sum() * SPHERE + executed[never].sum() * EXACT
 saved_env = len(dead) * len(boxes) * POINT_BOX
 print(f"predicted VALU per row removed: self {saved_self:.0f} ({int(never.sum())} x {SPHERE} + {executed[never].sum():.3f} x {EXACT}), "
       f"env {saved_env:.0f} ({len(dead)} x {len(boxes)} x {POINT_BOX}), together {saved_self + saved_env:.0f}")
+
+# ---- per-lane classification in front of the exact capsule-cuboid test (env_item_undecided, csrc/kernels_collision.h) ------------------
+# The stage as it runs: capsules outermost, the capsules that reach no cuboid skipped; per capsule first every cuboid is classified,
+# then the exact test runs for the cuboids some lane of the wavefront is still undecided for, and stops once every lane that was
+# undecided for this capsule is hit.  An executed test ORs its bit into all 64 lanes.  Rules: 1 a lane whose env bit is set stops
+# asking; 3 the centre within r - 1 cm is a hit; 4 the segment's bounding box beyond r + 1 cm is a miss; ideal: only lanes whose exact
+# clearance is within +-1 cm ask.  Rules 3 and 4 are evaluated only for the items some lane is within reach of and not yet hit
+# (`surviving items`; a certain hit lies within reach, so rule 3 loses nothing by that), and cost their VALU there alone.
+SEG_BOX, RULE3, RULE4 = 175, 2, 12
+live_caps = [k for k in range(ch.n_capsules) if k not in dead]
+hv = 0.5 * (ep[..., 3:] - ep[..., :3])
+clear = np.stack([np.asarray(H.oracle32(name).env_dists(x, lo, hi)) for lo, hi in boxes], axis=-1)  # [rows, L, O]: distance - r
+r32 = ch.cap_r.astype(np.float32)
+cull = [float(gen_robots.cull_threshold(half[k] + float(r32[k]))) for k in range(ch.n_capsules)]
+cin = [float(gen_robots.inside_threshold(r32[k])) for k in range(ch.n_capsules)]
+cbox = [float(gen_robots.cull_threshold(float(r32[k]))) for k in range(ch.n_capsules)]
+
+
+def wave_any(m):
+    return np.repeat(m.reshape(-1, 64).any(1), 64)
+
+
+def lane_census(rules):
+    hit = np.zeros(x.shape[0], dtype=bool)
+    tests = surviving = 0.0
+    for k in live_caps:
+        und = []
+        for o, (lo, hi) in enumerate(boxes):
+            e = c[:, k] - np.clip(c[:, k], lo, hi)
+            pd = (e**2).sum(-1)
+            if rules == "ideal":
+                hit |= clear[:, k, o] < -0.01
+                und.append((np.abs(clear[:, k, o]) <= 0.01) & ~hit)
+                continue
+            u = pd <= cull[k]
+            if 1 in rules:
+                u &= ~hit
+            ask = wave_any(u)
+            if 3 in rules or 4 in rules:
+                surviving += ask.mean()
+            if 3 in rules:
+                hit |= ask & (pd < cin[k])
+                u &= ~hit
+            if 4 in rules:
+                gap = np.maximum(np.abs(e) - np.abs(hv[:, k]), 0.0)
+                u &= ~(ask & ((gap**2).sum(-1) > cbox[k]))
+            und.append(u)
+        open_ = np.logical_or.reduce(und)
+        for o in range(len(boxes)):
+            run = wave_any(und[o])
+            if rules:  # (today's stage has no early stop)
+                run &= wave_any(open_ & ~hit)
+            tests += run.mean()
+            hit |= run & (clear[:, k, o] < 0)
+    assert np.array_equal(hit, (clear[:, live_caps] < 0).any((1, 2))), "the classification changed a mask bit"
+    return tests, surviving
+
+
+items = len(live_caps) * len(boxes)
+print(f"\nexact capsule-cuboid tests per row by rule ({items} live items per row; {SEG_BOX} VALU per exact test, {RULE3} per surviving item for rule 3, "
+      f"{RULE4} per surviving item for rule 4):")
+base_tests = None
+for label, rules in (("today", ()), ("rule 1", (1,)), ("rules 1+3", (1, 3)), ("rules 1+4", (1, 4)), ("rules 1+3+4", (1, 3, 4)), ("ideal 1 cm bound", "ideal")):
+    t, s = lane_census(rules)
+    base_tests = t if base_tests is None else base_tests
+    added = ((RULE3 if 3 in rules else 0) + (RULE4 if 4 in rules else 0)) * s if rules != "ideal" else 0.0
+    print(f"  {label:18s} tests per row {t:.3f}   surviving items per row {s:.3f}   predicted net VALU per row {(t - base_tests) * SEG_BOX + added:+.0f}")
