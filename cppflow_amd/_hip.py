@@ -191,6 +191,17 @@ MOTION_RESOLVE_MAX_DEPTH = 16  # CPPF_MOTION_RESOLVE_MAX_DEPTH
 MOTION_RESOLVE_MAX_FRONTIER = 4096  # CPPF_MOTION_RESOLVE_MAX_FRONTIER
 
 
+VOXEL_MAX_DIM = 1024  # CPPF_VOXEL_MAX_DIM
+VOXEL_MAX_CELLS = 1 << 24  # CPPF_VOXEL_MAX_CELLS
+VOXEL_MAX_SELF = 16  # CPPF_VOXEL_MAX_SELF
+
+
+class VoxelGrid(ctypes.Structure):
+    """struct cppf_voxel_grid"""
+
+    _fields_ = [("origin", _f * 3), ("voxel_m", _f), ("dims", _i32 * 3)]
+
+
 class LmBatchItem(ctypes.Structure):
     """struct cppf_lm_batch_item: one problem of a batched fused launch (cppf_lm_batch_create)"""
 
@@ -229,6 +240,17 @@ SIGNATURES = {
     "cppf_scene_env_collisions": (
         ctypes.c_int,
         [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp],
+    ),
+    "cppf_voxel_scene_workspace_bytes": (ctypes.c_int, [ctypes.POINTER(VoxelGrid), ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
+    "cppf_scene_from_points": (
+        ctypes.c_int,
+        [_vp, _vp, ctypes.c_int, ctypes.POINTER(VoxelGrid), _vp, ctypes.c_int, ctypes.c_float, ctypes.c_int, _vp, _vp, _vp, _vp,
+         ctypes.c_size_t, _vp],
+    ),
+    "cppf_scene_from_depth": (
+        ctypes.c_int,
+        [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_f), ctypes.POINTER(_f), ctypes.c_float, ctypes.c_float,
+         ctypes.POINTER(VoxelGrid), _vp, ctypes.c_int, ctypes.c_float, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp],
     ),
     "cppf_motion_workspace_bytes": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
     "cppf_motion_clearance": (

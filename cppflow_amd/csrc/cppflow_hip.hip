@@ -65,6 +65,7 @@ constexpr int kBlock = CPPF_BLOCK;
 #include "kernels_quad.h"
 #include "kernels_eval.h"
 #include "kernels_scene.h"  // (ahead of the coupled step: its scene form shares the box / broadcast helpers)
+#include "kernels_voxel.h"  // (scenes from sensor data: reads nothing of the above but the capsule FK)
 #include "kernels_motion.h"
 #include "kernels_motion_resolve.h"
 #include "kernels_coupled.h"
@@ -1948,6 +1949,183 @@ int cppf_scene_env_collisions(const cppf_robot* robot, const float* q, int S, in
     hipLaunchKernelGGL(scene_finish_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, sc.row_key, obs_key, (int)n, n_obs,
                        want_min ? 1 : 0, env_mask, min_env, nearest_obs, obs_min);
     return check_launch();
+}
+
+// ---- scenes from sensor data (kernels_voxel.h) ----------------------------------------------------------------------------------------
+namespace {
+// the workspace, every part a multiple of 16 bytes: bitset | row_heads | row_cells | row_offset | self segments
+struct VoxelLayout {
+    int wpr, rows;
+    size_t bits, row, segs, total;  // bytes: the bitset, ONE per-row array, the segments, everything (+ 16: never 0)
+};
+inline size_t up16(size_t b) { return (b + 15) / 16 * 16; }
+
+// the grid's rules (cppflow_hip.h, "Grid" and "Planes"); fills *lay where given
+int voxel_check_grid(const cppf_voxel_grid* grid, int n_self, VoxelLayout* lay) {
+    CPPF_REQUIRE(grid, "grid is NULL");
+    for (int k = 0; k < 3; ++k)
+        CPPF_REQUIRE(grid->dims[k] >= 1 && grid->dims[k] <= CPPF_VOXEL_MAX_DIM, "grid dims out of range (1 .. CPPF_VOXEL_MAX_DIM each)");
+    const int wpr = (grid->dims[0] + 63) / 64;
+    const size_t rows = (size_t)grid->dims[1] * grid->dims[2];
+    CPPF_REQUIRE((size_t)wpr * 64 * rows <= (size_t)CPPF_VOXEL_MAX_CELLS, "grid has too many cells (64 ceil(nx / 64) ny nz <= CPPF_VOXEL_MAX_CELLS)");
+    CPPF_REQUIRE(n_self >= 0 && n_self <= CPPF_VOXEL_MAX_SELF, "n_self out of range (0 .. CPPF_VOXEL_MAX_SELF)");
+    CPPF_REQUIRE(std::isfinite(grid->voxel_m) && grid->voxel_m > 0.f, "voxel_m must be positive and finite");
+    for (int k = 0; k < 3; ++k) {
+        float prev = 0.f;
+        for (int i = 0; i <= grid->dims[k]; ++i) {
+            // (volatile: two roundings whatever the host compiler would like to contract)
+            volatile float step = (float)i * grid->voxel_m;
+            volatile float plane = grid->origin[k] + step;
+            const float pl = plane;
+            CPPF_REQUIRE(std::isfinite(pl) && (i == 0 || pl > prev), "the grid's planes are not finite and strictly increasing in fp32");
+            prev = pl;
+        }
+    }
+    if (lay) {
+        lay->wpr = wpr;
+        lay->rows = (int)rows;
+        lay->bits = up16(rows * wpr * sizeof(unsigned long long));
+        lay->row = up16(rows * sizeof(int32_t));
+        lay->segs = up16((size_t)n_self * CPPF_MAX_CAPSULES * 8 * sizeof(float));
+        lay->total = lay->bits + 3 * lay->row + lay->segs + 16;
+    }
+    return CPPF_OK;
+}
+
+struct VoxelSource {
+    const float* points;  // the point form, else NULL
+    VoxelDepthK cam;      // the depth form
+    size_t n;
+};
+
+// everything behind the source's own checks: the shared refusals, then the launches
+int voxel_scene_run(const cppf_robot* robot, const VoxelSource& src, const cppf_voxel_grid* grid, const float* q_self, int n_self,
+                    float self_margin_m, int capacity, float* box_lo, float* box_hi, int32_t* counts, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+    VoxelLayout lay;
+    if (int rc = voxel_check_grid(grid, n_self, &lay)) return rc;
+    if (n_self > 0) {
+        CPPF_REQUIRE(robot != nullptr, "robot handle is NULL (only n_self = 0 needs none)");
+        CPPF_REQUIRE(!(robot->life.load(std::memory_order_acquire) & kRobotDead), "the robot handle was destroyed");
+        CPPF_REQUIRE(q_self, "q_self is NULL");
+    }
+    CPPF_REQUIRE(self_margin_m >= 0.f && std::isfinite(self_margin_m), "self_margin_m must be finite and >= 0 (not NaN)");
+    CPPF_REQUIRE(capacity >= 0 && capacity <= CPPF_MAX_SCENE_OBSTACLES, "capacity out of range (0 .. CPPF_MAX_SCENE_OBSTACLES)");
+    CPPF_REQUIRE(capacity == 0 || (box_lo && box_hi), "box_lo / box_hi is NULL");
+    CPPF_REQUIRE(counts, "counts is NULL");
+    CPPF_REQUIRE(workspace, "workspace is NULL");
+    CPPF_REQUIRE(((uintptr_t)workspace & 15u) == 0, "workspace must be 16-byte aligned");
+    CPPF_REQUIRE(workspace_bytes >= lay.total, "workspace is smaller than cppf_voxel_scene_workspace_bytes(grid, n_self)");
+    if (n_self > 0 && robot->desc.ndof < 3) return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: kernels are built for ndof in 3..12");
+
+    // (without a handle the launches go to the calling thread's current device, where the caller's pointers live)
+    int device = -1;
+    if (n_self > 0)
+        device = robot->device;
+    else
+        CPPF_HIP(hipGetDevice(&device));
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess)
+        return fail(CPPF_ERR_HIP, std::string("cppflow_hip: selecting the robot's device failed: ") + hipGetErrorString(guard.err));
+    hipStream_t st = (hipStream_t)stream;
+
+    char* const base = static_cast<char*>(workspace);
+    VoxelK g;
+    for (int k = 0; k < 3; ++k) g.origin[k] = grid->origin[k];
+    g.voxel = grid->voxel_m;
+    g.inv_voxel = 1.0f / grid->voxel_m;
+    g.nx = grid->dims[0], g.ny = grid->dims[1], g.nz = grid->dims[2];
+    g.wpr = lay.wpr, g.rows = lay.rows;
+    g.bits = reinterpret_cast<unsigned long long*>(base);
+    g.row_heads = reinterpret_cast<int32_t*>(base + lay.bits);
+    g.row_cells = reinterpret_cast<int32_t*>(base + lay.bits + lay.row);
+    g.row_offset = reinterpret_cast<int32_t*>(base + lay.bits + 2 * lay.row);
+    float* const segs = reinterpret_cast<float*>(base + lay.bits + 3 * lay.row);
+    g.segs = segs;
+    g.n_self = n_self;
+    g.ncaps = n_self > 0 ? robot->coll.ncaps : 0;
+    g.capacity = capacity;
+    g.counts = counts;
+    g.box_lo = box_lo, g.box_hi = box_hi;
+
+    const size_t n16 = (lay.bits + 3 * lay.row) / 16;
+    hipLaunchKernelGGL(voxel_clear_kernel, dim3((unsigned)((std::max<size_t>(n16, 8) + 255) / 256)), dim3(256), 0, st,
+                       reinterpret_cast<uint4*>(base), n16, counts);
+    if (n_self > 0 && g.ncaps > 0) {
+        VoxelSelfK sk;
+        sk.q = q_self, sk.segs = segs, sk.n_self = n_self;
+        for (int c = 0; c < CPPF_MAX_CAPSULES; ++c) {
+            const double s = c < g.ncaps ? (double)robot->desc.cap_r[c] + (double)self_margin_m : 0.0;
+            sk.thr2[c] = (float)(s * s);
+        }
+        // the generic capsule FK serves every robot: a generated table gives the same bits
+        const int rc = for_dyn_robot(robot, [&](auto tag) {
+            using RB = typename decltype(tag)::type;
+            hipLaunchKernelGGL(voxel_self_kernel<RB>, dim3(1), dim3(64), 0, st, robot->chain, robot->coll, sk);
+            return CPPF_OK;
+        });
+        if (rc) return rc;
+    }
+    if (src.n > 0) {
+        const dim3 pgrid((unsigned)((src.n + 255) / 256));
+        if (src.points)
+            hipLaunchKernelGGL(voxel_points_kernel<false>, pgrid, dim3(256), 0, st, g, src.points, src.cam, src.n);
+        else
+            hipLaunchKernelGGL(voxel_points_kernel<true>, pgrid, dim3(256), 0, st, g, (const float*)nullptr, src.cam, src.n);
+    }
+    const dim3 rgrid((unsigned)((lay.rows + 255) / 256));
+    hipLaunchKernelGGL(voxel_rows_kernel, rgrid, dim3(256), 0, st, g);
+    hipLaunchKernelGGL(voxel_scan_kernel, dim3(1), dim3(1024), 0, st, g);
+    hipLaunchKernelGGL(voxel_emit_kernel, rgrid, dim3(256), 0, st, g);
+    return check_launch();
+}
+}  // namespace
+
+int cppf_voxel_scene_workspace_bytes(const cppf_voxel_grid* grid, int n_self, size_t* bytes) {
+    CPPF_REQUIRE(bytes, "bytes is NULL");
+    VoxelLayout lay;
+    if (int rc = voxel_check_grid(grid, n_self, &lay)) return rc;
+    *bytes = lay.total;
+    return CPPF_OK;
+}
+
+int cppf_scene_from_points(const cppf_robot* robot, const float* points, int n_points, const cppf_voxel_grid* grid, const float* q_self,
+                           int n_self, float self_margin_m, int capacity, float* box_lo, float* box_hi, int32_t* counts,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+    CPPF_REQUIRE(n_points >= 0, "n_points < 0");
+    CPPF_REQUIRE(n_points == 0 || points, "points is NULL");
+    VoxelSource src{};
+    src.points = points;
+    src.n = (size_t)n_points;
+    return voxel_scene_run(robot, src, grid, q_self, n_self, self_margin_m, capacity, box_lo, box_hi, counts, workspace, workspace_bytes,
+                           stream);
+}
+
+int cppf_scene_from_depth(const cppf_robot* robot, const float* depth, int height, int width, const float intrinsics[4],
+                          const float cam_to_world[12], float z_min, float z_max, const cppf_voxel_grid* grid, const float* q_self,
+                          int n_self, float self_margin_m, int capacity, float* box_lo, float* box_hi, int32_t* counts,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+    CPPF_REQUIRE(height >= 0 && width >= 0, "height / width < 0");
+    const size_t n = (size_t)height * (size_t)width;
+    CPPF_REQUIRE(n < ((size_t)1 << 31), "height*width exceeds 2^31-1 pixels");
+    CPPF_REQUIRE(n == 0 || depth, "depth is NULL");
+    CPPF_REQUIRE(intrinsics && cam_to_world, "intrinsics / cam_to_world is NULL");
+    CPPF_REQUIRE(z_min < z_max, "z_min must be below z_max (neither NaN)");
+    VoxelSource src{};
+    src.cam.depth = depth;
+    src.cam.width = width;
+    src.cam.ifx = 1.0f / intrinsics[0], src.cam.ify = 1.0f / intrinsics[1];
+    CPPF_REQUIRE(std::isfinite(intrinsics[0]) && std::isfinite(intrinsics[1]) && intrinsics[0] != 0.f && intrinsics[1] != 0.f &&
+                     std::isfinite(src.cam.ifx) && std::isfinite(src.cam.ify),
+                 "fx / fy must be finite and non-zero (and 1 / fx, 1 / fy finite)");
+    src.cam.cx = intrinsics[2], src.cam.cy = intrinsics[3];
+    for (int k = 0; k < 9; ++k) src.cam.R[k] = cam_to_world[k];
+    for (int k = 0; k < 3; ++k) src.cam.t[k] = cam_to_world[9 + k];
+    src.cam.z_min = z_min, src.cam.z_max = z_max;
+    src.n = n;
+    // (the point kernel tells the forms apart by its template argument; src.points stays NULL)
+    return voxel_scene_run(robot, src, grid, q_self, n_self, self_margin_m, capacity, box_lo, box_hi, counts, workspace, workspace_bytes,
+                           stream);
 }
 
 // ---- motion between the waypoints (kernels_motion.h) ------------------------------------------------------------------------------

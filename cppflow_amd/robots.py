@@ -547,6 +547,93 @@ class Robot:
         res["env_mask"] = res["env_mask"].view(torch.bool)
         return res
 
+    # ---- scenes from sensor data (cppf_scene_from_points / cppf_scene_from_depth; include/cppflow_hip.h) ------------------------------
+    def _voxel_scene(self, source, dev: torch.device, origin, voxel_m: float, dims, q_self, self_margin_m: float, max_cuboids: int,
+                     coarsen: bool):
+        """the rounds behind `scene_from_points` / `scene_from_depth`; source(grid, tail) makes the library call of one round"""
+        from cppflow_amd.scene import VOXEL_COUNT_NAMES, ObstacleScene
+
+        assert 0 <= int(max_cuboids) <= _hip.MAX_SCENE_OBSTACLES, f"max_cuboids must be in 0 .. {_hip.MAX_SCENE_OBSTACLES}"
+        origin = [float(v) for v in origin]
+        dims = [int(v) for v in dims]
+        assert len(origin) == 3 and len(dims) == 3, "origin and dims have three entries"
+        if q_self is None:
+            n_self, q_ptr, handle = 0, None, None
+        else:
+            q_self = self._x2d(q_self.unsqueeze(0) if q_self.dim() == 1 else q_self, "q_self")
+            assert q_self.device == dev, "q_self must be on the device of the sensor data"
+            n_self, q_ptr, handle = int(q_self.shape[0]), q_self.data_ptr(), self._handle(dev)
+            if n_self == 0:
+                q_ptr, handle = None, None
+        cap = int(max_cuboids)
+        lo = torch.empty((cap, 3), dtype=torch.float32, device=dev)
+        hi = torch.empty((cap, 3), dtype=torch.float32, device=dev)
+        counts = torch.empty((8,), dtype=torch.int32, device=dev)
+        voxel, history = float(voxel_m), []
+        for rnd in range(4 if coarsen else 1):
+            grid = _hip.VoxelGrid((_hip._f * 3)(*origin), voxel, (_hip._i32 * 3)(*dims))
+            nbytes = ctypes.c_size_t()
+            _hip.check(_hip.lib().cppf_voxel_scene_workspace_bytes(ctypes.byref(grid), n_self, ctypes.byref(nbytes)))
+            work = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+            tail = (ctypes.byref(grid), q_ptr, n_self, float(self_margin_m), cap, lo.data_ptr(), hi.data_ptr(), counts.data_ptr(),
+                    work.data_ptr(), nbytes.value, _stream_ptr(dev))  # fmt: skip
+            with torch.cuda.device(dev):  # (without a handle the library launches on the current device)
+                _hip.check(source(handle, tail))
+            c = counts.cpu().tolist()  # (the one device-to-host copy of this round)
+            stats = dict(zip(VOXEL_COUNT_NAMES, c[:7]), voxel_m=voxel, dims=tuple(dims), origin=tuple(origin), rounds=rnd + 1)
+            history.append(stats)
+            if c[0] <= cap:
+                n = c[1]
+                return ObstacleScene(lo[:n].clone(), hi[:n].clone(), stats)
+            voxel, dims = voxel * 2.0, [(d + 1) // 2 for d in dims]
+        raise RuntimeError(
+            f"the sensor data gives more cuboids than max_cuboids = {cap}"
+            + (" after 3 coarsening rounds" if coarsen else " and coarsen is off") + ": "
+            + "; ".join(f"voxel_m={h['voxel_m']:g} dims={h['dims']}: {h['boxes_total']} boxes, {h['occupied_cells']} cells, "
+                        f"{h['kept_points']} kept / {h['outside_points']} outside / {h['invalid_points']} invalid / {h['self_points']} self points"
+                        for h in history)
+        )  # fmt: skip
+
+    def scene_from_points(self, points: torch.Tensor, origin, voxel_m: float, dims, q_self: Optional[torch.Tensor] = None,
+                          self_margin_m: float = 0.03, max_cuboids: int = _hip.MAX_SCENE_OBSTACLES, coarsen: bool = True):
+        """A world-frame point cloud [n, 3] (device) -> `ObstacleScene` of at most `max_cuboids` axis-aligned cuboids on the same
+        device: the occupied cells of the grid (origin, voxel_m, dims = (nx, ny, nz)), equal x-runs of neighbouring rows merged along
+        y (`cppf_scene_from_points`; include/cppflow_hip.h states grid, classes and box list).  `q_self` [n_self <= 16, d] (device):
+        points within `self_margin_m` of the robot's capsules at any of these configurations are dropped; None: no filter.  More
+        cuboids than `max_cuboids`: with `coarsen` the build is repeated with voxel_m * 2 and ceil(dims / 2) at the same origin, at
+        most 3 more times; otherwise, or if that does not fit either, RuntimeError -- a truncated scene is never returned.  The counts
+        of the returned round are its `.stats`.  One device-to-host copy (the counts) per round."""
+        points = _require_device_tensor(points, "points")
+        assert points.dim() == 2 and points.shape[1] == 3, f"points must be [n, 3], is {tuple(points.shape)}"
+        n = int(points.shape[0])
+
+        def source(handle, tail):
+            return _hip.lib().cppf_scene_from_points(handle, points.data_ptr() if n else None, n, *tail)
+
+        return self._voxel_scene(source, points.device, origin, voxel_m, dims, q_self, self_margin_m, max_cuboids, coarsen)
+
+    def scene_from_depth(self, depth: torch.Tensor, intrinsics, cam_to_world, z_min: float, z_max: float, origin, voxel_m: float, dims,
+                         q_self: Optional[torch.Tensor] = None, self_margin_m: float = 0.03,
+                         max_cuboids: int = _hip.MAX_SCENE_OBSTACLES, coarsen: bool = True):
+        """A depth image [H, W] (device, fp32 metres) -> `ObstacleScene`, as `scene_from_points` on its back-projected pixels
+        (`cppf_scene_from_depth`).  intrinsics = (fx, fy, cx, cy); cam_to_world: a 4x4 (or 3x4) transform, host; a pixel counts only
+        with z_min < depth < z_max."""
+        depth = _require_device_tensor(depth, "depth")
+        assert depth.dim() == 2, f"depth must be [H, W], is {tuple(depth.shape)}"
+        T = cam_to_world.detach().cpu().numpy() if isinstance(cam_to_world, torch.Tensor) else np.asarray(cam_to_world)
+        T = T.astype(np.float32)
+        assert T.shape in ((4, 4), (3, 4)), f"cam_to_world must be 4x4 or 3x4, is {T.shape}"
+        rt = np.ascontiguousarray(np.concatenate([T[:3, :3].reshape(9), T[:3, 3]]), dtype=np.float32)
+        k = np.ascontiguousarray(np.asarray([float(v) for v in intrinsics], dtype=np.float32))
+        assert k.shape == (4,), "intrinsics = (fx, fy, cx, cy)"
+        h, w = int(depth.shape[0]), int(depth.shape[1])
+
+        def source(handle, tail):
+            return _hip.lib().cppf_scene_from_depth(handle, depth.data_ptr() if h * w else None, h, w, _hip.fptr(k), _hip.fptr(rt),
+                                                    float(z_min), float(z_max), *tail)  # fmt: skip
+
+        return self._voxel_scene(source, depth.device, origin, voxel_m, dims, q_self, self_margin_m, max_cuboids, coarsen)
+
     def motion_travel_table(self) -> np.ndarray:
         """rho [d, n_capsules] fp32: the travel bounds `motion_clearance` certifies with (`cppf_motion_rho`; include/cppflow_hip.h).
         Host only: needs no device."""

@@ -361,6 +361,63 @@ int cppf_motion_resolve(const cppf_robot* robot, const float* q, int S, int W, i
                         uint8_t* status, int32_t* depth, int32_t* hit_num, float* min_clear, int32_t* n_tested,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* Scenes from sensor data: a point cloud (points [n, 3], world frame) or a depth image becomes the box_lo / box_hi list the four
+ * scene readers above take, entirely on the device.  DEVICE pointers only; the library allocates nothing.
+ *   Grid.  cppf_voxel_grid { origin[3], voxel_m, dims = (nx, ny, nz) }, each dim in 1 .. CPPF_VOXEL_MAX_DIM; nxp = 64 ceil(nx / 64) is
+ *   the padded row length in bits, and nxp ny nz <= CPPF_VOXEL_MAX_CELLS.
+ *   Planes.  Plane i of axis k is P_k(i) = fadd_rn(origin[k], fmul_rn((float)i, voxel_m)), i = 0 .. n_k: two separate roundings, on
+ *   purpose not an fmaf, so that float32 arithmetic anywhere reproduces every corner bit for bit whatever voxel_m is.  The entry
+ *   points check on the host that every P_k is finite and strictly increasing (CPPF_ERR_INVALID otherwise).
+ *   Cell of a point.  The index of coordinate p_k is the unique i in [0, n_k) with P_k(i) <= p_k < P_k(i+1) -- decided against the
+ *   planes themselves, exactly, for every fp32 input; a point with no such i on some axis is OUTSIDE.
+ *   Classes.  Every input falls into exactly one class, tested in this order: INVALID (a non-finite coordinate, or an invalid pixel
+ *   of the depth form), OUTSIDE, SELF (removed by the self filter), KEPT.  A cell is occupied if it holds at least one kept point.
+ *   Self filter.  q_self [n_self, d], 0 <= n_self <= CPPF_VOXEL_MAX_SELF, and self_margin_m >= 0.  A point p is SELF if for some
+ *   configuration and some capsule c of the robot dist2(p, segment_c) < thr2_c, thr2_c = fp32((r_c + self_margin_m)^2) formed on the
+ *   host in fp64.  Centre C and half-axis H of the capsule are the canonical capsule FK's (the bits cppf_collision_masks works on);
+ *   with D = p - C (fp32), u = clamp(fmaf-chain(D . H) * inv, -1, 1), inv = fp32 1 / (H . H) (0 where H . H = 0: a sphere),
+ *   E = fmaf(-u, H, D) per axis, dist2 = E . E (fmaf chain, x first).  n_self = 0 switches the filter off; only then may robot and
+ *   q_self be NULL.
+ *   Boxes of an occupancy.  An x-RUN of row (y, z) is a maximal interval [x0, x1) of occupied cells.  A run is a HEAD if row
+ *   (y-1, z) does not hold the identical maximal run [x0, x1).  A head's box spans y .. y1, y1 the first y' > y whose row (y', z)
+ *   does not hold that identical maximal run.  The list is the heads ascending by (z, y, x0):
+ *       box_lo = (P_x(x0), P_y(y), P_z(z)),  box_hi = (P_x(x1), P_y(y1), P_z(z+1)).
+ *   The union of the boxes is the union of the occupied cells, exactly; their interiors are disjoint; the list depends on the
+ *   occupancy alone.  Nothing is merged along z.
+ *   Capacity.  0 <= capacity <= CPPF_MAX_SCENE_OBSTACLES: the first min(total, capacity) boxes of the list are written to box_lo /
+ *   box_hi [capacity, 3]; nothing beyond is touched.  A scene with total > capacity is NOT a sound scene -- it has lost obstacles:
+ *   read counts before using it.
+ *   counts int32 [8]: 0 boxes in total, 1 boxes written, 2 occupied cells, 3 kept, 4 outside, 5 invalid, 6 self points, 7 zero.
+ *   counts[3..6] sum to the number of inputs.
+ *   Depth form.  depth [height, width] fp32 metres, intrinsics (fx, fy, cx, cy), cam_to_world[12] = R row-major, then t.  Pixel
+ *   (row v, column u) of depth z is INVALID unless z > z_min && z < z_max (a NaN fails both).  Otherwise, with ifx = 1.0f / fx and
+ *   ify = 1.0f / fy formed on the host in fp32, every operation rounded separately and in this order:
+ *       xc = fmul(fsub((float)u, cx), fmul(z, ifx)),  yc likewise with v, cy, ify,  zc = z,
+ *       w_k = fadd(fadd(fadd(fmul(R_k0, xc), fmul(R_k1, yc)), fmul(R_k2, zc)), t_k);
+ *   from there on w takes the point form's path (a non-finite w_k is INVALID).
+ * workspace: cppf_voxel_scene_workspace_bytes(grid, n_self) bytes, 16-byte aligned, device; it need not be initialised and is
+ * scratch on return.  Up to six launches on `stream`, asynchronous, no host synchronisation, capturable in a graph; the only atomics
+ * are integer OR and integer add, so two runs give identical bytes.  n_points = 0 (height width = 0) is valid: 0 boxes.
+ * CPPF_ERR_INVALID, before a device is selected: a NULL or destroyed handle with n_self > 0, NULL pointers, dims / cells / n_self /
+ * capacity out of range, a non-positive or non-finite voxel_m, planes that are not finite and strictly increasing, a negative or NaN
+ * margin, z_min >= z_max, fx or fy zero or not finite, a short or misaligned workspace, n_points < 0, height width >= 2^31. */
+#define CPPF_VOXEL_MAX_DIM 1024
+#define CPPF_VOXEL_MAX_CELLS (1 << 24)
+#define CPPF_VOXEL_MAX_SELF 16
+typedef struct cppf_voxel_grid {
+    float origin[3];
+    float voxel_m;
+    int32_t dims[3];
+} cppf_voxel_grid;
+int cppf_voxel_scene_workspace_bytes(const cppf_voxel_grid* grid, int n_self, size_t* bytes);
+int cppf_scene_from_points(const cppf_robot* robot, const float* points, int n_points, const cppf_voxel_grid* grid, const float* q_self,
+                           int n_self, float self_margin_m, int capacity, float* box_lo, float* box_hi, int32_t* counts,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int cppf_scene_from_depth(const cppf_robot* robot, const float* depth, int height, int width, const float intrinsics[4],
+                          const float cam_to_world[12], float z_min, float z_max, const cppf_voxel_grid* grid, const float* q_self,
+                          int n_self, float self_margin_m, int capacity, float* box_lo, float* box_hi, int32_t* counts,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* Robot.self_collision_distances(x) -> [n, n_pairs] (call site cppflow/collision_detection.py:65) */
 int cppf_self_collision_distances(const cppf_robot* robot, const float* x, int n, float* dists, void* stream);
 
