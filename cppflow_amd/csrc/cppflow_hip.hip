@@ -963,14 +963,16 @@ enum class FullStepForm {
     Rows,     // one block row per lane
     Wave,     // one wavefront per trajectory (takes no pinned end)
     Lane,     // one lane per trajectory
+    Local,    // the pose block without differencing rows: no elimination, every waypoint solved where its block is built, in fp64
 };
-FullStepForm full_step_form(const cppf_robot* robot, size_t n, int W, bool use_pose, bool var_coupling) {
+FullStepForm full_step_form(const cppf_robot* robot, size_t n, int W, bool use_pose, bool use_diff, bool var_coupling) {
     const int ndof = robot->desc.ndof;
     const int t_pcr_rows = tune(robot, CPPF_TUNE_PCR_MAX_ROWS);
     const bool g_pcr_lds = tune(robot, CPPF_TUNE_PCR_LDS) != 0;
     const bool g_rows_pose = tune(robot, CPPF_TUNE_ROWS_POSE) != 0, g_full_rows = tune(robot, CPPF_TUNE_FULL_ROWS) != 0;
     const size_t pcr_rows = t_pcr_rows >= 0 ? (size_t)t_pcr_rows : (size_t)((W <= 256 && g_pcr_lds) ? kPcrMaxRowsLds : kPcrMaxRowsGlobal);
     const size_t pcr_limit = pcr_rows * (ndof <= 7 ? 100 : 50) / 100;
+    if (use_pose && !use_diff) return FullStepForm::Local;
     if (var_coupling) return FullStepForm::LaneVar;
     if (!use_pose && W <= 512 && n <= pcr_limit && ndof >= 3 && ndof <= 8) return FullStepForm::Pcr;
     if ((!use_pose || g_rows_pose) && g_full_rows && ndof >= 3 && ndof <= 12 && W <= (1 << 19)) return FullStepForm::Rows;
@@ -996,7 +998,7 @@ int full_step_pin_check(const cppf_robot* robot, int S, int W, const cppf_full_p
     // CPPF_TUNE_FULL_ROWS = 0 beyond the parallel-in-time sizes, and also fewer than 3 joints or more than 2^19 waypoints, where the
     // row-per-lane form does not exist.
     if (S >= 1 && W >= 1 && (size_t)S * W <= 0x7fffffffu &&
-        full_step_form(robot, (size_t)S * W, W, params->use_pose != 0, false) == FullStepForm::Wave)
+        full_step_form(robot, (size_t)S * W, W, params->use_pose != 0, params->use_differencing != 0, false) == FullStepForm::Wave)
         return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: the one-wavefront-per-trajectory elimination (what a step resolves to under "
                                           "CPPF_TUNE_FULL_ROWS = 0, with fewer than 3 joints or beyond 2^19 waypoints) takes no "
                                           "pinned end waypoint");
@@ -1061,13 +1063,25 @@ int lm_full_step_gated(const cppf_robot* robot, const float* x_in, const float* 
     // which elimination kernel: see the comments at the launches below
     const int t_pcr_lds = tune(robot, CPPF_TUNE_PCR_LDS);
     const bool g_pcr_lds = t_pcr_lds != 0, g_pcr_split = t_pcr_lds != 1;
-    const FullStepForm form = full_step_form(robot, n, W, prm.use_pose != 0, var_coupling);
+    const FullStepForm form = full_step_form(robot, n, W, prm.use_pose != 0, prm.use_diff != 0, var_coupling);
     prm.fold = form != FullStepForm::Pcr;  // (the parallel-in-time kernel assembles the terms itself: FullK::fold)
     if (gate.ctl != nullptr && !full_step_gateable(form)) return fail(CPPF_ERR_UNSUPPORTED, kGatedFormRefusal);
     hipStream_t st = (hipStream_t)stream;
     const int rc = for_robot(robot, [&](auto tag) {
         using RB = typename decltype(tag)::type;
-        if (scene != nullptr) {
+        if (form == FullStepForm::Local) {
+            // Six pose rows against seven or eight joints and nothing else on the diagonal but lambda: the blocks in fp64, solved by
+            // the lane that builds them (full_local_solve).  The unconstrained build at every size: the fp64 block is 2 x d(d+3)/2
+            // registers on top of the rows'.
+            if (scene != nullptr) {
+                SceneStepK sc = *scene;
+                sc.tile_cull2 = tile_cull_threshold(robot, 0.f);
+                hipLaunchKernelGGL((full_blocks_kernel<RB, 0, true, true>), dim3(grid_for(n)), dim3(kBlock), robot->lds_bytes, st, robot->chain,
+                                   robot->coll, prm, x_in, target, virtual_configs, work_blocks, w2next, sc, x_out);
+            } else
+                hipLaunchKernelGGL((full_blocks_kernel<RB, 0, false, true>), dim3(grid_for(n)), dim3(kBlock), robot->lds_bytes, st, robot->chain,
+                                   robot->coll, prm, x_in, target, virtual_configs, work_blocks, w2next, gate, x_out);
+        } else if (scene != nullptr) {
             // ONE instantiation per robot, the unconstrained build: a planner steps S <= 8 trajectories, far below the row count at
             // which the occupancy-bound build of the handle form pays.  (A handle specialised at run time takes the generic form,
             // like every coupled step: for_robot.)
@@ -1075,16 +1089,17 @@ int lm_full_step_gated(const cppf_robot* robot, const float* x_in, const float* 
             sc.tile_cull2 = tile_cull_threshold(robot, 0.f);
             // (dynamic LDS as for the handle form beside it: chain12's 13 capsules are 78 KB in both)
             hipLaunchKernelGGL((full_blocks_kernel<RB, 0, true>), dim3(grid_for(n)), dim3(kBlock), robot->lds_bytes, st, robot->chain,
-                               robot->coll, prm, x_in, target, virtual_configs, work_blocks, w2next, sc);
+                               robot->coll, prm, x_in, target, virtual_configs, work_blocks, w2next, sc, (float*)nullptr);
         } else if (n >= 131072)
             hipLaunchKernelGGL((full_blocks_kernel<RB, full_blocks_occ<RB>()>), dim3(grid_for(n)), dim3(kBlock), robot->lds_bytes, st,
-                               robot->chain, robot->coll, prm, x_in, target, virtual_configs, work_blocks, w2next, gate);
+                               robot->chain, robot->coll, prm, x_in, target, virtual_configs, work_blocks, w2next, gate, (float*)nullptr);
         else
             hipLaunchKernelGGL((full_blocks_kernel<RB>), dim3(grid_for(n)), dim3(kBlock), robot->lds_bytes, st, robot->chain,
-                               robot->coll, prm, x_in, target, virtual_configs, work_blocks, w2next, gate);
+                               robot->coll, prm, x_in, target, virtual_configs, work_blocks, w2next, gate, (float*)nullptr);
         return CPPF_OK;
     });
     if (rc) return rc;
+    if (form == FullStepForm::Local) return check_launch();
     // row-per-lane kernels: 8 trajectories per one-wavefront workgroup and two workgroups (the two ends of the path) per 8
     // trajectories; the LDS reservation caps the workgroups per compute unit at ceil(#workgroups / 256) (160 KB per compute
     // unit), which spreads a small launch over distinct compute units
@@ -1143,8 +1158,9 @@ int lm_full_step_gated(const cppf_robot* robot, const float* x_in, const float* 
                     hipLaunchKernelGGL((full_solve_wave_kernel<D>), dim3((unsigned)S), dim3(64), 0, st, prm, pris_mask, x_in, work_blocks,
                                        work_G, work_y, x_out);
                 break;
+            case FullStepForm::Local: break;  // (returned above)
             case FullStepForm::Lane:
-                // With the pose block the d x d blocks are J^T J + a small diagonal (rank 6 of 7, cond ~1e7): this kernel's Cholesky
+                // With the pose block and differencing rows the d x d blocks are J^T J + a small diagonal (rank 6 of 7, cond ~1e7): this kernel's Cholesky
                 // with floored pivots copes with that better than the explicit Gauss-Jordan inverse, so it keeps that case.
                 hipLaunchKernelGGL((full_solve_kernel<D>), lane_grid, dim3(64), 0, st, prm, pris_mask, x_in, work_blocks, work_G, work_y,
                                    x_out, nullptr);
@@ -1649,7 +1665,7 @@ int cppf_lm_optimize_enqueue_pinned(const cppf_robot* robot, float* x, const flo
     if (params->diff.use_pose || params->diff.differencing_mode != 0)
         return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: the device-side optimiser loop takes a coupled step without pose block and without weighted differencing rows");
     // ... and so is the elimination of the coupled step: decided here, before the pose step's launch writes x_new
-    if (!full_step_gateable(full_step_form(robot, n, W, false, false))) return fail(CPPF_ERR_UNSUPPORTED, kGatedFormRefusal);
+    if (!full_step_gateable(full_step_form(robot, n, W, false, true, false))) return fail(CPPF_ERR_UNSUPPORTED, kGatedFormRefusal);
     if (n_iterations == 0) return CPPF_OK;
     CPPF_ENTER(robot);
     prm.n = (int)n;

@@ -20,6 +20,9 @@
 //   full_solve_pcr_kernel (one workgroup per trajectory, parallel cyclic reduction over the waypoints, state in LDS for
 //                        W <= 256): the default up to there -- the reference's cadence is ONE trajectory.
 //   full_solve_wave_kernel (one wavefront per trajectory, round 1's form): kept as a cross-check behind a test hook.
+//   full_blocks_kernel<.., LOCAL>: the pose block WITHOUT differencing rows.  Nothing couples the waypoints, so the lane that builds a
+//                        waypoint's block also solves it and writes x_out; and since A_tt = Js^T Js + lambda I then has d - 6
+//                        eigenvalues EQUAL to lambda = 1e-6, it accumulates and factors the block in fp64 (full_local_solve).
 
 struct FullK {
     float lm_lambda, a_pos, a_rot, a_diff, a_diff_pris, a_vq, a_self, a_env;
@@ -157,6 +160,21 @@ __device__ __forceinline__ void rank1(float (&M)[D * (D + 1) / 2], float (&m)[D]
             ++k;
         }
         m[i] = CPPF_FMA(wm, g[i], m[i]);
+    }
+}
+// the same on fp64 accumulators (full_blocks_kernel<.., LOCAL>): the products of the fp32 row are exact in double
+template <int D>
+__device__ __forceinline__ void rank1(double (&M)[D * (D + 1) / 2], double (&m)[D], const float (&g)[D], float w, float wm) {
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+        const double wi = (double)w * (double)g[i];
+#pragma unroll
+        for (int j = i; j < D; ++j) {
+            M[k] = __builtin_fma(wi, (double)g[j], M[k]);
+            ++k;
+        }
+        m[i] = __builtin_fma((double)wm, (double)g[i], m[i]);
     }
 }
 
@@ -311,6 +329,73 @@ __device__ __forceinline__ void full_block_store(const RB& rb, const FullK& prm,
     for (int j = 0; j < D; ++j) o[NT + j] = m[j];
 }
 
+// The step of ONE waypoint that no differencing row couples to its neighbours (full_blocks_kernel<.., LOCAL>: pose block on,
+// differencing off):  (M + virtual-config rows + lambda I) delta = m,  x_out = x + delta, all in fp64.  With six pose rows and seven or
+// eight joints M = Js^T Js has a null space of d - 6 dimensions, which lambda = 1e-6 alone lifts: m = Js^T es has no component there in
+// exact arithmetic, an fp32 one has 6e-8 |Js| |es|, and the solve divides it by lambda -- a tenth of the step, in joint space, against the
+// reference's fp64 result.  Formed from the fp32 rows in double the system is the exact one of those rows, whose step depends on
+// them no more sharply than 1 / sigma_min(Js).  A pinned waypoint (FullK::pin) comes back as it is.
+template <class RB>
+__device__ __forceinline__ void full_local_solve(const RB& rb, const FullK& prm, size_t row, const float (&q)[RB::D],
+                                                 const float* __restrict__ x, const float* __restrict__ xv,
+                                                 double (&M)[RB::D * (RB::D + 1) / 2], double (&m)[RB::D], float* __restrict__ x_out) {
+    constexpr int D = RB::D;
+    const int t = (int)(row % (size_t)prm.W), T = prm.W;
+    if (t < full_t0(prm) || t >= full_t1(prm)) {
+        copy_row<D>(x, x_out, row);
+        return;
+    }
+    const bool vq = prm.use_vq && (t < prm.n_vq || t >= T - prm.n_vq);
+    const float beta = prm.a_vq * prm.a_diff, beta2 = beta * beta;  // as in full_block_store
+    float wv[D];
+#pragma unroll
+    for (int j = 0; j < D; ++j) wv[j] = (vq && xv) ? q[j] - xv[row * D + j] : 0.f;
+    wrap_pi_all<D>(wv);
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+        M[sym_index<D>(j, j)] += (double)(vq ? beta2 : 0.f) + (double)prm.lm_lambda;
+        if (vq && xv) m[j] = __builtin_fma(-(double)beta2, (double)wv[j], m[j]);
+    }
+    // M = U^T U in place (upper triangle, row after row).  Every pivot of a matrix whose eigenvalues are >= lambda is >= lambda, so
+    // the floor only keeps a NaN out if the rows themselves were not finite numbers.
+    double inv[D];
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+#pragma unroll
+        for (int j = i; j < D; ++j) {
+            double s = M[sym_index<D>(i, j)];
+#pragma unroll
+            for (int k = 0; k < i; ++k) s = __builtin_fma(-M[sym_index<D>(k, i)], M[sym_index<D>(k, j)], s);
+            if (j == i) {
+                s = __builtin_sqrt(__builtin_fmax(s, 0.5 * (double)prm.lm_lambda));
+                inv[i] = 1.0 / s;
+                M[sym_index<D>(i, i)] = s;
+            } else {
+                M[sym_index<D>(i, j)] = s * inv[i];
+            }
+        }
+    }
+    // U^T y = m, then U delta = y
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+        double s = m[i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) s = __builtin_fma(-M[sym_index<D>(k, i)], m[k], s);
+        m[i] = s * inv[i];
+    }
+#pragma unroll
+    for (int i = D - 1; i >= 0; --i) {
+        double s = m[i];
+#pragma unroll
+        for (int k = i + 1; k < D; ++k) s = __builtin_fma(-M[sym_index<D>(i, k)], m[k], s);
+        m[i] = s * inv[i];
+    }
+    float xr[D];
+#pragma unroll
+    for (int j = 0; j < D; ++j) xr[j] = (float)((double)q[j] + m[j]);  // optimization.py:113: x + delta_x
+    store_x<D>(x_out, row, xr);
+}
+
 // RB = StaRobot<...>: a screening pass first -- capsule FK in registers, the wave-uniform broad phase, then the cheap squared
 // distance against the (slightly widened) tabulated thresholds -- leaves two wavefront-uniform bit sets of the pairs /
 // (cuboid, capsule) tests in which SOME lane may penetrate.  A wavefront with none (the common case on a planner's paths)
@@ -362,14 +447,25 @@ template <>
 struct FullBlocksTail<true> {
     using type = SceneStepK;
 };
+template <bool LOCAL>
+struct FullBlocksAcc {  // what a row's block is accumulated in
+    using type = float;
+};
+template <>
+struct FullBlocksAcc<true> {
+    using type = double;
+};
 
-template <class RB, int OCC = 0, bool SCENE = false>
+// LOCAL (pose block without differencing rows: nothing couples the waypoints): the block is accumulated in fp64 and solved here
+// (full_local_solve) -- x_out is written, `blocks` and `w2next` are not, and no elimination follows.
+template <class RB, int OCC = 0, bool SCENE = false, bool LOCAL = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(OCC ? OCC : 1, OCC ? OCC : 8))) void full_blocks_kernel(const ChainK ch, const CollK co, const FullK prm,
                                                              const float* __restrict__ x,
                                                              const float* __restrict__ target,
                                                              const float* __restrict__ xv, float* __restrict__ blocks,
                                                              float* __restrict__ w2next,
-                                                             const typename FullBlocksTail<SCENE>::type gate) {
+                                                             const typename FullBlocksTail<SCENE>::type gate,
+                                                             float* __restrict__ x_out) {
     extern __shared__ float lds[];
     constexpr int D = RB::D;
     constexpr int NT = D * (D + 1) / 2;
@@ -444,7 +540,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(OCC ? OC
                 }
             }
         }
-        if (!prm.use_pose && near_self == 0ull && near_env == 0ull) {
+        if (!LOCAL && !prm.use_pose && near_self == 0ull && near_env == 0ull) {
             float M[NT], m[D];
 #pragma unroll
             for (int k = 0; k < NT; ++k) M[k] = 0.f;
@@ -454,7 +550,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(OCC ? OC
             return;
         }
     }
-    float R[9], p[3], ax[D][3], og[D][3], M[NT], m[D];
+    float R[9], p[3], ax[D][3], og[D][3];
+    typename FullBlocksAcc<LOCAL>::type M[NT], m[D];
 #pragma unroll
     for (int k = 0; k < NT; ++k) M[k] = 0.f;
 #pragma unroll
@@ -594,7 +691,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(OCC ? OC
                 }
             }
     }
-    full_block_store<RB>(rb, prm, row, q, x, xv, M, m, blocks, w2next);
+    if constexpr (LOCAL)
+        full_local_solve<RB>(rb, prm, row, q, x, xv, M, m, x_out);
+    else
+        full_block_store<RB>(rb, prm, row, q, x, xv, M, m, blocks, w2next);
 }
 
 // inverse of a symmetric positive definite D x D matrix (full storage in, full storage out) by Cholesky; pivots floored

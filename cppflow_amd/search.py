@@ -120,9 +120,15 @@ def _get_mjacs(q: torch.Tensor, robot, prismatic_joint_scaling: float = 5.0) -> 
 
 def dp_search_slow(problem, qpaths, use_cuda: bool = True, verbosity: int = 1) -> torch.Tensor:
     """The reference keeps a doubly-nested Python-loop version of the dynamic programme beside the vectorised one
-    (cppflow/search.py:55-97: same costs, same first-minimal-index rule).  Both are the same recurrence, so here both
-    names run the device kernel; this entry takes the reference's arguments (a list of [T, d] paths and the problem) and
-    evaluates the masks itself."""
+    (cppflow/search.py:55-97: same costs, same first-minimal-index rule).  It is the same recurrence but for one thing: it takes the
+    wrapped joint change of every joint as it is (`:83-85`), where `dp_search` multiplies a prismatic joint's by 5 (`_get_mjacs`,
+    `:120-121`), so with a prismatic joint the two may return different paths (tests/golden/reference_runs_fetch.npz records one
+    where they do).  Here both names run the device kernel, this one with a prismatic scaling of 1; it takes the reference's
+    arguments (a list of [T, d] paths and the problem) and evaluates the masks itself."""
     q = torch.stack(list(qpaths)).detach().contiguous()
     cost, _, _, _ = q_costs_external(problem.robot, q, problem)
-    return dp_search(problem.robot, q, None, None, use_cuda=use_cuda, verbosity=verbosity, q_costs=cost)
+    cost = cost.contiguous()
+    best_path, best_idx, _, ran = problem.robot.dp_search(q, cost, prismatic_joint_scaling=1.0, return_method=True)
+    if ran == "resident" and int(best_idx[0].item()) < 0:  # as in dp_search: the resident launch's waits expired
+        best_path, best_idx, _ = problem.robot.dp_search(q, cost, prismatic_joint_scaling=1.0, method="launches")
+    return best_path

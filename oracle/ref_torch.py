@@ -14,6 +14,9 @@ torch op sequence as the reference --
 does them: a chain of batched 4x4 matmuls straight from the URDF-style description (xyz, rpy, axis), NOT from the
 canonical chain the kernels and the C oracle use.  It therefore doubles as an independent check of the canonical rewrite.
 It is what bench.py times as `cpu_baseline` (kind "port").
+
+`canonical_spec` turns a description into the canonical chain's own numbers in the same vocabulary: the robot that the recorded runs
+of the reference are made on (oracle/reference_standin/jrl/robot.py), where the question is the reference's logic and not a constant.
 """
 
 import math
@@ -103,7 +106,9 @@ class TorchRobot:
         pending = torch.eye(4, dtype=torch.float64)
         for j in spec.joints:
             T = torch.eye(4, dtype=torch.float64)
-            T[:3, :3] = torch.tensor(rpy_to_matrix(*j.rpy))
+            # (a joint may carry its 3x3 `rotation` as numbers, e.g. the canonical chain's fp32-rounded ones: used as given)
+            R = getattr(j, "rotation", None)
+            T[:3, :3] = torch.tensor(rpy_to_matrix(*j.rpy) if R is None else R, dtype=torch.float64)
             T[:3, 3] = torch.tensor(j.xyz, dtype=torch.float64)
             if j.jtype == "fixed":
                 pending = pending @ T
@@ -246,6 +251,35 @@ def _segment_box_distance(P0, P1, lo, hi):
     t = torch.where(gv[0] >= 0, zeros, torch.where(gv[1] <= 0, ones, t_in))
     x = P0 + D * t[:, None]
     return (x - torch.minimum(torch.maximum(x, lo), hi)).norm(dim=1)
+
+
+def canonical_spec(spec):
+    """`spec` rewritten as the robot this project computes with: cppflow_amd.robot_model.canonicalize's chain (one fixed transform per
+    joint, axis z, every constant rounded to fp32, capsules in the moving links' frames, the checked pairs listed) in the URDF
+    vocabulary again.  On the URDF doubles themselves link offsets differ from the chain's by up to 6e-8 m, which is a statement
+    about constants, not about anything the reference's cppflow code does; on this spec ref_torch and the fp64 oracle agree to 1e-15."""
+    import numpy as np
+
+    from cppflow_amd.robot_model import CapsuleSpec, JointSpec, RobotSpec, canonicalize
+
+    ch = canonicalize(spec)
+
+    def joint(name, F, *args, **kw):
+        # the chain's rotations are fp32-rounded numbers, not exactly orthonormal: handed over as they are (ref_torch reads `rotation`)
+        j = JointSpec(name, name, tuple(float(v) for v in F[9:]), (0.0, 0.0, 0.0), *args, **kw)
+        j.rotation = np.asarray(F[:9], dtype=np.float64).reshape(3, 3)
+        return j
+
+    joints = [joint(f"l{i}", ch.F[i], (0.0, 0.0, 1.0), "revolute" if ch.jtype[i] == 0 else "prismatic", (float(ch.lo[i]), float(ch.hi[i])))
+              for i in range(ch.ndof)]  # fmt: skip
+    joints.append(joint("ee", ch.F_ee, jtype="fixed"))
+    # a capsule is its centre and half-axis, each rounded to fp32 once (orc_robot_create, gen_robots.capsule_centred): the end points
+    # that go with those numbers are centre -+ half-axis, up to 1e-8 m off the chain's own p0 / p1
+    f32 = lambda v: np.asarray(v, dtype=np.float64).astype(np.float32).astype(np.float64)  # noqa: E731
+    centre, half = f32(0.5 * (f32(ch.cap_p0) + f32(ch.cap_p1))), f32(0.5 * (f32(ch.cap_p1) - f32(ch.cap_p0)))
+    caps = [CapsuleSpec("base" if li < 0 else f"l{li}", tuple(float(v) for v in c - h), tuple(float(v) for v in c + h), float(r))
+            for li, c, h, r in zip(ch.cap_link, centre, half, ch.cap_r)]  # fmt: skip
+    return RobotSpec(spec.name, spec.formal_name, "base", joints, caps, collision_pairs=[(int(a), int(b)) for a, b in ch.pairs])
 
 
 # ---- the reference's op sequences ----------------------------------------------------------------------------------------

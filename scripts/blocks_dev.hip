@@ -14,5 +14,5 @@ constexpr int kBlock = 256;
 #include "kernels_coupled.h"
 }
 using namespace dev;
-#define FB(RB) template __global__ void dev::full_blocks_kernel<RB, full_blocks_occ<RB>()>(const ChainK, const CollK, const FullK, const float*, const float*, const float*, float*, float*, const StepGateK);
+#define FB(RB) template __global__ void dev::full_blocks_kernel<RB, full_blocks_occ<RB>()>(const ChainK, const CollK, const FullK, const float*, const float*, const float*, float*, float*, const StepGateK, float*);
 FB(StaRobot<gen::Panda>) FB(StaRobot<gen::Fetch>) FB(StaRobot<gen::FetchArm>) FB(DynRobot<6>) FB(DynRobot<7>) FB(DynRobot<8>)

@@ -6,9 +6,10 @@
                         reference's own problem yaml / path csv DATA files (no reference source is read or copied)
   lm_golden_<robot>.npz 64 seeded rows per robot: x, target, and what the fp64 oracle (oracle/lmik_oracle.c, reference
                         operation order) returns for them -- pose error, scaled J, one LM step, 10 fused steps + metrics,
-                        self / env distances and masks.  The oracle is the ground truth of this build (the reference
-                        cannot be imported here: jrl is not vendored), so these files pin it against regressions and are
-                        what the GPU tests compare with when run without /root/reference.
+                        self / env distances and masks.  These files pin the oracle against regressions and are what the
+                        GPU tests compare with.  (The oracle itself is held to the reference's own code by
+                        reference_runs_<robot>.npz: make_reference_runs.py runs the reference's cppflow modules over a stand-in
+                        jrl and records what they return.)
 """
 import os
 import sys
