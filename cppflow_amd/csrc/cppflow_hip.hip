@@ -94,6 +94,7 @@ int fail(int code, const std::string& msg) {
     } while (0)
 
 inline unsigned grid_for(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
+inline size_t up16(size_t b) { return (b + 15) / 16 * 16; }
 
 struct RtcModule;  // rtc_specialize.h
 
@@ -330,14 +331,6 @@ constexpr int kPcrMaxRowsLds = 131072, kPcrMaxRowsGlobal = 49152;
 // per lane there and lost 9 %; profiles/r4_pcr_ab.txt
 constexpr int kPcrSplitMaxD = 8;
 
-// launch one of the run-time-specialised kernels of a handle (same argument lists as the compiled-in instantiations)
-int rtc_launch(const cppf_robot* rb, RtcKernel which, unsigned grid, size_t lds, hipStream_t st, void** args) {
-    hipFunction_t f = rb->rtc->fn[which];
-    if (!f) return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: this kernel is not part of the handle's specialised module");
-    CPPF_HIP(hipModuleLaunchKernel(f, grid, 1, 1, (unsigned)kBlock, 1, 1, (unsigned)lds, st, args, nullptr));
-    return CPPF_OK;
-}
-
 inline bool use_rtc(const cppf_robot* rb) { return rb->rtc != nullptr && !tune(rb, CPPF_TUNE_FORCE_GENERIC); }
 
 int check_launch() {
@@ -365,23 +358,76 @@ struct DeviceGuard {
     DeviceGuard& operator=(const DeviceGuard&) = delete;
 };
 
+// has cppf_robot_destroy been called on the handle (it is then only kept allocated for its live batches)?
+inline bool robot_destroyed(const cppf_robot* rb) { return (rb->life.load(std::memory_order_acquire) & kRobotDead) != 0; }
+
+// what every call that reads the handle asks of it before anything else, in the short words of the calls that check their arguments
+// before they select a device (CPPF_ENTER, which selects it, says more)
+#define CPPF_ROBOT_ALIVE(rb)                                 \
+    CPPF_REQUIRE((rb) != nullptr, "robot handle is NULL"); \
+    CPPF_REQUIRE(!robot_destroyed(rb), "the robot handle was destroyed")
+
 #define CPPF_ENTER(rb)                                                                                              \
     CPPF_REQUIRE((rb) != nullptr, "robot handle is NULL");                                                          \
-    CPPF_REQUIRE(!((rb)->life.load(std::memory_order_acquire) & kRobotDead),                                         \
+    CPPF_REQUIRE(!robot_destroyed(rb),                                                                               \
                  "the robot handle was destroyed (cppf_robot_destroy; it is only kept allocated for its live batches)"); \
     DeviceGuard device_guard__((rb)->device);                                                                        \
     if (device_guard__.err != hipSuccess)                                                                            \
         return fail(CPPF_ERR_HIP, std::string("cppflow_hip: selecting the robot's device failed: ") +               \
                                       hipGetErrorString(device_guard__.err))
 
-// a launch with `lds` bytes of dynamic LDS: beyond 64 KB the kernel's own limit is raised first (per device: set whenever it is
-// needed, a host-side table update)
+// ---- launches ------------------------------------------------------------------------------------------------------------------
+// A launch that claims `lds` bytes of dynamic LDS: beyond 64 KB the limit of THIS kernel is raised first (per device: set whenever
+// it is needed, a host-side table update).  Errors of the launch itself are the caller's check_launch().
 template <class K, class... A>
-int launch_lds(K kernel, dim3 grid, size_t lds, hipStream_t st, const A&... args) {
+int launch(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t st, const A&... args) {
     if (lds > (size_t)64 * 1024)
         CPPF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), lds, st, args...);
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
     return CPPF_OK;
+}
+
+// The one place that turns a kernel and its arguments into the untyped (function, void**) pair hipLaunchKernel and
+// hipModuleLaunchKernel take.  That route copies sizeof(parameter) bytes from each address and converts nothing, so the arguments'
+// types must BE the parameter list of the typed kernel -- which the compiler checks here.  Lvalues only: the addresses are read by
+// the launch that follows, where a temporary would be gone.
+template <class...>
+struct Types {};
+template <class... P>
+struct KernelArgs {
+    const void* fn;
+    void* ptr[sizeof...(P)];
+    template <class... A>
+    explicit KernelArgs(void (*kernel)(P...), A&... a) : fn(reinterpret_cast<const void*>(kernel)), ptr{(void*)&a...} {
+        static_assert(std::is_same<Types<P...>, Types<std::decay_t<A>...>>::value,
+                      "the arguments are not the kernel's parameter list (this route applies no implicit conversion)");
+    }
+};
+
+// Launch kernel `which` of the handle's run-time-specialised module.  `same` is a compiled-in instantiation of the same kernel
+// template -- of any robot type, the parameter list does not depend on it -- and is what the arguments are checked against.
+template <class... P, class... A>
+int rtc_launch(const cppf_robot* rb, RtcKernel which, void (*same)(P...), unsigned grid, unsigned block, size_t lds, hipStream_t st,
+               const A&... args) {
+    hipFunction_t f = rb->rtc->fn[which];
+    if (!f) return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: this kernel is not part of the handle's specialised module");
+    KernelArgs<P...> ka(same, args...);
+    CPPF_HIP(hipModuleLaunchKernel(f, grid, 1, 1, block, 1, 1, (unsigned)lds, st, ka.ptr, nullptr));
+    return CPPF_OK;
+}
+
+// The route of the heavy kernels that exist in all three forms (collision, quad, track): the handle's specialised module, else the
+// kernel of a generated table, else the generic one.  pick(tag) names the compiled-in instantiation for a robot type (NULL: there is
+// none for this type, nothing is launched); kernel `which` of the module takes the same arguments, checked against the generic
+// six-joint instantiation, which every one of these kernels has.
+template <class Pick, class... A>
+int launch_routed(const cppf_robot* rb, RtcKernel which, Pick&& pick, unsigned grid, unsigned block, size_t lds, hipStream_t st,
+                  const A&... args) {
+    if (use_rtc(rb)) return rtc_launch(rb, which, pick(RobotTag<DynRobot<6>>{}), grid, block, lds, st, args...);
+    return for_robot(rb, [&](auto tag) {
+        const auto kernel = pick(tag);
+        return kernel ? launch(kernel, dim3(grid), dim3(block), lds, st, args...) : CPPF_OK;
+    });
 }
 
 // ---- what the calls over a scene in device memory share (kernels_scene.h) ----------------------------------------------------------
@@ -432,8 +478,7 @@ template <class Shape, class Need>
 int check_scene_call(const cppf_robot* robot, Shape&& shape, int n_obs, float reach_m, bool io_ok, const char* io_msg, const float* box_lo,
                      const float* box_hi, const void* workspace, size_t workspace_bytes, Need&& need, const char* need_msg,
                      const char* kernel, size_t* lds) {
-    CPPF_REQUIRE(robot != nullptr, "robot handle is NULL");
-    CPPF_REQUIRE(!(robot->life.load(std::memory_order_acquire) & kRobotDead), "the robot handle was destroyed");
+    CPPF_ROBOT_ALIVE(robot);
     if (int rc = shape()) return rc;
     CPPF_REQUIRE(n_obs >= 0 && n_obs <= CPPF_MAX_SCENE_OBSTACLES, "n_obs out of range (0 .. CPPF_MAX_SCENE_OBSTACLES)");
     CPPF_REQUIRE(reach_m >= 0.f, "reach_m must be in [0, +inf] (not NaN, not negative)");
@@ -448,6 +493,18 @@ int check_scene_call(const cppf_robot* robot, Shape&& shape, int n_obs, float re
     *lds = use_table(robot) ? 0 : robot->lds_bytes;
     if (*lds > (size_t)160 * 1024 - 1024)
         return fail(CPPF_ERR_UNSUPPORTED, std::string("cppflow_hip: the generic ") + kernel + " kernel cannot stage this many capsules");
+    return CPPF_OK;
+}
+
+// a cuboid (min corner, max corner in its own frame) under Rt = [R | t] -> its corners in the world; R must be the identity
+int cuboid_corners(const float* cuboid, const float* Rt, float (&lo)[3], float (&hi)[3]) {
+    const float I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    for (int k = 0; k < 9; ++k)
+        CPPF_REQUIRE(std::fabs(Rt[k] - I[k]) < 1e-8f, "only axis-aligned cuboids are supported (R must be I)");
+    for (int k = 0; k < 3; ++k) {
+        lo[k] = Rt[9 + k] + cuboid[k];
+        hi[k] = Rt[9 + k] + cuboid[3 + k];
+    }
     return CPPF_OK;
 }
 
@@ -694,14 +751,12 @@ int cppf_set_obstacles(cppf_robot* robot, int n_obs, const float* cuboids, const
     CPPF_REQUIRE(n_obs >= 0 && n_obs <= CPPF_MAX_OBSTACLES, "n_obs out of range");
     CPPF_REQUIRE(n_obs == 0 || (cuboids && Rt), "cuboids / Rt is NULL");
     for (int o = 0; o < n_obs; ++o) {
-        const float* R = Rt + o * 12;
-        const float I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-        for (int k = 0; k < 9; ++k)
-            CPPF_REQUIRE(std::fabs(R[k] - I[k]) < 1e-8f, "only axis-aligned cuboids are supported (R must be I)");
+        float lo[3], hi[3];
+        if (int rc = cuboid_corners(cuboids + o * 6, Rt + o * 12, lo, hi)) return rc;
         for (int k = 0; k < 3; ++k) {
             CPPF_REQUIRE(cuboids[o * 6 + k] <= cuboids[o * 6 + 3 + k], "cuboid min corner > max corner");
-            robot->coll.obs_lo[o][k] = R[9 + k] + cuboids[o * 6 + k];
-            robot->coll.obs_hi[o][k] = R[9 + k] + cuboids[o * 6 + 3 + k];
+            robot->coll.obs_lo[o][k] = lo[k];
+            robot->coll.obs_hi[o][k] = hi[k];
         }
     }
     robot->coll.nobs = n_obs;
@@ -862,8 +917,9 @@ int launch_fused_rows(const cppf_robot* robot, int coll, size_t n_rows, unsigned
     fa.single = single;
     fa.table = table;
     if (use_rtc(robot)) {
-        void* args[] = {(void*)&fa.ch, (void*)&fa.co, (void*)&fa.prm, (void*)&fa.single, (void*)&fa.table};
-        if (int rc = rtc_launch(robot, coll == 0 ? RTC_FUSED0 : (coll == 2 ? RTC_FUSED2 : RTC_FUSED1), grid, spread, st, args)) return rc;
+        if (int rc = rtc_launch(robot, coll == 0 ? RTC_FUSED0 : (coll == 2 ? RTC_FUSED2 : RTC_FUSED1), &lm_fused_kernel<DynRobot<6>, 0>, grid,
+                                kBlock, spread, st, fa.ch, fa.co, fa.prm, fa.single, fa.table))
+            return rc;
     } else if (!generic) {
         // a generated table: the kernel lives in fused_static.hip
         if (!launch_fused_static(robot->static_id, coll, grid, spread, st, fa))
@@ -872,28 +928,16 @@ int launch_fused_rows(const cppf_robot* robot, int coll, size_t n_rows, unsigned
         const size_t lds = std::max(lds_need, spread);
         const int rc = for_dyn_robot(robot, [&](auto tag) {
             using RB = typename decltype(tag)::type;
-            if (coll == 2)
-                hipLaunchKernelGGL((lm_fused_kernel<RB, 2>), dim3(grid), dim3(kBlock), lds, st, fa.ch, fa.co, fa.prm, fa.single, fa.table);
-            else if (coll == 1)
-                hipLaunchKernelGGL((lm_fused_kernel<RB, 1>), dim3(grid), dim3(kBlock), lds, st, fa.ch, fa.co, fa.prm, fa.single, fa.table);
-            else
-                hipLaunchKernelGGL((lm_fused_kernel<RB, 0>), dim3(grid), dim3(kBlock), lds, st, fa.ch, fa.co, fa.prm, fa.single, fa.table);
-            return CPPF_OK;
+            const auto kernel = coll == 2 ? lm_fused_kernel<RB, 2> : coll == 1 ? lm_fused_kernel<RB, 1> : lm_fused_kernel<RB, 0>;
+            return launch(kernel, dim3(grid), dim3(kBlock), lds, st, fa.ch, fa.co, fa.prm, fa.single, fa.table);
         });
         if (rc) return rc;
     }
     return check_launch();
 }
 
-// the one spelling of the quad-shape kernel's launch (kernels_quad.h); launch_quad picks the instantiation
-template <class RB, int COLL, bool MFMA>
-void launch_quad_kernel(const cppf_robot* robot, unsigned grid, size_t lds, hipStream_t st, const LmK& prm, const float* x_in,
-                        const float* target, const cppf_lm_outputs& oq, const uint4* tab, const StepGateK gate) {
-    hipLaunchKernelGGL((lm_quad_kernel<RB, COLL, MFMA>), dim3(grid), dim3(kBlock), lds, st, robot->chain, robot->coll, prm, x_in, target,
-                       oq, tab, gate);
-}
-
-// One launch of the quad-shape kernel over n rows; `gate` = { NULL } unless the optimiser loop on the device asks
+// One launch of the quad-shape kernel (kernels_quad.h) over n rows; `gate` = { NULL } unless the optimiser loop on the device asks.
+// The callers hold ndof >= 6 (quad_possible, cppf_lm_optimize_enqueue_pinned): below that there is no such kernel on any route.
 int launch_quad(const cppf_robot* robot, bool coll, size_t n, hipStream_t st, const LmK& prm, const float* x_in, const float* target,
                 const cppf_lm_outputs& oq, const StepGateK gate) {
     const unsigned grid = (unsigned)((n + kQuadRows - 1) / kQuadRows);
@@ -902,20 +946,18 @@ int launch_quad(const cppf_robot* robot, bool coll, size_t n, hipStream_t st, co
                               : 0;
     const uint4* tab = static_cast<const uint4*>(robot->d_quad);
     const bool mfma = tune(robot, CPPF_TUNE_QUAD_MFMA) && use_table(robot);
-    if (use_rtc(robot) && robot->rtc->fn[RTC_QUAD0]) {
-        void* args[] = {(void*)&robot->chain, (void*)&robot->coll, (void*)&prm, (void*)&x_in, (void*)&target, (void*)&oq, (void*)&tab, (void*)&gate};
-        return rtc_launch(robot, coll ? RTC_QUAD1 : RTC_QUAD0, grid, lds_q, st, args);
-    }
-    return for_robot(robot, [&](auto tag) {
+    using QuadKernel = decltype(&lm_quad_kernel<DynRobot<6>, 0, false>);
+    const auto pick = [&](auto tag) -> QuadKernel {
         using RB = typename decltype(tag)::type;
         if constexpr (RB::D >= 6) {  // (the quad shape solves the dual 6x6 system)
             constexpr bool kTable = RB::kStatic;  // the MFMA form is instantiated for the generated tables only
-            const auto launch = coll ? (mfma ? launch_quad_kernel<RB, 1, kTable> : launch_quad_kernel<RB, 1, false>)
-                                     : (mfma ? launch_quad_kernel<RB, 0, kTable> : launch_quad_kernel<RB, 0, false>);
-            launch(robot, grid, lds_q, st, prm, x_in, target, oq, tab, gate);
-        }
-        return CPPF_OK;
-    });
+            return coll ? (mfma ? lm_quad_kernel<RB, 1, kTable> : lm_quad_kernel<RB, 1, false>)
+                        : (mfma ? lm_quad_kernel<RB, 0, kTable> : lm_quad_kernel<RB, 0, false>);
+        } else
+            return nullptr;
+    };
+    return launch_routed(robot, coll ? RTC_QUAD1 : RTC_QUAD0, pick, grid, kBlock, lds_q, st, robot->chain, robot->coll, prm, x_in, target, oq, tab,
+                         gate);
 }
 
 inline bool quad_possible(const cppf_robot* robot, const cppf_lm_outputs& out) {
@@ -934,23 +976,14 @@ int collision_masks_gated(const cppf_robot* robot, const float* q, int S, int W,
     CPPF_REQUIRE(n <= 0x7fffffffu, "S*W exceeds 2^31-1 rows");
     CPPF_REQUIRE(q, "q is NULL");
     hipStream_t st = (hipStream_t)stream;
-    const size_t lds = use_table(robot) ? 0 : robot->lds_bytes;
-    if (use_rtc(robot)) {
-        int n_i = (int)n;
-        void* args[] = {(void*)&robot->chain, (void*)&robot->coll, (void*)&n_i, (void*)&q, (void*)&self_mask, (void*)&env_mask,
-                        (void*)&jlim_mask, (void*)&ext_cost, (void*)&min_self, (void*)&min_env, (void*)&gate, (void*)&W};
-        return rtc_launch(robot, (min_self || min_env) ? RTC_COLL_MIN : RTC_COLL_MASK, grid_for(n), 0, st, args);
-    }
-    const int rc = for_robot(robot, [&](auto tag) {
+    const bool want_min = min_self || min_env;
+    const size_t lds = (use_rtc(robot) || use_table(robot)) ? 0 : robot->lds_bytes;  // only the generic kernel stages its capsules
+    const auto pick = [&](auto tag) {
         using RB = typename decltype(tag)::type;
-        if (min_self || min_env)
-            hipLaunchKernelGGL((collision_kernel<RB, true>), dim3(grid_for(n)), dim3(kBlock), lds, st, robot->chain, robot->coll, (int)n,
-                               q, self_mask, env_mask, jlim_mask, ext_cost, min_self, min_env, gate, W);
-        else
-            hipLaunchKernelGGL((collision_kernel<RB, false>), dim3(grid_for(n)), dim3(kBlock), lds, st, robot->chain, robot->coll, (int)n,
-                               q, self_mask, env_mask, jlim_mask, ext_cost, min_self, min_env, gate, W);
-        return CPPF_OK;
-    });
+        return want_min ? collision_kernel<RB, true> : collision_kernel<RB, false>;
+    };
+    const int rc = launch_routed(robot, want_min ? RTC_COLL_MIN : RTC_COLL_MASK, pick, grid_for(n), kBlock, lds, st, robot->chain, robot->coll,
+                                 (int)n, q, self_mask, env_mask, jlim_mask, ext_cost, min_self, min_env, gate, W);
     return rc ? rc : check_launch();
 }
 
@@ -988,8 +1021,7 @@ const char* const kGatedFormRefusal =
 int full_step_pin_check(const cppf_robot* robot, int S, int W, const cppf_full_params* params, int pin) {
     CPPF_REQUIRE(pin >= 0 && pin <= (CPPF_PIN_FIRST | CPPF_PIN_LAST), "pin_mask must be a combination of CPPF_PIN_FIRST and CPPF_PIN_LAST");
     if (pin == 0) return CPPF_OK;
-    CPPF_REQUIRE(robot != nullptr, "robot handle is NULL");
-    CPPF_REQUIRE(!(robot->life.load(std::memory_order_acquire) & kRobotDead), "the robot handle was destroyed");
+    CPPF_ROBOT_ALIVE(robot);
     CPPF_REQUIRE(params, "params is NULL");
     if (params->differencing_mode != 0 || params->pose_do_scale_down_satisfied)
         return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: a pinned end waypoint is not combined with the \"satisfied\" row options "
@@ -1069,34 +1101,28 @@ int lm_full_step_gated(const cppf_robot* robot, const float* x_in, const float* 
     hipStream_t st = (hipStream_t)stream;
     const int rc = for_robot(robot, [&](auto tag) {
         using RB = typename decltype(tag)::type;
-        if (form == FullStepForm::Local) {
-            // Six pose rows against seven or eight joints and nothing else on the diagonal but lambda: the blocks in fp64, solved by
-            // the lane that builds them (full_local_solve).  The unconstrained build at every size: the fp64 block is 2 x d(d+3)/2
-            // registers on top of the rows'.
-            if (scene != nullptr) {
-                SceneStepK sc = *scene;
-                sc.tile_cull2 = tile_cull_threshold(robot, 0.f);
-                hipLaunchKernelGGL((full_blocks_kernel<RB, 0, true, true>), dim3(grid_for(n)), dim3(kBlock), robot->lds_bytes, st, robot->chain,
-                                   robot->coll, prm, x_in, target, virtual_configs, work_blocks, w2next, sc, x_out);
-            } else
-                hipLaunchKernelGGL((full_blocks_kernel<RB, 0, false, true>), dim3(grid_for(n)), dim3(kBlock), robot->lds_bytes, st, robot->chain,
-                                   robot->coll, prm, x_in, target, virtual_configs, work_blocks, w2next, gate, x_out);
-        } else if (scene != nullptr) {
-            // ONE instantiation per robot, the unconstrained build: a planner steps S <= 8 trajectories, far below the row count at
-            // which the occupancy-bound build of the handle form pays.  (A handle specialised at run time takes the generic form,
-            // like every coupled step: for_robot.)
+        // Local -- six pose rows against seven or eight joints and nothing else on the diagonal but lambda: the blocks in fp64, solved
+        // by the lane that builds them (full_local_solve), which writes x_out.  The unconstrained build at every size: the fp64 block
+        // is 2 x d(d+3)/2 registers on top of the rows'.
+        const bool local = form == FullStepForm::Local;
+        // one argument list for the five instantiations in use; they differ in the tail: the scene's cuboids or the gate
+        const auto blocks = [&](auto kernel, const auto& tail) {
+            return launch(kernel, dim3(grid_for(n)), dim3(kBlock), robot->lds_bytes, st, robot->chain, robot->coll, prm, x_in, target,
+                          virtual_configs, work_blocks, w2next, tail, local ? x_out : (float*)nullptr);
+        };
+        if (scene != nullptr) {
+            // Outside Local, too, ONE instantiation per robot, the unconstrained build: a planner steps S <= 8 trajectories, far below
+            // the row count at which the occupancy-bound build of the handle form pays.  (A handle specialised at run time takes the
+            // generic form, like every coupled step: for_robot.)
             SceneStepK sc = *scene;
             sc.tile_cull2 = tile_cull_threshold(robot, 0.f);
             // (dynamic LDS as for the handle form beside it: chain12's 13 capsules are 78 KB in both)
-            hipLaunchKernelGGL((full_blocks_kernel<RB, 0, true>), dim3(grid_for(n)), dim3(kBlock), robot->lds_bytes, st, robot->chain,
-                               robot->coll, prm, x_in, target, virtual_configs, work_blocks, w2next, sc, (float*)nullptr);
-        } else if (n >= 131072)
-            hipLaunchKernelGGL((full_blocks_kernel<RB, full_blocks_occ<RB>()>), dim3(grid_for(n)), dim3(kBlock), robot->lds_bytes, st,
-                               robot->chain, robot->coll, prm, x_in, target, virtual_configs, work_blocks, w2next, gate, (float*)nullptr);
-        else
-            hipLaunchKernelGGL((full_blocks_kernel<RB>), dim3(grid_for(n)), dim3(kBlock), robot->lds_bytes, st, robot->chain,
-                               robot->coll, prm, x_in, target, virtual_configs, work_blocks, w2next, gate, (float*)nullptr);
-        return CPPF_OK;
+            return blocks(local ? full_blocks_kernel<RB, 0, true, true> : full_blocks_kernel<RB, 0, true>, sc);
+        }
+        return blocks(local             ? full_blocks_kernel<RB, 0, false, true>
+                      : n >= 131072 ? full_blocks_kernel<RB, full_blocks_occ<RB>()>
+                                    : full_blocks_kernel<RB>,
+                      gate);
     });
     if (rc) return rc;
     if (form == FullStepForm::Local) return check_launch();
@@ -1121,37 +1147,27 @@ int lm_full_step_gated(const cppf_robot* robot, const float* x_in, const float* 
                 // trajectory, one lane per waypoint; beyond that its O(T log T) work and traffic lose against the
                 // waypoint-after-waypoint kernels.
                 if constexpr (D <= 8) {  // (full_step_form: the parallel-in-time form exists for 3 .. 8 joints)
-                    if (W <= 256 && g_pcr_lds) {  // the state in LDS: 256 x ((d(d+1)/2 + d + d^2) | 1) floats
-                        constexpr size_t kState = 256 * (size_t)((D * (D + 1) / 2 + D + D * D) | 1) * sizeof(float);
-                        CPPF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&full_solve_pcr_kernel<D, 256, true>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)kState));
-                        if (g_pcr_split && (D <= kPcrSplitMaxD || t_pcr_lds == 3)) {  // see kPcrSplitMaxD; 3 forces the split form
-                            CPPF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&full_solve_pcr_kernel<D, 512, true, true>),
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)kState));
-                            hipLaunchKernelGGL((full_solve_pcr_kernel<D, 512, true, true>), dim3((unsigned)S), dim3(512), kState, st, robot->chain, prm, x_in,
-                                           virtual_configs, work_blocks, work_G, x_out, gate);
-                        } else
-                            hipLaunchKernelGGL((full_solve_pcr_kernel<D, 256, true>), dim3((unsigned)S), dim3(256), kState, st, robot->chain, prm, x_in,
-                                           virtual_configs, work_blocks, work_G, x_out, gate);
-                    } else if (W <= 256)
-                        hipLaunchKernelGGL((full_solve_pcr_kernel<D, 256>), dim3((unsigned)S), dim3(256), 0, st, robot->chain, prm, x_in,
-                                           virtual_configs, work_blocks, work_G, x_out, gate);
-                    else
-                        hipLaunchKernelGGL((full_solve_pcr_kernel<D, 512>), dim3((unsigned)S), dim3(512), 0, st, robot->chain, prm, x_in,
-                                           virtual_configs, work_blocks, work_G, x_out, gate);
+                    // the four forms: the state in LDS (W <= 256: 256 x ((d(d+1)/2 + d + d^2) | 1) floats), on 256 lanes or split over 512
+                    // (see kPcrSplitMaxD; CPPF_TUNE_PCR_LDS = 3 forces the split form), else in the workspace, on 256 or 512 lanes
+                    constexpr size_t kState = 256 * (size_t)((D * (D + 1) / 2 + D + D * D) | 1) * sizeof(float);
+                    const bool in_lds = W <= 256 && g_pcr_lds;
+                    const bool split = in_lds && g_pcr_split && (D <= kPcrSplitMaxD || t_pcr_lds == 3);
+                    const auto kernel = split      ? full_solve_pcr_kernel<D, 512, true, true>
+                                        : in_lds   ? full_solve_pcr_kernel<D, 256, true>
+                                        : W <= 256 ? full_solve_pcr_kernel<D, 256>
+                                                   : full_solve_pcr_kernel<D, 512>;
+                    if (int rc2 = launch(kernel, dim3((unsigned)S), dim3(split || W > 256 ? 512 : 256), in_lds ? kState : 0, st, robot->chain, prm,
+                                         x_in, virtual_configs, work_blocks, work_G, x_out, gate))
+                        return rc2;
                 }
                 break;
             case FullStepForm::Rows:  // (every ndof; sixteen lanes per trajectory at 9 .. 12 joints, see rows_tpw)
-                if (rows_lds > 64 * 1024) {  // per device: set whenever it is needed, a host-side table update
-                    CPPF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&full_rows_eliminate_kernel<D>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-                    CPPF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&full_rows_substitute_kernel<D>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-                }
-                hipLaunchKernelGGL((full_rows_eliminate_kernel<D>), dim3(rows_wgs), dim3(64), rows_lds, st, prm, pris_mask, work_blocks,
-                                   work_G, work_y, gate);
-                hipLaunchKernelGGL((full_rows_substitute_kernel<D>), dim3(rows_wgs), dim3(64), rows_lds, st, prm, pris_mask, x_in,
-                                   work_blocks, work_G, work_y, x_out, gate);
+                if (int rc2 = launch(full_rows_eliminate_kernel<D>, dim3(rows_wgs), dim3(64), rows_lds, st, prm, pris_mask, work_blocks, work_G,
+                                     work_y, gate))
+                    return rc2;
+                if (int rc2 = launch(full_rows_substitute_kernel<D>, dim3(rows_wgs), dim3(64), rows_lds, st, prm, pris_mask, x_in, work_blocks,
+                                     work_G, work_y, x_out, gate))
+                    return rc2;
                 break;
             case FullStepForm::Wave:  // one trajectory per wavefront (8 x 8 lane tile), up to 8 joints
                 if constexpr (D <= 8)
@@ -1352,16 +1368,10 @@ int cppf_env_collision_distances(const cppf_robot* robot, const float* x, int n,
     CPPF_ENTER(robot);
     CPPF_REQUIRE(n >= 0, "n < 0");
     CPPF_REQUIRE(cuboid && Rt, "cuboid / Rt is NULL");
-    const float I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    for (int k = 0; k < 9; ++k)
-        CPPF_REQUIRE(std::fabs(Rt[k] - I[k]) < 1e-8f, "only axis-aligned cuboids are supported (R must be I)");
+    float lo[3], hi[3];
+    if (int rc = cuboid_corners(cuboid, Rt, lo, hi)) return rc;
     if (n == 0 || robot->coll.ncaps == 0) return CPPF_OK;
     CPPF_REQUIRE(x && dists, "x / dists is NULL");
-    float lo[3], hi[3];
-    for (int k = 0; k < 3; ++k) {
-        lo[k] = Rt[9 + k] + cuboid[k];
-        hi[k] = Rt[9 + k] + cuboid[3 + k];
-    }
     hipStream_t st = (hipStream_t)stream;
     return for_ndof(robot->desc.ndof, [&](auto dof) {
         hipLaunchKernelGGL((distances_kernel<decltype(dof)::D, true>), dim3(grid_for(n)), dim3(kBlock), robot->lds_bytes, st,
@@ -1389,16 +1399,10 @@ int cppf_env_collision_distances_jacobian(const cppf_robot* robot, const float* 
     CPPF_ENTER(robot);
     CPPF_REQUIRE(n >= 0, "n < 0");
     CPPF_REQUIRE(cuboid && Rt, "cuboid / Rt is NULL");
-    const float I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    for (int k = 0; k < 9; ++k)
-        CPPF_REQUIRE(std::fabs(Rt[k] - I[k]) < 1e-8f, "only axis-aligned cuboids are supported (R must be I)");
+    float lo[3], hi[3];
+    if (int rc = cuboid_corners(cuboid, Rt, lo, hi)) return rc;
     if (n == 0 || robot->coll.ncaps == 0) return CPPF_OK;
     CPPF_REQUIRE(x && jac, "x / jac is NULL");
-    float lo[3], hi[3];
-    for (int k = 0; k < 3; ++k) {
-        lo[k] = Rt[9 + k] + cuboid[k];
-        hi[k] = Rt[9 + k] + cuboid[3 + k];
-    }
     hipStream_t st = (hipStream_t)stream;
     return for_ndof(robot->desc.ndof, [&](auto dof) {
         hipLaunchKernelGGL((distance_jacobians_kernel<decltype(dof)::D, true>), dim3(grid_for(n)), dim3(kBlock), robot->lds_bytes, st,
@@ -1426,8 +1430,7 @@ int cppf_pose_error_metrics(const cppf_robot* robot, const float* x, const float
 int cppf_track_paths(const cppf_robot* robot, const float* target, int T, int k, int S, const cppf_track_params* params,
                      const float* q0, float* q_out, float* pos_err_m, float* rot_err_rad, uint8_t* status, void* stream) {
     // every argument is checked before the device is selected (CPPF_ENTER), so that the checks hold for a host-only handle too
-    CPPF_REQUIRE(robot != nullptr, "robot handle is NULL");
-    CPPF_REQUIRE(!(robot->life.load(std::memory_order_acquire) & kRobotDead), "the robot handle was destroyed");
+    CPPF_ROBOT_ALIVE(robot);
     CPPF_REQUIRE(params, "params is NULL");
     CPPF_REQUIRE(T >= 0 && k >= 0, "T / k < 0");
     CPPF_REQUIRE(S >= 1, "S (segments) must be >= 1");
@@ -1461,16 +1464,8 @@ int cppf_track_paths(const cppf_robot* robot, const float* target, int T, int k,
     tk.seed = params->seed, tk.call_index = params->call_index;
     hipStream_t st = (hipStream_t)stream;
     const unsigned grid = (unsigned)(((size_t)k * S + kTrackBlock - 1) / kTrackBlock);
-    if (use_rtc(robot)) {
-        void* args[] = {(void*)&robot->chain, (void*)&robot->coll, (void*)&prm, (void*)&tk};
-        CPPF_HIP(hipModuleLaunchKernel(robot->rtc->fn[RTC_TRACK], grid, 1, 1, (unsigned)kTrackBlock, 1, 1, 0, st, args, nullptr));
-        return CPPF_OK;
-    }
-    const int rc = for_robot(robot, [&](auto tag) {
-        using RB = typename decltype(tag)::type;
-        hipLaunchKernelGGL((track_kernel<RB>), dim3(grid), dim3(kTrackBlock), 0, st, robot->chain, robot->coll, prm, tk);
-        return CPPF_OK;
-    });
+    const auto pick = [](auto tag) { return &track_kernel<typename decltype(tag)::type>; };
+    const int rc = launch_routed(robot, RTC_TRACK, pick, grid, kTrackBlock, 0, st, robot->chain, robot->coll, prm, tk);
     return rc ? rc : check_launch();
 }
 
@@ -1559,8 +1554,7 @@ int cppf_lm_full_step_scene(const cppf_robot* robot, const float* x_in, const fl
                             int W, const cppf_full_params* params, int pin_mask, const float* box_lo, const float* box_hi,
                             int n_obs, float* work_blocks, float* work_G, float* work_y, float* x_out, void* stream) {
     // every argument is checked before the device is selected (CPPF_ENTER), so that the checks hold for a host-only handle too
-    CPPF_REQUIRE(robot != nullptr, "robot handle is NULL");
-    CPPF_REQUIRE(!(robot->life.load(std::memory_order_acquire) & kRobotDead), "the robot handle was destroyed");
+    CPPF_ROBOT_ALIVE(robot);
     CPPF_REQUIRE(params, "params is NULL");
     CPPF_REQUIRE(pin_mask >= 0 && pin_mask <= (CPPF_PIN_FIRST | CPPF_PIN_LAST),
                  "pin_mask must be a combination of CPPF_PIN_FIRST and CPPF_PIN_LAST");
@@ -1601,8 +1595,7 @@ OptloopLayout optloop_layout(int d, size_t S, size_t W) {
 extern "C" {
 
 int cppf_lm_optimize_workspace_bytes(const cppf_robot* robot, int S, int W, size_t* bytes) {
-    CPPF_REQUIRE(robot != nullptr, "robot handle is NULL");
-    CPPF_REQUIRE(!(robot->life.load(std::memory_order_acquire) & kRobotDead), "the robot handle was destroyed");
+    CPPF_ROBOT_ALIVE(robot);
     CPPF_REQUIRE(bytes, "bytes is NULL");
     CPPF_REQUIRE(S >= 1 && W >= 1 && (size_t)S * W <= 0x7fffffffu, "S / W must be >= 1 and S*W at most 2^31-1");
     *bytes = optloop_layout(robot->desc.ndof, (size_t)S, (size_t)W).total * sizeof(float);
@@ -1627,8 +1620,7 @@ int cppf_lm_optimize_enqueue_pinned(const cppf_robot* robot, float* x, const flo
                                     const cppf_optloop_params* params, int pin_mask, void* workspace, int32_t* control,
                                     int n_iterations, void* stream) {
     // every argument is checked before the device is selected (CPPF_ENTER), so that the checks hold for a host-only handle too
-    CPPF_REQUIRE(robot != nullptr, "robot handle is NULL");
-    CPPF_REQUIRE(!(robot->life.load(std::memory_order_acquire) & kRobotDead), "the robot handle was destroyed");
+    CPPF_ROBOT_ALIVE(robot);
     CPPF_REQUIRE(params, "params is NULL");
     CPPF_REQUIRE(S >= 1 && W >= 1, "S / W must be >= 1");
     CPPF_REQUIRE((size_t)S * W <= 0x7fffffffu, "S*W exceeds 2^31-1 rows");
@@ -1728,6 +1720,25 @@ constexpr int kDpResidentMaxK = 1024;  // four destinations per workgroup x 256 
 // dynamic LDS of dp_backtrace_kernel: the memo table as bytes when it fits (k <= 256, T k <= 60 KB), else 0 = walk it in global memory
 static size_t dp_stage_bytes(int k, int T) { return (k <= 256 && (size_t)k * T <= 60 * 1024) ? (size_t)k * T : 0; }
 
+// what cppf_dp_search and cppf_dp_search_tabled start with: q [k, T, d] -> qT [T, k, d], the cost row of the first waypoint, memo[:,0]
+static int dp_transpose_launch(hipStream_t st, const float* q, const float* ext_cost, int k, int T, int d, float* work_qT,
+                               float* work_costsT, int32_t* work_memoT) {
+    const size_t total = (size_t)k * T * d;
+    hipLaunchKernelGGL(dp_transpose_kernel, dim3(grid_for(total > (size_t)k ? total : (size_t)k)), dim3(256), 0, st, q, ext_cost, k, T, d,
+                       work_qT, work_costsT);
+    // memo[:,0] is never read by the back-trace's result but is read as a value: define it (search.py:154 zero-inits memo)
+    CPPF_HIP(hipMemsetAsync(work_memoT, 0, sizeof(int32_t) * (size_t)k, st));
+    return CPPF_OK;
+}
+
+// ... and end with: the best last candidate and its path, walked back through the memo table
+static int dp_backtrace_launch(hipStream_t st, const float* q, const float* work_costsT, const int32_t* work_memoT, int k, int T, int d,
+                               int32_t* best_idx, float* best_path) {
+    const size_t stage = dp_stage_bytes(k, T);
+    hipLaunchKernelGGL(dp_backtrace_kernel, dim3(1), dim3(256), stage, st, q, work_costsT, work_memoT, k, T, d, stage != 0, best_idx, best_path);
+    return check_launch();
+}
+
 int cppf_dp_search(const cppf_robot* robot, const float* q, const float* ext_cost, int k, int T, float prismatic_scaling,
                    float* work_qT, float* work_costsT, int32_t* work_memoT, float* best_path, int32_t* best_idx, int mode,
                    void* stream) {
@@ -1739,7 +1750,6 @@ int cppf_dp_search(const cppf_robot* robot, const float* q, const float* ext_cos
     CPPF_REQUIRE(mode != CPPF_DP_RESIDENT || k <= kDpResidentMaxK, "CPPF_DP_RESIDENT: the resident launch holds at most 1024 candidates");
     hipStream_t st = (hipStream_t)stream;
     const int d = robot->desc.ndof;
-    const size_t total = (size_t)k * T * d;
     bool persistent = T >= 2 && k <= kDpResidentMaxK &&
                       (mode == CPPF_DP_RESIDENT || (mode == CPPF_DP_AUTO && tune(robot, CPPF_TUNE_DP_PERSISTENT)));
     DpResidentForm form{nullptr, 0, 0};
@@ -1766,22 +1776,14 @@ int cppf_dp_search(const cppf_robot* robot, const float* q, const float* ext_cos
     }
     if (persistent)  // every cost word starts as "not yet" (kernels_dp.h); 16-byte multiple, from the allocation's start
         CPPF_HIP(hipMemsetAsync(work_costsT, 0xFF, sizeof(float) * (size_t)k * T, st));
-    hipLaunchKernelGGL(dp_transpose_kernel, dim3(grid_for(total > (size_t)k ? total : (size_t)k)), dim3(256), 0, st, q,
-                       ext_cost, k, T, d, work_qT, work_costsT);
-    // memo[:,0] is never read by the back-trace's result but is read as a value: define it (search.py:154 zero-inits memo)
-    CPPF_HIP(hipMemsetAsync(work_memoT, 0, sizeof(int32_t) * (size_t)k, st));
+    if (int rc = dp_transpose_launch(st, q, ext_cost, k, T, d, work_qT, work_costsT, work_memoT)) return rc;
     if (persistent) {
         const int spin_log2 = tune(robot, CPPF_TUNE_DP_SPIN_LOG2);
-        uint32_t spin = spin_log2 <= 0 ? 0u : (1u << (spin_log2 > 30 ? 30 : spin_log2));
-        uint32_t pris_mask = robot->chain.pris_mask;
-        // (the six resident kernels share one argument list)
-        void* args[] = {(void*)&work_qT, (void*)&ext_cost, (void*)&k, (void*)&T, (void*)&pris_mask, (void*)&prismatic_scaling,
-                        (void*)&work_costsT, (void*)&work_memoT, (void*)&spin};
-        CPPF_HIP(hipLaunchKernel(form.fn, dim3(form.grid), dim3((unsigned)form.block), args, 0, st));
-        hipLaunchKernelGGL(dp_backtrace_kernel, dim3(1), dim3(256), dp_stage_bytes(k, T), st, q, work_costsT, work_memoT, k, T, d,
-                       dp_stage_bytes(k, T) != 0, best_idx,
-                           best_path);
-        return check_launch();
+        const uint32_t spin = spin_log2 <= 0 ? 0u : (1u << (spin_log2 > 30 ? 30 : spin_log2));
+        const float* const qT = work_qT;
+        KernelArgs args(form.fn, qT, ext_cost, k, T, robot->chain.pris_mask, prismatic_scaling, work_costsT, work_memoT, spin);
+        CPPF_HIP(hipLaunchKernel(args.fn, dim3(form.grid), dim3((unsigned)form.block), args.ptr, 0, st));
+        return dp_backtrace_launch(st, q, work_costsT, work_memoT, k, T, d, best_idx, best_path);
     }
     const int bpb = k >= 4096 ? 4 : (k >= 2048 ? 2 : 1);
     const unsigned blocks = (unsigned)((k + bpb - 1) / bpb);
@@ -1790,25 +1792,15 @@ int cppf_dp_search(const cppf_robot* robot, const float* q, const float* ext_cos
         const float* qc = work_qT + (size_t)t * k * d;
         const int rc = for_ndof(d, [&](auto dof) {
             constexpr int D = decltype(dof)::D;
-            const auto step = [&](auto bpb_tag) {  // the destinations per workgroup, as a constant
-                hipLaunchKernelGGL((dp_step_kernel<D, decltype(bpb_tag)::value>), dim3(blocks), dim3(256), 0, st, qp, qc,
-                                   work_costsT + (size_t)(t - 1) * k, ext_cost, k, T, t, robot->chain.pris_mask, prismatic_scaling,
-                                   work_costsT + (size_t)t * k, work_memoT + (size_t)t * k);
-            };
-            if (bpb == 4)
-                step(std::integral_constant<int, 4>{});
-            else if (bpb == 2)
-                step(std::integral_constant<int, 2>{});
-            else
-                step(std::integral_constant<int, 1>{});
+            // (the destinations per workgroup are a constant of the kernel)
+            const auto step = bpb == 4 ? dp_step_kernel<D, 4> : bpb == 2 ? dp_step_kernel<D, 2> : dp_step_kernel<D, 1>;
+            hipLaunchKernelGGL(step, dim3(blocks), dim3(256), 0, st, qp, qc, work_costsT + (size_t)(t - 1) * k, ext_cost, k, T, t,
+                               robot->chain.pris_mask, prismatic_scaling, work_costsT + (size_t)t * k, work_memoT + (size_t)t * k);
             return CPPF_OK;
         });
         if (rc) return rc;
     }
-    hipLaunchKernelGGL(dp_backtrace_kernel, dim3(1), dim3(256), dp_stage_bytes(k, T), st, q, work_costsT, work_memoT, k, T, d,
-                       dp_stage_bytes(k, T) != 0, best_idx,
-                       best_path);
-    return check_launch();
+    return dp_backtrace_launch(st, q, work_costsT, work_memoT, k, T, d, best_idx, best_path);
 }
 
 int cppf_dp_table_floats(int k, int T, size_t* n_floats) {
@@ -1827,11 +1819,7 @@ int cppf_dp_search_tabled(const cppf_robot* robot, const float* q, const float* 
     CPPF_REQUIRE(T == 1 || work_table, "work_table is NULL");
     hipStream_t st = (hipStream_t)stream;
     const int d = robot->desc.ndof, kp = (k + 63) / 64 * 64;
-    const size_t total = (size_t)k * T * d;
-    hipLaunchKernelGGL(dp_transpose_kernel, dim3(grid_for(total > (size_t)k ? total : (size_t)k)), dim3(256), 0, st, q,
-                       ext_cost, k, T, d, work_qT, work_costsT);
-    // memo[:,0] is never read by the back-trace's result but is read as a value: define it (search.py:154 zero-inits memo)
-    CPPF_HIP(hipMemsetAsync(work_memoT, 0, sizeof(int32_t) * (size_t)k, st));
+    if (int rc = dp_transpose_launch(st, q, ext_cost, k, T, d, work_qT, work_costsT, work_memoT)) return rc;
     if (T >= 2) {
         CPPF_REQUIRE(T - 1 <= 65535, "cppf_dp_search_tabled: T <= 65536");
         const int rc = for_ndof(d, [&](auto dof) {
@@ -1842,19 +1830,12 @@ int cppf_dp_search_tabled(const cppf_robot* robot, const float* q, const float* 
         });
         if (rc) return rc;
         const uint32_t* tab = reinterpret_cast<const uint32_t*>(work_table);
-        switch (kp) {
-            case 64: hipLaunchKernelGGL(dp_chain_kernel<64>, dim3(1), dim3(512), 0, st, tab, ext_cost, k, T, work_costsT); break;
-            case 128: hipLaunchKernelGGL(dp_chain_kernel<128>, dim3(1), dim3(512), 0, st, tab, ext_cost, k, T, work_costsT); break;
-            case 192: hipLaunchKernelGGL(dp_chain_kernel<192>, dim3(1), dim3(512), 0, st, tab, ext_cost, k, T, work_costsT); break;
-            default: hipLaunchKernelGGL(dp_chain_kernel<256>, dim3(1), dim3(512), 0, st, tab, ext_cost, k, T, work_costsT); break;
-        }
+        const auto chain = kp == 64 ? dp_chain_kernel<64> : kp == 128 ? dp_chain_kernel<128> : kp == 192 ? dp_chain_kernel<192> : dp_chain_kernel<256>;
+        hipLaunchKernelGGL(chain, dim3(1), dim3(512), 0, st, tab, ext_cost, k, T, work_costsT);
         hipLaunchKernelGGL(dp_memo_kernel, dim3((unsigned)((k + 63) / 64), (unsigned)(T - 1)), dim3(256), 0, st, tab, ext_cost,
                            work_costsT, k, kp, T, work_memoT);
     }
-    hipLaunchKernelGGL(dp_backtrace_kernel, dim3(1), dim3(256), dp_stage_bytes(k, T), st, q, work_costsT, work_memoT, k, T, d,
-                       dp_stage_bytes(k, T) != 0, best_idx,
-                       best_path);
-    return check_launch();
+    return dp_backtrace_launch(st, q, work_costsT, work_memoT, k, T, d, best_idx, best_path);
 }
 
 static size_t dp_nbest_workspace_words(int k, int T, int n_paths) {  // idxT [T][k], order / alive / far [k], sel [n_paths]
@@ -1865,7 +1846,7 @@ int cppf_dp_nbest_workspace_bytes(int k, int T, int n_paths, size_t* bytes) {
     CPPF_REQUIRE(bytes, "bytes is NULL");
     CPPF_REQUIRE(k >= 1 && T >= 1 && n_paths >= 1, "k, T, n_paths must be >= 1");
     CPPF_REQUIRE((size_t)k * T <= 0x7fffffffu, "k*T exceeds 2^31-1");
-    *bytes = (dp_nbest_workspace_words(k, T, n_paths) * sizeof(int32_t) + 15) / 16 * 16;
+    *bytes = up16(dp_nbest_workspace_words(k, T, n_paths) * sizeof(int32_t));
     return CPPF_OK;
 }
 
@@ -1873,8 +1854,7 @@ int cppf_dp_nbest(const cppf_robot* robot, const float* q, const float* costsT, 
                   float min_separation, float prismatic_scaling, void* workspace, float* paths, int32_t* path_idx, float* path_cost,
                   int32_t* n_found, void* stream) {
     // every argument is checked before the device is selected (CPPF_ENTER), so that the checks hold for a host-only handle too
-    CPPF_REQUIRE(robot != nullptr, "robot handle is NULL");
-    CPPF_REQUIRE(!(robot->life.load(std::memory_order_acquire) & kRobotDead), "the robot handle was destroyed");
+    CPPF_ROBOT_ALIVE(robot);
     CPPF_REQUIRE(k >= 1 && T >= 1 && n_paths >= 1, "k, T, n_paths must be >= 1");
     CPPF_REQUIRE(std::isfinite(min_separation) && min_separation >= 0.f, "min_separation must be finite and >= 0");
     CPPF_REQUIRE(q && costsT && memoT && workspace && paths && path_idx && path_cost && n_found, "NULL pointer");
@@ -1890,10 +1870,9 @@ int cppf_dp_nbest(const cppf_robot* robot, const float* q, const float* costsT, 
     int32_t* const far = alive + k;
     int32_t* const sel = far + k;
     const size_t stage = dp_stage_bytes(k, T);
-    if (stage)
-        hipLaunchKernelGGL(dp_trace_all_kernel, dim3(1), dim3(1024), stage, st, memoT, k, T, 1, idxT);
-    else
-        hipLaunchKernelGGL(dp_trace_all_kernel, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, st, memoT, k, T, 0, idxT);
+    // (the memo table staged in LDS by one workgroup of 1024 lanes where it fits, else walked in global memory, one lane per candidate)
+    hipLaunchKernelGGL(dp_trace_all_kernel, dim3(stage ? 1u : (unsigned)((k + 255) / 256)), dim3(stage ? 1024 : 256), stage, st, memoT, k, T,
+                       stage ? 1 : 0, idxT);
     const int rc = for_ndof(d, [&](auto dof) {
         hipLaunchKernelGGL((dp_nbest_select_kernel<decltype(dof)::D>), dim3(1), dim3(1024), 0, st, q, costsT, memoT, k, T, n_paths,
                            min_separation, robot->chain.pris_mask, prismatic_scaling, idxT, order, alive, far, sel, n_found);
@@ -1912,7 +1891,7 @@ int cppf_scene_workspace_bytes(int n_rows, int n_obs, size_t* bytes) {
     CPPF_REQUIRE(n_rows >= 0, "n_rows < 0");
     CPPF_REQUIRE(n_obs >= 0 && n_obs <= CPPF_MAX_SCENE_OBSTACLES, "n_obs out of range (0 .. CPPF_MAX_SCENE_OBSTACLES)");
     // one 64-bit key per row, one 32-bit key per cuboid (kernels_scene.h); never 0, so that "workspace is NULL" stays a refusal
-    *bytes = ((size_t)n_rows * sizeof(unsigned long long) + (size_t)n_obs * sizeof(uint32_t) + 15) / 16 * 16 + 16;
+    *bytes = up16((size_t)n_rows * sizeof(unsigned long long) + (size_t)n_obs * sizeof(uint32_t)) + 16;
     return CPPF_OK;
 }
 
@@ -1953,10 +1932,8 @@ int cppf_scene_env_collisions(const cppf_robot* robot, const float* q, int S, in
     if (n > 0 && n_obs > 0) {
         const int rc = for_robot(robot, [&](auto tag) {
             using RB = typename decltype(tag)::type;
-            const auto launch = [&](auto kernel) {
-                return launch_lds(kernel, dim3(row_blocks, (unsigned)cut.n_chunks), lds, st, robot->chain, robot->coll, sc, q);
-            };
-            return want_min ? launch(&scene_kernel<RB, true>) : launch(&scene_kernel<RB, false>);
+            return launch(want_min ? scene_kernel<RB, true> : scene_kernel<RB, false>, dim3(row_blocks, (unsigned)cut.n_chunks), dim3(kBlock), lds,
+                          st, robot->chain, robot->coll, sc, q);
         });
         if (rc) return rc;
         if (int rc2 = check_launch()) return rc2;
@@ -1974,8 +1951,6 @@ struct VoxelLayout {
     int wpr, rows;
     size_t bits, row, segs, total;  // bytes: the bitset, ONE per-row array, the segments, everything (+ 16: never 0)
 };
-inline size_t up16(size_t b) { return (b + 15) / 16 * 16; }
-
 // the grid's rules (cppflow_hip.h, "Grid" and "Planes"); fills *lay where given
 int voxel_check_grid(const cppf_voxel_grid* grid, int n_self, VoxelLayout* lay) {
     CPPF_REQUIRE(grid, "grid is NULL");
@@ -2022,7 +1997,7 @@ int voxel_scene_run(const cppf_robot* robot, const VoxelSource& src, const cppf_
     if (int rc = voxel_check_grid(grid, n_self, &lay)) return rc;
     if (n_self > 0) {
         CPPF_REQUIRE(robot != nullptr, "robot handle is NULL (only n_self = 0 needs none)");
-        CPPF_REQUIRE(!(robot->life.load(std::memory_order_acquire) & kRobotDead), "the robot handle was destroyed");
+        CPPF_ROBOT_ALIVE(robot);
         CPPF_REQUIRE(q_self, "q_self is NULL");
     }
     CPPF_REQUIRE(self_margin_m >= 0.f && std::isfinite(self_margin_m), "self_margin_m must be finite and >= 0 (not NaN)");
@@ -2084,10 +2059,9 @@ int voxel_scene_run(const cppf_robot* robot, const VoxelSource& src, const cppf_
     }
     if (src.n > 0) {
         const dim3 pgrid((unsigned)((src.n + 255) / 256));
-        if (src.points)
-            hipLaunchKernelGGL(voxel_points_kernel<false>, pgrid, dim3(256), 0, st, g, src.points, src.cam, src.n);
-        else
-            hipLaunchKernelGGL(voxel_points_kernel<true>, pgrid, dim3(256), 0, st, g, (const float*)nullptr, src.cam, src.n);
+        // (the depth form reads src.cam and is handed src.points = NULL)
+        const auto points_kernel = src.points ? voxel_points_kernel<false> : voxel_points_kernel<true>;
+        hipLaunchKernelGGL(points_kernel, pgrid, dim3(256), 0, st, g, src.points, src.cam, src.n);
     }
     const dim3 rgrid((unsigned)((lay.rows + 255) / 256));
     hipLaunchKernelGGL(voxel_rows_kernel, rgrid, dim3(256), 0, st, g);
@@ -2146,8 +2120,7 @@ int cppf_scene_from_depth(const cppf_robot* robot, const float* depth, int heigh
 
 // ---- motion between the waypoints (kernels_motion.h) ------------------------------------------------------------------------------
 int cppf_motion_rho(const cppf_robot* robot, float* rho) {
-    CPPF_REQUIRE(robot != nullptr, "robot handle is NULL");
-    CPPF_REQUIRE(!(robot->life.load(std::memory_order_acquire) & kRobotDead), "the robot handle was destroyed");
+    CPPF_ROBOT_ALIVE(robot);
     CPPF_REQUIRE(rho, "rho is NULL");
     std::memcpy(rho, robot->rho, sizeof(robot->rho));
     return CPPF_OK;
@@ -2158,7 +2131,7 @@ int cppf_motion_workspace_bytes(int S, int W, size_t* bytes) {
     CPPF_REQUIRE(S >= 0, "S < 0");
     CPPF_REQUIRE(W >= 2, "W < 2: a motion needs two waypoints");
     // three 32-bit words per transition (kernels_motion.h); never 0, so that "workspace is NULL" stays a refusal
-    *bytes = ((size_t)S * (size_t)(W - 1) * 3 * sizeof(uint32_t) + 15) / 16 * 16 + 16;
+    *bytes = up16((size_t)S * (size_t)(W - 1) * 3 * sizeof(uint32_t)) + 16;
     return CPPF_OK;
 }
 
@@ -2205,7 +2178,7 @@ int cppf_motion_clearance(const cppf_robot* robot, const float* q, int S, int W,
     hipLaunchKernelGGL(motion_init_kernel, dim3(tr_blocks), dim3(256), 0, st, mk.fail, mk.clear_key, mk.hit, n_tr);
     const int rc = for_robot(robot, [&](auto tag) {
         using RB = typename decltype(tag)::type;
-        return launch_lds(&motion_kernel<RB>, dim3(wave_blocks, (unsigned)cut.n_chunks), lds, st, robot->chain, robot->coll, mk, q);
+        return launch(motion_kernel<RB>, dim3(wave_blocks, (unsigned)cut.n_chunks), dim3(kBlock), lds, st, robot->chain, robot->coll, mk, q);
     });
     if (rc) return rc;
     if (int rc2 = check_launch()) return rc2;
@@ -2222,7 +2195,7 @@ int cppf_motion_resolve_workspace_bytes(int S, int W, int max_frontier, size_t* 
     CPPF_REQUIRE(max_frontier >= 1 && max_frontier <= CPPF_MOTION_RESOLVE_MAX_FRONTIER,
                  "max_frontier out of range (1 .. CPPF_MOTION_RESOLVE_MAX_FRONTIER)");
     // two lists of max_frontier 32-bit interval indices per transition; never 0, so that "workspace is NULL" stays a refusal
-    *bytes = ((size_t)S * (size_t)(W - 1) * 2 * (size_t)max_frontier * sizeof(uint32_t) + 15) / 16 * 16 + 16;
+    *bytes = up16((size_t)S * (size_t)(W - 1) * 2 * (size_t)max_frontier * sizeof(uint32_t)) + 16;
     return CPPF_OK;
 }
 
@@ -2267,7 +2240,7 @@ int cppf_motion_resolve(const cppf_robot* robot, const float* q, int S, int W, i
     const unsigned blocks = (unsigned)((n_tr + kBlock / 64 - 1) / (kBlock / 64));  // one wavefront per transition
     const int rc = for_robot(robot, [&](auto tag) {
         using RB = typename decltype(tag)::type;
-        return launch_lds(&motion_resolve_kernel<RB>, dim3(blocks), lds, st, robot->chain, robot->coll, rk, q);
+        return launch(motion_resolve_kernel<RB>, dim3(blocks), dim3(kBlock), lds, st, robot->chain, robot->coll, rk, q);
     });
     if (rc) return rc;
     return check_launch();

@@ -41,12 +41,9 @@ constexpr int kBlock = CPPF_BLOCK;
 template <class Type>
 void launch_one(int coll, unsigned grid, size_t lds, hipStream_t st, const FusedArgs& args) {
     using RB = StaRobot<Type>;
-    if (coll == 2)
-        hipLaunchKernelGGL((lm_fused_kernel<RB, 2>), dim3(grid), dim3(kBlock), lds, st, args.ch, args.co, args.prm, args.single, args.table);
-    else if (coll == 1)
-        hipLaunchKernelGGL((lm_fused_kernel<RB, 1>), dim3(grid), dim3(kBlock), lds, st, args.ch, args.co, args.prm, args.single, args.table);
-    else
-        hipLaunchKernelGGL((lm_fused_kernel<RB, 0>), dim3(grid), dim3(kBlock), lds, st, args.ch, args.co, args.prm, args.single, args.table);
+    const auto kernel = coll == 2 ? lm_fused_kernel<RB, 2> : coll == 1 ? lm_fused_kernel<RB, 1> : lm_fused_kernel<RB, 0>;
+    // (lds is the residency claim alone, below the 64 KB a kernel may have without asking: the table forms stage nothing)
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, st, args.ch, args.co, args.prm, args.single, args.table);
 }
 
 }  // namespace

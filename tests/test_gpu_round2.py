@@ -376,6 +376,30 @@ def test_arbitrary_chains_specialised_equal_generic_bit_for_bit(ndof, seed, tmp_
     assert outs["fast"][0]["self_mask"].any() or outs["fast"][0]["env_mask"].any() or True
 
 
+def test_quad_shape_without_collision_stage_specialised_equals_generic_bit_for_bit():
+    """The one kernel of a run-time-specialised module the test above does not launch: the quad shape WITHOUT its collision stage.
+    65 rows (one full wavefront of rows plus one lane of the next), on a description other tests specialise too, so the cached
+    module serves it: x and the pose errors equal the generic kernel's bit for bit."""
+    from cppflow_amd import _hip
+    from cppflow_amd.robot_model import canonicalize
+    from cppflow_amd.robots import Robot
+
+    spec = H.random_chain_spec(7, seed=21)
+    ch = canonicalize(spec)
+    fast, slow = Robot(spec, specialize=True), Robot(spec, specialize=False)
+    assert fast.specialization("cuda:0") == 1000 and slow.specialization("cuda:0") == -1
+    rng = np.random.RandomState(21)
+    S, W, K = 13, 5, 4
+    q_star = H.f32(rng.uniform(ch.lo, ch.hi, size=(W, 7)))
+    target = H.f32(H.f32(Oracle_fk(ch, q_star)))
+    x0 = H.f32(np.clip(q_star[None] + 0.1 * rng.randn(S, W, 7), ch.lo, ch.hi).reshape(S * W, 7))
+    a, b = (rb.lm_pose_steps(dev(x0), dev(target), n_steps=K, want_errors=True, shape=_hip.SHAPE_QUAD, **LM) for rb in (fast, slow))
+    assert a.keys() == b.keys() and {"x", "pos_err_m", "rot_err_rad"} <= a.keys()
+    for k in a:
+        assert torch.equal(a[k], b[k]), k
+    assert not torch.equal(a["x"], dev(x0))  # (the launch did step)
+
+
 def Oracle_fk(ch, q):
     from oracle.oracle import Oracle
 
