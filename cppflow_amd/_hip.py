@@ -194,6 +194,7 @@ MOTION_RESOLVE_MAX_FRONTIER = 4096  # CPPF_MOTION_RESOLVE_MAX_FRONTIER
 VOXEL_MAX_DIM = 1024  # CPPF_VOXEL_MAX_DIM
 VOXEL_MAX_CELLS = 1 << 24  # CPPF_VOXEL_MAX_CELLS
 VOXEL_MAX_SELF = 16  # CPPF_VOXEL_MAX_SELF
+VOXEL_MERGE_XY, VOXEL_MERGE_XYZ = 0, 1  # CPPF_VOXEL_MERGE_*
 
 
 class VoxelGrid(ctypes.Structure):
@@ -251,6 +252,23 @@ SIGNATURES = {
         ctypes.c_int,
         [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_f), ctypes.POINTER(_f), ctypes.c_float, ctypes.c_float,
          ctypes.POINTER(VoxelGrid), _vp, ctypes.c_int, ctypes.c_float, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp],
+    ),
+    "cppf_voxel_map_bytes": (ctypes.c_int, [ctypes.POINTER(VoxelGrid), ctypes.POINTER(ctypes.c_size_t)]),
+    "cppf_voxel_map_clear": (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.POINTER(VoxelGrid), _vp]),
+    "cppf_voxel_map_add_points": (
+        ctypes.c_int,
+        [_vp, _vp, ctypes.c_int, ctypes.POINTER(VoxelGrid), _vp, ctypes.c_int, ctypes.c_float, _vp, ctypes.c_size_t, _vp, _vp,
+         ctypes.c_size_t, _vp],
+    ),
+    "cppf_voxel_map_add_depth": (
+        ctypes.c_int,
+        [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_f), ctypes.POINTER(_f), ctypes.c_float, ctypes.c_float,
+         ctypes.POINTER(VoxelGrid), _vp, ctypes.c_int, ctypes.c_float, _vp, ctypes.c_size_t, _vp, _vp, ctypes.c_size_t, _vp],
+    ),
+    "cppf_scene_from_map": (
+        ctypes.c_int,
+        [_vp, ctypes.c_size_t, ctypes.POINTER(VoxelGrid), ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_size_t,
+         _vp],
     ),
     "cppf_motion_workspace_bytes": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
     "cppf_motion_clearance": (

@@ -1989,37 +1989,83 @@ struct VoxelSource {
     size_t n;
 };
 
-// everything behind the source's own checks: the shared refusals, then the launches
-int voxel_scene_run(const cppf_robot* robot, const VoxelSource& src, const cppf_voxel_grid* grid, const float* q_self, int n_self,
-                    float self_margin_m, int capacity, float* box_lo, float* box_hi, int32_t* counts, void* workspace,
-                    size_t workspace_bytes, void* stream) {
-    VoxelLayout lay;
-    if (int rc = voxel_check_grid(grid, n_self, &lay)) return rc;
+// the source's own checks: the point form ...
+int voxel_points_source(const float* points, int n_points, VoxelSource* src) {
+    CPPF_REQUIRE(n_points >= 0, "n_points < 0");
+    CPPF_REQUIRE(n_points == 0 || points, "points is NULL");
+    src->points = points;
+    src->n = (size_t)n_points;
+    return CPPF_OK;
+}
+// ... and the depth form
+int voxel_depth_source(const float* depth, int height, int width, const float intrinsics[4], const float cam_to_world[12], float z_min,
+                       float z_max, VoxelSource* src) {
+    CPPF_REQUIRE(height >= 0 && width >= 0, "height / width < 0");
+    const size_t n = (size_t)height * (size_t)width;
+    CPPF_REQUIRE(n < ((size_t)1 << 31), "height*width exceeds 2^31-1 pixels");
+    CPPF_REQUIRE(n == 0 || depth, "depth is NULL");
+    CPPF_REQUIRE(intrinsics && cam_to_world, "intrinsics / cam_to_world is NULL");
+    CPPF_REQUIRE(z_min < z_max, "z_min must be below z_max (neither NaN)");
+    src->cam.depth = depth;
+    src->cam.width = width;
+    src->cam.ifx = 1.0f / intrinsics[0], src->cam.ify = 1.0f / intrinsics[1];
+    CPPF_REQUIRE(std::isfinite(intrinsics[0]) && std::isfinite(intrinsics[1]) && intrinsics[0] != 0.f && intrinsics[1] != 0.f &&
+                     std::isfinite(src->cam.ifx) && std::isfinite(src->cam.ify),
+                 "fx / fy must be finite and non-zero (and 1 / fx, 1 / fy finite)");
+    src->cam.cx = intrinsics[2], src->cam.cy = intrinsics[3];
+    for (int k = 0; k < 9; ++k) src->cam.R[k] = cam_to_world[k];
+    for (int k = 0; k < 3; ++k) src->cam.t[k] = cam_to_world[9 + k];
+    src->cam.z_min = z_min, src->cam.z_max = z_max;
+    src->n = n;
+    // (the point kernel tells the forms apart by its template argument; src->points stays NULL)
+    return CPPF_OK;
+}
+
+// the refusals of everything that takes a frame in: the grid (fills *lay), the handle and q_self, the margin
+int voxel_check_frame(const cppf_robot* robot, const cppf_voxel_grid* grid, const float* q_self, int n_self, float self_margin_m,
+                      VoxelLayout* lay) {
+    if (int rc = voxel_check_grid(grid, n_self, lay)) return rc;
     if (n_self > 0) {
         CPPF_REQUIRE(robot != nullptr, "robot handle is NULL (only n_self = 0 needs none)");
         CPPF_ROBOT_ALIVE(robot);
         CPPF_REQUIRE(q_self, "q_self is NULL");
     }
     CPPF_REQUIRE(self_margin_m >= 0.f && std::isfinite(self_margin_m), "self_margin_m must be finite and >= 0 (not NaN)");
+    return CPPF_OK;
+}
+int voxel_check_boxes(int capacity, const float* box_lo, const float* box_hi) {
     CPPF_REQUIRE(capacity >= 0 && capacity <= CPPF_MAX_SCENE_OBSTACLES, "capacity out of range (0 .. CPPF_MAX_SCENE_OBSTACLES)");
     CPPF_REQUIRE(capacity == 0 || (box_lo && box_hi), "box_lo / box_hi is NULL");
+    return CPPF_OK;
+}
+int voxel_check_scratch(const int32_t* counts, const void* workspace, size_t workspace_bytes, const VoxelLayout& lay) {
     CPPF_REQUIRE(counts, "counts is NULL");
     CPPF_REQUIRE(workspace, "workspace is NULL");
     CPPF_REQUIRE(((uintptr_t)workspace & 15u) == 0, "workspace must be 16-byte aligned");
     CPPF_REQUIRE(workspace_bytes >= lay.total, "workspace is smaller than cppf_voxel_scene_workspace_bytes(grid, n_self)");
-    if (n_self > 0 && robot->desc.ndof < 3) return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: kernels are built for ndof in 3..12");
+    return CPPF_OK;
+}
+// the map of a grid: 16 bytes of header, then one uint8 per cell of the padded grid
+size_t voxel_map_size(const VoxelLayout& lay) { return 16 + (size_t)lay.rows * lay.wpr * 64; }
+int voxel_check_map(const void* map, size_t map_bytes, const VoxelLayout& lay) {
+    CPPF_REQUIRE(map, "map is NULL");
+    CPPF_REQUIRE(((uintptr_t)map & 15u) == 0, "map must be 16-byte aligned");
+    CPPF_REQUIRE(map_bytes == voxel_map_size(lay), "map_bytes is not cppf_voxel_map_bytes(grid)");
+    return CPPF_OK;
+}
 
-    // (without a handle the launches go to the calling thread's current device, where the caller's pointers live)
-    int device = -1;
+// (without a handle the launches go to the calling thread's current device, where the caller's pointers live)
+int voxel_device(const cppf_robot* robot, int n_self, int* device) {
     if (n_self > 0)
-        device = robot->device;
+        *device = robot->device;
     else
-        CPPF_HIP(hipGetDevice(&device));
-    DeviceGuard guard(device);
-    if (guard.err != hipSuccess)
-        return fail(CPPF_ERR_HIP, std::string("cppflow_hip: selecting the robot's device failed: ") + hipGetErrorString(guard.err));
-    hipStream_t st = (hipStream_t)stream;
+        CPPF_HIP(hipGetDevice(device));
+    return CPPF_OK;
+}
 
+// the kernels' view of a grid and its workspace; *segs: where the self filter's segments go
+VoxelK voxel_args(const cppf_robot* robot, const cppf_voxel_grid* grid, const VoxelLayout& lay, int n_self, int capacity, float* box_lo,
+                  float* box_hi, int32_t* counts, void* workspace, float** segs) {
     char* const base = static_cast<char*>(workspace);
     VoxelK g;
     for (int k = 0; k < 3; ++k) g.origin[k] = grid->origin[k];
@@ -2031,20 +2077,25 @@ int voxel_scene_run(const cppf_robot* robot, const VoxelSource& src, const cppf_
     g.row_heads = reinterpret_cast<int32_t*>(base + lay.bits);
     g.row_cells = reinterpret_cast<int32_t*>(base + lay.bits + lay.row);
     g.row_offset = reinterpret_cast<int32_t*>(base + lay.bits + 2 * lay.row);
-    float* const segs = reinterpret_cast<float*>(base + lay.bits + 3 * lay.row);
-    g.segs = segs;
+    *segs = reinterpret_cast<float*>(base + lay.bits + 3 * lay.row);
+    g.segs = *segs;
     g.n_self = n_self;
     g.ncaps = n_self > 0 ? robot->coll.ncaps : 0;
     g.capacity = capacity;
     g.counts = counts;
     g.box_lo = box_lo, g.box_hi = box_hi;
+    return g;
+}
 
+// a frame's occupancy into the workspace bitset: clear, the self filter's segments, the points
+int voxel_launch_frame(const cppf_robot* robot, const VoxelSource& src, const VoxelK& g, const VoxelLayout& lay, const float* q_self,
+                       float self_margin_m, float* segs, hipStream_t st) {
     const size_t n16 = (lay.bits + 3 * lay.row) / 16;
     hipLaunchKernelGGL(voxel_clear_kernel, dim3((unsigned)((std::max<size_t>(n16, 8) + 255) / 256)), dim3(256), 0, st,
-                       reinterpret_cast<uint4*>(base), n16, counts);
-    if (n_self > 0 && g.ncaps > 0) {
+                       reinterpret_cast<uint4*>(g.bits), n16, g.counts);
+    if (g.n_self > 0 && g.ncaps > 0) {
         VoxelSelfK sk;
-        sk.q = q_self, sk.segs = segs, sk.n_self = n_self;
+        sk.q = q_self, sk.segs = segs, sk.n_self = g.n_self;
         for (int c = 0; c < CPPF_MAX_CAPSULES; ++c) {
             const double s = c < g.ncaps ? (double)robot->desc.cap_r[c] + (double)self_margin_m : 0.0;
             sk.thr2[c] = (float)(s * s);
@@ -2063,10 +2114,65 @@ int voxel_scene_run(const cppf_robot* robot, const VoxelSource& src, const cppf_
         const auto points_kernel = src.points ? voxel_points_kernel<false> : voxel_points_kernel<true>;
         hipLaunchKernelGGL(points_kernel, pgrid, dim3(256), 0, st, g, src.points, src.cam, src.n);
     }
-    const dim3 rgrid((unsigned)((lay.rows + 255) / 256));
-    hipLaunchKernelGGL(voxel_rows_kernel, rgrid, dim3(256), 0, st, g);
+    return CPPF_OK;
+}
+
+// the bitset's box list: rows -> scan -> emit, merged along x and y or along z as well
+void voxel_launch_boxes(const VoxelK& g, int merge, hipStream_t st) {
+    const dim3 rgrid((unsigned)((g.rows + 255) / 256));
+    hipLaunchKernelGGL(merge == CPPF_VOXEL_MERGE_XYZ ? voxel_rows_z_kernel : voxel_rows_kernel, rgrid, dim3(256), 0, st, g);
     hipLaunchKernelGGL(voxel_scan_kernel, dim3(1), dim3(1024), 0, st, g);
-    hipLaunchKernelGGL(voxel_emit_kernel, rgrid, dim3(256), 0, st, g);
+    hipLaunchKernelGGL(merge == CPPF_VOXEL_MERGE_XYZ ? voxel_emit_z_kernel : voxel_emit_kernel, rgrid, dim3(256), 0, st, g);
+}
+
+// everything behind the source's own checks: the shared refusals, then the launches
+int voxel_scene_run(const cppf_robot* robot, const VoxelSource& src, const cppf_voxel_grid* grid, const float* q_self, int n_self,
+                    float self_margin_m, int capacity, float* box_lo, float* box_hi, int32_t* counts, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+    VoxelLayout lay;
+    if (int rc = voxel_check_frame(robot, grid, q_self, n_self, self_margin_m, &lay)) return rc;
+    if (int rc = voxel_check_boxes(capacity, box_lo, box_hi)) return rc;
+    if (int rc = voxel_check_scratch(counts, workspace, workspace_bytes, lay)) return rc;
+    if (n_self > 0 && robot->desc.ndof < 3) return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: kernels are built for ndof in 3..12");
+
+    int device = -1;
+    if (int rc = voxel_device(robot, n_self, &device)) return rc;
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess)
+        return fail(CPPF_ERR_HIP, std::string("cppflow_hip: selecting the robot's device failed: ") + hipGetErrorString(guard.err));
+    hipStream_t st = (hipStream_t)stream;
+    float* segs = nullptr;
+    const VoxelK g = voxel_args(robot, grid, lay, n_self, capacity, box_lo, box_hi, counts, workspace, &segs);
+    if (int rc = voxel_launch_frame(robot, src, g, lay, q_self, self_margin_m, segs, st)) return rc;
+    voxel_launch_boxes(g, CPPF_VOXEL_MERGE_XY, st);
+    return check_launch();
+}
+
+// a frame into the map: the frame's bitset as voxel_scene_run builds it, then the integration
+int voxel_map_add(const cppf_robot* robot, const VoxelSource& src, const cppf_voxel_grid* grid, const float* q_self, int n_self,
+                  float self_margin_m, void* map, size_t map_bytes, int32_t* counts, void* workspace, size_t workspace_bytes,
+                  void* stream) {
+    VoxelLayout lay;
+    if (int rc = voxel_check_frame(robot, grid, q_self, n_self, self_margin_m, &lay)) return rc;
+    if (int rc = voxel_check_map(map, map_bytes, lay)) return rc;
+    if (int rc = voxel_check_scratch(counts, workspace, workspace_bytes, lay)) return rc;
+    if (n_self > 0 && robot->desc.ndof < 3) return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: kernels are built for ndof in 3..12");
+
+    int device = -1;
+    if (int rc = voxel_device(robot, n_self, &device)) return rc;
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess)
+        return fail(CPPF_ERR_HIP, std::string("cppflow_hip: selecting the robot's device failed: ") + hipGetErrorString(guard.err));
+    hipStream_t st = (hipStream_t)stream;
+    float* segs = nullptr;
+    const VoxelK g = voxel_args(robot, grid, lay, n_self, 0, nullptr, nullptr, counts, workspace, &segs);
+    if (int rc = voxel_launch_frame(robot, src, g, lay, q_self, self_margin_m, segs, st)) return rc;
+    VoxelMapK m;
+    m.header = static_cast<int32_t*>(map);
+    m.counters = reinterpret_cast<unsigned long long*>(static_cast<char*>(map) + 16);
+    m.n_bytes = (size_t)lay.rows * lay.wpr * 8;
+    hipLaunchKernelGGL(voxel_integrate_kernel, dim3((unsigned)((m.n_bytes + 255) / 256)), dim3(256), 0, st,
+                       reinterpret_cast<const unsigned char*>(g.bits), m, counts);
     return check_launch();
 }
 }  // namespace
@@ -2082,11 +2188,8 @@ int cppf_voxel_scene_workspace_bytes(const cppf_voxel_grid* grid, int n_self, si
 int cppf_scene_from_points(const cppf_robot* robot, const float* points, int n_points, const cppf_voxel_grid* grid, const float* q_self,
                            int n_self, float self_margin_m, int capacity, float* box_lo, float* box_hi, int32_t* counts,
                            void* workspace, size_t workspace_bytes, void* stream) {
-    CPPF_REQUIRE(n_points >= 0, "n_points < 0");
-    CPPF_REQUIRE(n_points == 0 || points, "points is NULL");
     VoxelSource src{};
-    src.points = points;
-    src.n = (size_t)n_points;
+    if (int rc = voxel_points_source(points, n_points, &src)) return rc;
     return voxel_scene_run(robot, src, grid, q_self, n_self, self_margin_m, capacity, box_lo, box_hi, counts, workspace, workspace_bytes,
                            stream);
 }
@@ -2095,27 +2198,71 @@ int cppf_scene_from_depth(const cppf_robot* robot, const float* depth, int heigh
                           const float cam_to_world[12], float z_min, float z_max, const cppf_voxel_grid* grid, const float* q_self,
                           int n_self, float self_margin_m, int capacity, float* box_lo, float* box_hi, int32_t* counts,
                           void* workspace, size_t workspace_bytes, void* stream) {
-    CPPF_REQUIRE(height >= 0 && width >= 0, "height / width < 0");
-    const size_t n = (size_t)height * (size_t)width;
-    CPPF_REQUIRE(n < ((size_t)1 << 31), "height*width exceeds 2^31-1 pixels");
-    CPPF_REQUIRE(n == 0 || depth, "depth is NULL");
-    CPPF_REQUIRE(intrinsics && cam_to_world, "intrinsics / cam_to_world is NULL");
-    CPPF_REQUIRE(z_min < z_max, "z_min must be below z_max (neither NaN)");
     VoxelSource src{};
-    src.cam.depth = depth;
-    src.cam.width = width;
-    src.cam.ifx = 1.0f / intrinsics[0], src.cam.ify = 1.0f / intrinsics[1];
-    CPPF_REQUIRE(std::isfinite(intrinsics[0]) && std::isfinite(intrinsics[1]) && intrinsics[0] != 0.f && intrinsics[1] != 0.f &&
-                     std::isfinite(src.cam.ifx) && std::isfinite(src.cam.ify),
-                 "fx / fy must be finite and non-zero (and 1 / fx, 1 / fy finite)");
-    src.cam.cx = intrinsics[2], src.cam.cy = intrinsics[3];
-    for (int k = 0; k < 9; ++k) src.cam.R[k] = cam_to_world[k];
-    for (int k = 0; k < 3; ++k) src.cam.t[k] = cam_to_world[9 + k];
-    src.cam.z_min = z_min, src.cam.z_max = z_max;
-    src.n = n;
-    // (the point kernel tells the forms apart by its template argument; src.points stays NULL)
+    if (int rc = voxel_depth_source(depth, height, width, intrinsics, cam_to_world, z_min, z_max, &src)) return rc;
     return voxel_scene_run(robot, src, grid, q_self, n_self, self_margin_m, capacity, box_lo, box_hi, counts, workspace, workspace_bytes,
                            stream);
+}
+
+// ---- scenes fused over frames (kernels_voxel.h) -----------------------------------------------------------------------------------------
+int cppf_voxel_map_bytes(const cppf_voxel_grid* grid, size_t* bytes) {
+    CPPF_REQUIRE(bytes, "bytes is NULL");
+    VoxelLayout lay;
+    if (int rc = voxel_check_grid(grid, 0, &lay)) return rc;
+    *bytes = voxel_map_size(lay);
+    return CPPF_OK;
+}
+
+int cppf_voxel_map_clear(void* map, size_t map_bytes, const cppf_voxel_grid* grid, void* stream) {
+    VoxelLayout lay;
+    if (int rc = voxel_check_grid(grid, 0, &lay)) return rc;
+    if (int rc = voxel_check_map(map, map_bytes, lay)) return rc;
+    const size_t n16 = map_bytes / 16;
+    hipLaunchKernelGGL(voxel_map_clear_kernel, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       static_cast<uint4*>(map), n16);
+    return check_launch();
+}
+
+int cppf_voxel_map_add_points(const cppf_robot* robot, const float* points, int n_points, const cppf_voxel_grid* grid,
+                              const float* q_self, int n_self, float self_margin_m, void* map, size_t map_bytes, int32_t* counts,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+    VoxelSource src{};
+    if (int rc = voxel_points_source(points, n_points, &src)) return rc;
+    return voxel_map_add(robot, src, grid, q_self, n_self, self_margin_m, map, map_bytes, counts, workspace, workspace_bytes, stream);
+}
+
+int cppf_voxel_map_add_depth(const cppf_robot* robot, const float* depth, int height, int width, const float intrinsics[4],
+                             const float cam_to_world[12], float z_min, float z_max, const cppf_voxel_grid* grid, const float* q_self,
+                             int n_self, float self_margin_m, void* map, size_t map_bytes, int32_t* counts, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+    VoxelSource src{};
+    if (int rc = voxel_depth_source(depth, height, width, intrinsics, cam_to_world, z_min, z_max, &src)) return rc;
+    return voxel_map_add(robot, src, grid, q_self, n_self, self_margin_m, map, map_bytes, counts, workspace, workspace_bytes, stream);
+}
+
+int cppf_scene_from_map(const void* map, size_t map_bytes, const cppf_voxel_grid* grid, int min_frames, int merge, int capacity,
+                        float* box_lo, float* box_hi, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
+    VoxelLayout lay;
+    if (int rc = voxel_check_grid(grid, 0, &lay)) return rc;
+    if (int rc = voxel_check_map(map, map_bytes, lay)) return rc;
+    CPPF_REQUIRE(min_frames >= 1 && min_frames <= 255, "min_frames out of range (1 .. 255)");
+    CPPF_REQUIRE(merge == CPPF_VOXEL_MERGE_XY || merge == CPPF_VOXEL_MERGE_XYZ, "merge is neither CPPF_VOXEL_MERGE_XY nor CPPF_VOXEL_MERGE_XYZ");
+    if (int rc = voxel_check_boxes(capacity, box_lo, box_hi)) return rc;
+    if (int rc = voxel_check_scratch(counts, workspace, workspace_bytes, lay)) return rc;
+
+    // (no handle: the launches go to the calling thread's current device, where the caller's pointers live)
+    hipStream_t st = (hipStream_t)stream;
+    float* segs = nullptr;
+    const VoxelK g = voxel_args(nullptr, grid, lay, 0, capacity, box_lo, box_hi, counts, workspace, &segs);
+    // the threshold pass stores every word of the bitset: what is left to clear are the per-row arrays and counts
+    const size_t n16 = 3 * lay.row / 16;
+    hipLaunchKernelGGL(voxel_clear_kernel, dim3((unsigned)((std::max<size_t>(n16, 8) + 255) / 256)), dim3(256), 0, st,
+                       reinterpret_cast<uint4*>(g.row_heads), n16, counts);
+    const size_t n_words = (size_t)lay.rows * lay.wpr;
+    hipLaunchKernelGGL(voxel_threshold_kernel, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, st, g,
+                       reinterpret_cast<const uint4*>(static_cast<const char*>(map) + 16), static_cast<const int32_t*>(map), min_frames);
+    voxel_launch_boxes(g, merge, st);
+    return check_launch();
 }
 
 // ---- motion between the waypoints (kernels_motion.h) ------------------------------------------------------------------------------

@@ -18,6 +18,21 @@
 //
 // Bitset: row (y, z) is wpr = ceil(nx / 64) 64-bit words at (z ny + y) wpr; bit x & 63 of word x >> 6 is cell x.  Bits at x >= nx
 // are never set (a kept point has ix < nx), which is what lets a run that reaches the row's end stop at nx in every row alike.
+//
+// Scenes FUSED OVER FRAMES (cppf_voxel_map_*, cppf_scene_from_map; "Scenes fused over frames" in the header, tests/voxel_map.py): a
+// map of one uint8 hit counter per cell in the bitset's geometry (cell x of row r at byte r 64 wpr + x behind a 16-byte header), so
+// that byte b of the bitset and the 64-bit word b of the counters speak of the same eight cells.
+//   adding a frame      voxel_clear_kernel, voxel_self_kernel, voxel_points_kernel as above -- the frame's bitset -- and then
+//     voxel_integrate_kernel   one lane per bitset byte: its eight counters + 1 where the bit is set, saturating at 255; the cells of
+//                              the frame by a population count, summed per workgroup; lane 0 of the grid counts the frame
+//   map to scene        voxel_clear_kernel (the per-row arrays and counts), then
+//     voxel_threshold_kernel   one lane per bitset word: its 64 counters >= min_frames, stored whole; the cells seen at all likewise
+//   and either voxel_rows_kernel / voxel_scan_kernel / voxel_emit_kernel, or, merging along z as well,
+//     voxel_rows_z_kernel      one lane per row (y, z): its cells and its Z-HEADS (heads whose box layer z - 1 does not repeat)
+//     voxel_scan_kernel        as above
+//     voxel_emit_z_kernel      the same walk; a z-head follows its box up z + 1, ... and stores its cuboid at its offset
+// No lane shares a counter or a bitset word with another, so these passes need no atomic but the integer add of a workgroup's
+// population count (once per workgroup that counted anything): the map and the lists are again the same bytes in every run.
 #pragma once
 
 struct VoxelK {
@@ -301,5 +316,153 @@ __global__ __launch_bounds__(256) void voxel_emit_kernel(const VoxelK g) {
         hi[0] = voxel_plane(g.origin[0], g.voxel, x1);
         hi[1] = voxel_plane(g.origin[1], g.voxel, y1);
         hi[2] = hi_z;
+    });
+}
+
+// ---- scenes fused over frames ---------------------------------------------------------------------------------------------------------
+struct VoxelMapK {
+    int32_t* header;               // the map's first 16 bytes: { frames, 0, 0, 0 }
+    unsigned long long* counters;  // behind them: word b holds the uint8 counters of the eight cells of bitset byte b
+    size_t n_bytes;                // rows wpr 8: the bitset's bytes, the counters' words
+};
+
+__global__ __launch_bounds__(256) void voxel_map_clear_kernel(uint4* __restrict__ map16, size_t n16) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n16) map16[i] = make_uint4(0u, 0u, 0u, 0u);
+}
+
+// the sum of v over the workgroup (256 lanes, every one of them here) onto *dst: shuffles, the four wavefront sums through LDS, one
+// integer atomic add by lane 0 unless the sum is 0
+__device__ __forceinline__ void voxel_block_add(int v, int32_t* dst) {
+    __shared__ int wsum[4];
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int all = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+        if (all != 0) atomicAdd(dst, all);
+    }
+}
+
+constexpr unsigned long long kVoxelByteTop = 0x8080808080808080ull, kVoxelByteOne = 0x0101010101010101ull;
+
+// Byte k of the result is 1 where bit k of b is set, else 0: b in every byte, bit k kept in byte k, and + 0x7f carries any kept bit
+// into the byte's top (a byte holds at most 0x80 + 0x7f: nothing leaves it).
+__device__ __forceinline__ unsigned long long voxel_bits_to_bytes(unsigned b) {
+    const unsigned long long own = ((unsigned long long)b * kVoxelByteOne) & 0x8040201008040201ull;
+    return ((own + (kVoxelByteOne * 0x7full)) >> 7) & kVoxelByteOne;
+}
+
+// Bit k of the result: byte k of c >= m, unsigned, 1 <= m <= 255.  Per byte: (low seven bits | 0x80) - (m's low seven bits) lies
+// in 1 .. 255 -- no borrow leaves the byte -- and keeps its top bit iff the low seven bits are >= m's; the top bits of c and m
+// decide first.  The top bits are then gathered by one multiplication (its partial products fall on pairwise different bits).
+__device__ __forceinline__ unsigned voxel_bytes_ge(unsigned long long c, unsigned m) {
+    const unsigned long long low = ((c & ~kVoxelByteTop) | kVoxelByteTop) - (unsigned long long)(m & 127u) * kVoxelByteOne;
+    const unsigned long long ge = ((m & 128u) ? (c & low) : (c | low)) & kVoxelByteTop;
+    return (unsigned)(((ge >> 7) * 0x0102040810204080ull) >> 56);
+}
+
+// One lane per byte of the frame's bitset = per word of eight counters, which it alone reads and writes.  No lane leaves before the
+// barrier of voxel_block_add.
+__global__ __launch_bounds__(256) void voxel_integrate_kernel(const unsigned char* __restrict__ bits, const VoxelMapK m,
+                                                              int32_t* __restrict__ counts) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const unsigned b = i < m.n_bytes ? bits[i] : 0u;
+    if (b != 0u) {
+        const unsigned long long c = m.counters[i];
+        // a counter at 255 stays: its byte is the one whose low seven bits + 1 reach the top bit while its own top bit is set
+        const unsigned long long full = ((c & ~kVoxelByteTop) + kVoxelByteOne) & c & kVoxelByteTop;
+        m.counters[i] = c + (voxel_bits_to_bytes(b) & ~(full >> 7));  // (no byte that is added to holds 255: no carry)
+    }
+    voxel_block_add(__builtin_popcount(b), &counts[2]);
+    if (i == 0) {
+        const int32_t f = m.header[0], g = f < INT32_MAX ? f + 1 : f;
+        m.header[0] = g;
+        counts[7] = g;
+    }
+}
+
+// One lane per word of the bitset: its 64 counters are 64 consecutive bytes (four 16-byte loads).  Counters at x >= nx are 0 in a
+// map only this library wrote; the last word of a row is masked all the same, so that no caller's byte can set a bit there.
+__global__ __launch_bounds__(256) void voxel_threshold_kernel(const VoxelK g, const uint4* __restrict__ counters16,
+                                                              const int32_t* __restrict__ header, int min_frames) {
+    const size_t w = (size_t)blockIdx.x * 256 + threadIdx.x;
+    int seen_cells = 0;
+    if (w < (size_t)g.rows * g.wpr) {
+        unsigned long long occ = 0ull, seen = 0ull;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const uint4 v = counters16[w * 4 + k];
+            const unsigned long long c0 = (unsigned long long)v.x | ((unsigned long long)v.y << 32);
+            const unsigned long long c1 = (unsigned long long)v.z | ((unsigned long long)v.w << 32);
+            occ |= (unsigned long long)(voxel_bytes_ge(c0, (unsigned)min_frames) | (voxel_bytes_ge(c1, (unsigned)min_frames) << 8)) << (16 * k);
+            seen |= (unsigned long long)(voxel_bytes_ge(c0, 1u) | (voxel_bytes_ge(c1, 1u) << 8)) << (16 * k);
+        }
+        const int tail = g.nx & 63;
+        const unsigned long long valid = (tail != 0 && (int)(w % (size_t)g.wpr) == g.wpr - 1) ? (1ull << tail) - 1ull : ~0ull;
+        g.bits[w] = occ & valid;
+        seen_cells = __builtin_popcountll(seen & valid);
+    }
+    voxel_block_add(seen_cells, &g.counts[3]);
+    if (w == 0) g.counts[7] = header[0];
+}
+
+// Does layer z' hold the box (x0, x1, y, y1) -- is it a member of B(z')?  row: row (y, z').  Row y holds the identical maximal run, row
+// y - 1 does not (so the run is a head there), rows y + 1 .. y1 - 1 do, and row y1 does not (so the head's box ends where this one does).
+__device__ __forceinline__ bool voxel_layer_holds_box(const unsigned long long* __restrict__ row, int wpr, int ny, int x0, int x1, int y,
+                                                      int y1) {
+    if (!voxel_holds_run(row, wpr, x0, x1)) return false;
+    if (y > 0 && voxel_holds_run(row - wpr, wpr, x0, x1)) return false;
+    for (int yy = y + 1; yy < y1; ++yy)
+        if (!voxel_holds_run(row + (size_t)(yy - y) * wpr, wpr, x0, x1)) return false;
+    return y1 == ny || !voxel_holds_run(row + (size_t)(y1 - y) * wpr, wpr, x0, x1);
+}
+// f(k, x0, x1, y1) for the z-heads of row (y, z) in ascending x0, k = 0, 1, ...; cur: that row.  Returns their number.
+template <class F>
+__device__ __forceinline__ int voxel_row_zheads(const VoxelK& g, const unsigned long long* __restrict__ cur, int y, int z, F&& f) {
+    const size_t layer = (size_t)g.ny * g.wpr;
+    int zheads = 0;
+    voxel_row_heads(cur, y > 0 ? cur - g.wpr : nullptr, g.wpr, [&](int, int x0, int x1) {
+        int y1 = y + 1;
+        while (y1 < g.ny && voxel_holds_run(cur + (size_t)(y1 - y) * g.wpr, g.wpr, x0, x1)) ++y1;
+        if (z > 0 && voxel_layer_holds_box(cur - layer, g.wpr, g.ny, x0, x1, y, y1)) return;
+        f(zheads++, x0, x1, y1);
+    });
+    return zheads;
+}
+
+__global__ __launch_bounds__(256) void voxel_rows_z_kernel(const VoxelK g) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= g.rows) return;
+    const unsigned long long* cur = g.bits + (size_t)r * g.wpr;
+    int cells = 0;
+    for (int w = 0; w < g.wpr; ++w) cells += __builtin_popcountll(cur[w]);
+    g.row_cells[r] = cells;
+    g.row_heads[r] = cells == 0 ? 0 : voxel_row_zheads(g, cur, r % g.ny, r / g.ny, [](int, int, int, int) {});
+}
+
+__global__ __launch_bounds__(256) void voxel_emit_z_kernel(const VoxelK g) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= g.rows) return;
+    const int off = g.row_offset[r];
+    if (g.row_heads[r] == 0 || off >= g.capacity) return;
+    const int y = r % g.ny, z = r / g.ny;
+    const unsigned long long* cur = g.bits + (size_t)r * g.wpr;
+    const size_t layer = (size_t)g.ny * g.wpr;
+    const float lo_y = voxel_plane(g.origin[1], g.voxel, y), lo_z = voxel_plane(g.origin[2], g.voxel, z);
+    voxel_row_zheads(g, cur, y, z, [&](int k, int x0, int x1, int y1) {
+        const int o = off + k;
+        if (o >= g.capacity) return;
+        int z1 = z + 1;
+        while (z1 < g.nz && voxel_layer_holds_box(cur + (size_t)(z1 - z) * layer, g.wpr, g.ny, x0, x1, y, y1)) ++z1;
+        float* lo = g.box_lo + (size_t)o * 3;
+        float* hi = g.box_hi + (size_t)o * 3;
+        lo[0] = voxel_plane(g.origin[0], g.voxel, x0);
+        lo[1] = lo_y;
+        lo[2] = lo_z;
+        hi[0] = voxel_plane(g.origin[0], g.voxel, x1);
+        hi[1] = voxel_plane(g.origin[1], g.voxel, y1);
+        hi[2] = voxel_plane(g.origin[2], g.voxel, z1);
     });
 }

@@ -548,6 +548,30 @@ class Robot:
         return res
 
     # ---- scenes from sensor data (cppf_scene_from_points / cppf_scene_from_depth; include/cppflow_hip.h) ------------------------------
+    def _voxel_self(self, q_self, dev: torch.device):
+        """the self filter's arguments: (q_self [n_self, d] -- to be kept alive over the call --, n_self, its pointer, the handle); without
+        configurations the library takes neither pointer nor handle"""
+        if q_self is None:
+            return None, 0, None, None
+        q_self = self._x2d(q_self.unsqueeze(0) if q_self.dim() == 1 else q_self, "q_self")
+        assert q_self.device == dev, "q_self must be on the device of the sensor data"
+        if int(q_self.shape[0]) == 0:
+            return q_self, 0, None, None
+        return q_self, int(q_self.shape[0]), q_self.data_ptr(), self._handle(dev)
+
+    @staticmethod
+    def _voxel_camera(depth: torch.Tensor, intrinsics, cam_to_world):
+        """the depth form's arguments: (depth, H, W, intrinsics fp32 [4], cam_to_world as R row-major then t, fp32 [12])"""
+        depth = _require_device_tensor(depth, "depth")
+        assert depth.dim() == 2, f"depth must be [H, W], is {tuple(depth.shape)}"
+        T = cam_to_world.detach().cpu().numpy() if isinstance(cam_to_world, torch.Tensor) else np.asarray(cam_to_world)
+        T = T.astype(np.float32)
+        assert T.shape in ((4, 4), (3, 4)), f"cam_to_world must be 4x4 or 3x4, is {T.shape}"
+        rt = np.ascontiguousarray(np.concatenate([T[:3, :3].reshape(9), T[:3, 3]]), dtype=np.float32)
+        k = np.ascontiguousarray(np.asarray([float(v) for v in intrinsics], dtype=np.float32))
+        assert k.shape == (4,), "intrinsics = (fx, fy, cx, cy)"
+        return depth, int(depth.shape[0]), int(depth.shape[1]), k, rt
+
     def _voxel_scene(self, source, dev: torch.device, origin, voxel_m: float, dims, q_self, self_margin_m: float, max_cuboids: int,
                      coarsen: bool):
         """the rounds behind `scene_from_points` / `scene_from_depth`; source(grid, tail) makes the library call of one round"""
@@ -557,14 +581,7 @@ class Robot:
         origin = [float(v) for v in origin]
         dims = [int(v) for v in dims]
         assert len(origin) == 3 and len(dims) == 3, "origin and dims have three entries"
-        if q_self is None:
-            n_self, q_ptr, handle = 0, None, None
-        else:
-            q_self = self._x2d(q_self.unsqueeze(0) if q_self.dim() == 1 else q_self, "q_self")
-            assert q_self.device == dev, "q_self must be on the device of the sensor data"
-            n_self, q_ptr, handle = int(q_self.shape[0]), q_self.data_ptr(), self._handle(dev)
-            if n_self == 0:
-                q_ptr, handle = None, None
+        q_self, n_self, q_ptr, handle = self._voxel_self(q_self, dev)
         cap = int(max_cuboids)
         lo = torch.empty((cap, 3), dtype=torch.float32, device=dev)
         hi = torch.empty((cap, 3), dtype=torch.float32, device=dev)
@@ -618,21 +635,22 @@ class Robot:
         """A depth image [H, W] (device, fp32 metres) -> `ObstacleScene`, as `scene_from_points` on its back-projected pixels
         (`cppf_scene_from_depth`).  intrinsics = (fx, fy, cx, cy); cam_to_world: a 4x4 (or 3x4) transform, host; a pixel counts only
         with z_min < depth < z_max."""
-        depth = _require_device_tensor(depth, "depth")
-        assert depth.dim() == 2, f"depth must be [H, W], is {tuple(depth.shape)}"
-        T = cam_to_world.detach().cpu().numpy() if isinstance(cam_to_world, torch.Tensor) else np.asarray(cam_to_world)
-        T = T.astype(np.float32)
-        assert T.shape in ((4, 4), (3, 4)), f"cam_to_world must be 4x4 or 3x4, is {T.shape}"
-        rt = np.ascontiguousarray(np.concatenate([T[:3, :3].reshape(9), T[:3, 3]]), dtype=np.float32)
-        k = np.ascontiguousarray(np.asarray([float(v) for v in intrinsics], dtype=np.float32))
-        assert k.shape == (4,), "intrinsics = (fx, fy, cx, cy)"
-        h, w = int(depth.shape[0]), int(depth.shape[1])
+        depth, h, w, k, rt = self._voxel_camera(depth, intrinsics, cam_to_world)
 
         def source(handle, tail):
             return _hip.lib().cppf_scene_from_depth(handle, depth.data_ptr() if h * w else None, h, w, _hip.fptr(k), _hip.fptr(rt),
                                                     float(z_min), float(z_max), *tail)  # fmt: skip
 
         return self._voxel_scene(source, depth.device, origin, voxel_m, dims, q_self, self_margin_m, max_cuboids, coarsen)
+
+    def voxel_map(self, origin, voxel_m: float, dims, device):
+        """A `VoxelMap` (cppflow_amd/scene.py) on `device`, cleared: the per-cell hit counts of the grid (origin, voxel_m, dims =
+        (nx, ny, nz)) that frames are added to over time, and from which `VoxelMap.scene(min_frames, merge_z)` builds an
+        `ObstacleScene` of the cells seen in at least `min_frames` frames (`cppf_voxel_map_*`, `cppf_scene_from_map`;
+        include/cppflow_hip.h, "Scenes fused over frames")."""
+        from cppflow_amd.scene import VoxelMap
+
+        return VoxelMap(self, origin, voxel_m, dims, device)
 
     def motion_travel_table(self) -> np.ndarray:
         """rho [d, n_capsules] fp32: the travel bounds `motion_clearance` certifies with (`cppf_motion_rho`; include/cppflow_hip.h).

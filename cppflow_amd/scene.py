@@ -5,6 +5,7 @@ all rows in one call (`Robot.scene_env_collisions`, csrc/kernels_scene.h; up to 
 planner turns the scene kernel's per-cuboid minimum distance into the <= 8 cuboids the optimiser's kernels take.
 """
 
+import ctypes
 import math
 from dataclasses import dataclass
 from typing import List, Optional, Sequence
@@ -44,7 +45,8 @@ class ObstacleScene:
     lo: torch.Tensor  # [O, 3] float32, world-frame min corners
     hi: torch.Tensor  # [O, 3] float32, world-frame max corners
     # a scene built from sensor data (`Robot.scene_from_points` / `scene_from_depth`) only: VOXEL_COUNT_NAMES of the round that
-    # was returned, and the grid it was built on ("voxel_m", "dims", "origin", "rounds": 1 + the coarsening rounds taken)
+    # was returned, and the grid it was built on ("voxel_m", "dims", "origin", "rounds": 1 + the coarsening rounds taken); of a
+    # `VoxelMap.scene`: what its docstring lists
     stats: Optional[dict] = None
 
     @property
@@ -68,6 +70,126 @@ class ObstacleScene:
 
     def to(self, device) -> "ObstacleScene":
         return ObstacleScene(self.lo.to(device), self.hi.to(device), self.stats)
+
+
+MAP_ADD_COUNT_NAMES = ("frame_cells", "kept_points", "outside_points", "invalid_points", "self_points",
+                       "frames")  # counts[2..7] of cppf_voxel_map_add_points / cppf_voxel_map_add_depth  # fmt: skip
+MAP_SCENE_COUNT_NAMES = ("boxes_total", "boxes_written", "occupied_cells", "seen_cells")  # counts[0..3] of cppf_scene_from_map
+
+
+class VoxelMap:
+    """Per-cell hit counts of a voxel grid, fused over frames on the device (`Robot.voxel_map`; include/cppflow_hip.h, "Scenes fused
+    over frames").  Owns the map tensor -- a 16-byte header { frames, 0, 0, 0 } and one uint8 counter per cell of the padded grid --
+    and the workspaces of its calls.  A counter counts the FRAMES in which its cell held at least one kept point (saturating at 255),
+    so `scene(min_frames=2)` drops what only one view ever saw.  Counters only grow until `clear()`."""
+
+    def __init__(self, robot, origin, voxel_m: float, dims, device):
+        from cppflow_amd import _hip
+
+        self.robot = robot
+        self.device = torch.device(device)
+        assert self.device.type == "cuda", f"a VoxelMap lives on the MI355X, not on '{self.device}' (no CPU fallback)"
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.origin = tuple(float(v) for v in origin)
+        self.voxel_m = float(voxel_m)
+        self.dims = tuple(int(v) for v in dims)
+        assert len(self.origin) == 3 and len(self.dims) == 3, "origin and dims have three entries"
+        self._grid = _hip.VoxelGrid((_hip._f * 3)(*self.origin), self.voxel_m, (_hip._i32 * 3)(*self.dims))
+        nbytes = ctypes.c_size_t()
+        _hip.check(_hip.lib().cppf_voxel_map_bytes(ctypes.byref(self._grid), ctypes.byref(nbytes)))
+        self._map = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
+        # one workspace for every call: that of an add with the most self-filter configurations serves the others
+        _hip.check(_hip.lib().cppf_voxel_scene_workspace_bytes(ctypes.byref(self._grid), _hip.VOXEL_MAX_SELF, ctypes.byref(nbytes)))
+        self._work = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
+        self._add_counts = torch.zeros((8,), dtype=torch.int32, device=self.device)
+        self.clear()
+
+    def _stream(self) -> int:
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def clear(self) -> None:
+        """every counter and `frames` to zero (one launch)"""
+        from cppflow_amd import _hip
+
+        with torch.cuda.device(self.device):  # (the map's calls without a handle launch on the current device)
+            _hip.check(_hip.lib().cppf_voxel_map_clear(self._map.data_ptr(), self._map.numel(), ctypes.byref(self._grid), self._stream()))
+            self._add_counts.zero_()
+
+    def _add(self, call, q_self, self_margin_m: float) -> None:
+        from cppflow_amd import _hip
+
+        q_self, n_self, q_ptr, handle = self.robot._voxel_self(q_self, self.device)
+        tail = (ctypes.byref(self._grid), q_ptr, n_self, float(self_margin_m), self._map.data_ptr(), self._map.numel(),
+                self._add_counts.data_ptr(), self._work.data_ptr(), self._work.numel(), self._stream())  # fmt: skip
+        with torch.cuda.device(self.device):
+            _hip.check(call(handle, tail))
+
+    def add_points(self, points: torch.Tensor, q_self: Optional[torch.Tensor] = None, self_margin_m: float = 0.03) -> None:
+        """one frame from a world-frame point cloud [n, 3] (device); the arguments are `Robot.scene_from_points`'s.  No
+        device-to-host copy: `last_counts()` fetches what the frame did."""
+        from cppflow_amd import _hip
+        from cppflow_amd.robots import _require_device_tensor
+
+        points = _require_device_tensor(points, "points")
+        assert points.dim() == 2 and points.shape[1] == 3, f"points must be [n, 3], is {tuple(points.shape)}"
+        assert points.device == self.device, "points must be on the map's device"
+        n = int(points.shape[0])
+        self._add(lambda handle, tail: _hip.lib().cppf_voxel_map_add_points(handle, points.data_ptr() if n else None, n, *tail),
+                  q_self, self_margin_m)  # fmt: skip
+
+    def add_depth(self, depth: torch.Tensor, intrinsics, cam_to_world, z_min: float, z_max: float,
+                  q_self: Optional[torch.Tensor] = None, self_margin_m: float = 0.03) -> None:
+        """one frame from a depth image [H, W] (device, fp32 metres); the arguments are `Robot.scene_from_depth`'s.  No
+        device-to-host copy."""
+        from cppflow_amd import _hip
+
+        depth, h, w, k, rt = self.robot._voxel_camera(depth, intrinsics, cam_to_world)
+        assert depth.device == self.device, "depth must be on the map's device"
+        self._add(lambda handle, tail: _hip.lib().cppf_voxel_map_add_depth(handle, depth.data_ptr() if h * w else None, h, w,
+                                                                           _hip.fptr(k), _hip.fptr(rt), float(z_min), float(z_max), *tail),
+                  q_self, self_margin_m)  # fmt: skip
+
+    def last_counts(self) -> dict:
+        """what the last add did (MAP_ADD_COUNT_NAMES; all zero before the first): one device-to-host copy"""
+        return dict(zip(MAP_ADD_COUNT_NAMES, self._add_counts.cpu().tolist()[2:]))
+
+    @property
+    def frames(self) -> int:
+        """the frames added since the last clear (one device-to-host copy of the header)"""
+        return int(self._map[:4].view(torch.int32).item())
+
+    def counts_tensor(self) -> torch.Tensor:
+        """the counters as a [nz, ny, nxp] uint8 VIEW of the map, nxp = 64 ceil(nx / 64); columns x >= nx are, and must stay, 0"""
+        nx, ny, nz = self.dims
+        return self._map[16:].view(nz, ny, (nx + 63) // 64 * 64)
+
+    def scene(self, min_frames: int = 1, merge_z: bool = True, max_cuboids: int = MAX_SCENE_OBSTACLES) -> ObstacleScene:
+        """The cells counted in at least `min_frames` (1 .. 255) frames as an `ObstacleScene` of at most `max_cuboids` cuboids, merged
+        along x and y (`cppf_scene_from_points`'s list) and, with `merge_z`, along z as well.  Its `.stats`: MAP_SCENE_COUNT_NAMES,
+        "frames", "min_frames", "merge_z" and the grid.  One device-to-host copy (the counts).  A truncated scene is never returned:
+        more boxes than `max_cuboids` raise RuntimeError.  There is no coarsening round as `Robot.scene_from_points` has one: a map
+        cannot be voxelised again from points that are gone -- raise `min_frames`, or keep a second, coarser map beside this one."""
+        from cppflow_amd import _hip
+
+        cap = int(max_cuboids)
+        assert 0 <= cap <= _hip.MAX_SCENE_OBSTACLES, f"max_cuboids must be in 0 .. {_hip.MAX_SCENE_OBSTACLES}"
+        assert 1 <= int(min_frames) <= 255, "min_frames must be in 1 .. 255"
+        lo = torch.empty((cap, 3), dtype=torch.float32, device=self.device)
+        hi = torch.empty((cap, 3), dtype=torch.float32, device=self.device)
+        counts = torch.empty((8,), dtype=torch.int32, device=self.device)
+        merge = _hip.VOXEL_MERGE_XYZ if merge_z else _hip.VOXEL_MERGE_XY
+        with torch.cuda.device(self.device):
+            _hip.check(_hip.lib().cppf_scene_from_map(self._map.data_ptr(), self._map.numel(), ctypes.byref(self._grid), int(min_frames),
+                                                      merge, cap, lo.data_ptr(), hi.data_ptr(), counts.data_ptr(), self._work.data_ptr(),
+                                                      self._work.numel(), self._stream()))  # fmt: skip
+        c = counts.cpu().tolist()  # (the one device-to-host copy)
+        stats = dict(zip(MAP_SCENE_COUNT_NAMES, c[:4]), frames=c[7], min_frames=int(min_frames), merge_z=bool(merge_z),
+                     voxel_m=self.voxel_m, dims=self.dims, origin=self.origin)  # fmt: skip
+        if c[0] > cap:
+            raise RuntimeError(f"the map gives {c[0]} boxes, more than max_cuboids = {cap} ({c[2]} occupied cells at min_frames = "
+                               f"{int(min_frames)}, merge_z = {bool(merge_z)}, {c[7]} frames): a truncated scene is never returned")  # fmt: skip
+        return ObstacleScene(lo[: c[1]].clone(), hi[: c[1]].clone(), stats)
 
 
 def problem_with_scene(problem, scene: ObstacleScene):

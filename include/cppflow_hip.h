@@ -418,6 +418,57 @@ int cppf_scene_from_depth(const cppf_robot* robot, const float* depth, int heigh
                           int n_self, float self_margin_m, int capacity, float* box_lo, float* box_hi, int32_t* counts,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* Scenes fused over frames: a persistent MAP of per-cell hit counts that frames are added to, and the scene of the cells seen in at
+ * least min_frames of them.  Grid, planes, cell of a point, classes, self filter, the depth form's arithmetic, the boxes of an
+ * occupancy and the capacity rule are the definitions above, word for word.  DEVICE pointers only; the library allocates nothing.
+ *   Map.  cppf_voxel_map_bytes(grid) = 16 + nxp ny nz bytes of device memory, 16-byte aligned, the caller's: a 16-byte header --
+ *   int32 frames, then three zero words -- and behind it one uint8 counter per cell of the padded grid, cell (x, y, z) at
+ *   (z ny + y) nxp + x.  Counters at x >= nx stay 0 (and are not read as cells).  At CPPF_VOXEL_MAX_CELLS the map is 16 MB + 16 B.  cppf_voxel_map_clear zeroes
+ *   all of it (header included) in one launch; a map must be cleared once before its first frame.
+ *   Adding a frame.  The frame's occupancy is that of cppf_scene_from_points / cppf_scene_from_depth on the same arguments: a cell
+ *   is occupied if it holds at least one KEPT input.  Then count = min(count + 1, 255) for every cell the frame occupies, every
+ *   other counter unchanged, and frames = min(frames + 1, INT32_MAX).  A counter therefore counts the FRAMES in which its cell held
+ *   a kept point, not points.  The map after a set of frames does not depend on their order.  n_points = 0 (height width = 0) is a
+ *   valid frame: frames + 1 and no counter changes.
+ *   counts int32 [8] of an add call: 0 and 1 zero, 2 the cells this frame occupies, 3 kept, 4 outside, 5 invalid, 6 self inputs of
+ *   this frame (they sum to the number of inputs), 7 frames after the call.
+ *   Map to scene.  1 <= min_frames <= 255.  A cell is occupied iff count >= min_frames.  merge = CPPF_VOXEL_MERGE_XY: the list is
+ *   "Boxes of an occupancy" above -- for a map of one frame and min_frames = 1 byte for byte the list cppf_scene_from_points /
+ *   _from_depth give for that frame.  merge = CPPF_VOXEL_MERGE_XYZ: "Boxes merged along z" below.  cppf_scene_from_map reads the
+ *   map and does not change it; it takes no robot.
+ *   counts int32 [8] of cppf_scene_from_map: 0 boxes in total, 1 boxes written, 2 occupied cells, 3 cells with count >= 1, 4..6 zero,
+ *   7 frames.
+ *   Boxes merged along z.  Let B(z) be the set of boxes (x0, x1, y, y1) of layer z under "Boxes of an occupancy": its heads, each
+ *   with the y1 it reaches.  A box of B(z) is a Z-HEAD if B(z-1) does not contain the identical (x0, x1, y, y1); every box of layer
+ *   0 is a z-head.  A z-head's cuboid spans z .. z1, z1 the first z' > z with (x0, x1, y, y1) not in B(z'), or nz.  The list is the
+ *   z-heads ascending by (z, y, x0):
+ *       box_lo = (P_x(x0), P_y(y), P_z(z)),  box_hi = (P_x(x1), P_y(y1), P_z(z1)).
+ *   Each B(z') tiles its layer exactly, so the union of the cuboids is the union of the occupied cells, exactly; the interiors of
+ *   the cuboids are disjoint; the list is a function of the occupancy alone.  (A box belongs to exactly one maximal chain of
+ *   consecutive layers that hold it, and the chain's first member is its z-head.)
+ * workspace: cppf_voxel_scene_workspace_bytes(grid, n_self) bytes for an add call, cppf_voxel_scene_workspace_bytes(grid, 0) for
+ * cppf_scene_from_map, 16-byte aligned, device; it need not be initialised and is scratch on return.  Every call is asynchronous on
+ * `stream`, makes no host synchronisation and can be captured in a graph: one launch for the clear, up to four for an add call (the
+ * three that build the frame's bitset and the integration), five for cppf_scene_from_map.  The only atomics are the integer OR of
+ * the point pass and integer adds of counts, so two runs give identical bytes, map included.
+ * CPPF_ERR_INVALID, before a device is selected: every refusal of the entry points above (grid, handle with n_self > 0, q_self,
+ * margin, the source's own, capacity and boxes, counts, workspace); a NULL or misaligned map; map_bytes other than
+ * cppf_voxel_map_bytes(grid) (a short map among them); min_frames outside 1 .. 255; a merge other than the two constants.  robot and
+ * q_self may be NULL only with n_self = 0. */
+#define CPPF_VOXEL_MERGE_XY 0  /* the existing box list */
+#define CPPF_VOXEL_MERGE_XYZ 1 /* merged along z as well */
+int cppf_voxel_map_bytes(const cppf_voxel_grid* grid, size_t* bytes);
+int cppf_voxel_map_clear(void* map, size_t map_bytes, const cppf_voxel_grid* grid, void* stream);
+int cppf_voxel_map_add_points(const cppf_robot* robot, const float* points, int n_points, const cppf_voxel_grid* grid,
+                              const float* q_self, int n_self, float self_margin_m, void* map, size_t map_bytes, int32_t* counts,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int cppf_voxel_map_add_depth(const cppf_robot* robot, const float* depth, int height, int width, const float intrinsics[4],
+                             const float cam_to_world[12], float z_min, float z_max, const cppf_voxel_grid* grid, const float* q_self,
+                             int n_self, float self_margin_m, void* map, size_t map_bytes, int32_t* counts, void* workspace,
+                             size_t workspace_bytes, void* stream);
+int cppf_scene_from_map(const void* map, size_t map_bytes, const cppf_voxel_grid* grid, int min_frames, int merge, int capacity,
+                        float* box_lo, float* box_hi, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Robot.self_collision_distances(x) -> [n, n_pairs] (call site cppflow/collision_detection.py:65) */
 int cppf_self_collision_distances(const cppf_robot* robot, const float* x, int n, float* dists, void* stream);
 
