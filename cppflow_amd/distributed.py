@@ -32,7 +32,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-PACKED_BYTES_PER_ROW = 15
+from cppflow_amd.packed_rows import PACKED_BYTES_PER_ROW, packed_views
+
 SEED_SUMMARY_FLOATS = 8  # Robot.SEED_SUMMARY_FIELDS
 FULL_WIDTH_ROWS = 262144  # four wavefronts per SIMD of the row shape on 256 CUs: the launch width of the unsharded C4 workload
 LM_POSE = dict(lm_lambda=1e-6, alpha_position=3.5, alpha_rotation=0.35)  # ALT_LOSS_V2_1_POSE (cppflow/lm_hyper_parameters.py:119-151)
@@ -108,10 +109,8 @@ class GatheredSeedOutputs:
 
 def unpack_rows(packed: torch.Tensor, n: int):
     """Views into one rank's packed buffer: (ext_cost, pos_err_m, rot_err_rad) float32 [n], 3 x uint8 [n]."""
-    assert packed.dtype == torch.uint8 and packed.numel() == PACKED_BYTES_PER_ROW * n
-    f = packed[: 12 * n].view(torch.float32)
-    m = packed[12 * n :]
-    return f[:n], f[n : 2 * n], f[2 * n :], m[:n], m[n : 2 * n], m[2 * n :]
+    v = packed_views(packed, n)
+    return v["ext_cost"], v["pos_err_m"], v["rot_err_rad"], v["self_mask"], v["env_mask"], v["jlim_mask"]
 
 
 def allgather_seed_outputs(

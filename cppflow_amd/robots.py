@@ -21,48 +21,21 @@ import numpy as np
 import torch
 
 from cppflow_amd import _hip
+from cppflow_amd._marshal import (
+    _check_summary_buffer, _ptr, _require_device_tensor, _require_output_tensor, _scene_boxes, _stream_ptr, device_packed_views,
+    fill_lm_outputs, optional_outputs, paths_tensor, query_size, rows_and_target, rows_tensor, sized_buffer,
+)  # fmt: skip
+from cppflow_amd.packed_rows import PACKED_BYTES_PER_ROW
 from cppflow_amd.robot_model import CanonicalChain, RobotSpec, canonicalize, urdf_forward_kinematics
 from cppflow_amd.robot_zoo import ROBOT_SPECS
+from cppflow_amd.scene import VOXEL_COUNT_NAMES, ObstacleScene, VoxelMap
 
-
-def _require_device_tensor(t: torch.Tensor, name: str, dtype=torch.float32) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a torch.Tensor")
-    if not t.is_cuda:
-        raise RuntimeError(
-            f"{name} is on '{t.device}': cppflow_amd runs on MI355X only (no CPU fallback); move the tensor to cuda"
-        )
-    assert t.dtype == dtype, f"{name} must be {dtype}, is {t.dtype}"
-    return t if t.is_contiguous() else t.contiguous()
-
-
-def _require_output_tensor(t: torch.Tensor, name: str, dtype=torch.float32) -> torch.Tensor:
-    """A caller-supplied OUTPUT buffer: the kernel writes through its data_ptr(), so a non-contiguous tensor cannot be
-    silently replaced by a contiguous copy (the caller's buffer would never be written)."""
-    t = _require_device_tensor(t, name, dtype) if t.is_contiguous() else None
-    assert t is not None, f"{name} is an output buffer and must be contiguous"
-    return t
-
-
-def _stream_ptr(device: torch.device) -> int:
-    return torch.cuda.current_stream(device).cuda_stream
-
-
-def _scene_boxes(box_lo: torch.Tensor, box_hi: torch.Tensor, dev: torch.device, rows: str = "q"):
-    """The cuboids of a device scene, world-frame corners [O, 3] on the device of the rows (`rows`: their name) -> (box_lo, box_hi, O)."""
-    box_lo, box_hi = _require_device_tensor(box_lo, "box_lo"), _require_device_tensor(box_hi, "box_hi")
-    assert box_lo.dim() == 2 and box_lo.shape[1] == 3 and box_hi.shape == box_lo.shape, (tuple(box_lo.shape), tuple(box_hi.shape))
-    assert box_lo.device == dev and box_hi.device == dev, f"{rows}, box_lo and box_hi must be on one device"
-    return box_lo, box_hi, int(box_lo.shape[0])
-
-
-def _ptr(res: Dict[str, torch.Tensor], k: str) -> Optional[int]:
-    """the pointer of the output res[k], or None where it was not asked for"""
-    return res[k].data_ptr() if k in res else None
+# the per-row arguments of cppf_seed_summary, in the order of its signature (each a view of the packed buffer)
+_SEED_SUMMARY_ROW_ARGS = ("ext_cost", "pos_err_m", "rot_err_rad", "self_mask", "env_mask", "jlim_mask")
 
 
 class Robot:
-    PACKED_BYTES_PER_ROW = 15  # 3 x fp32 (ext_cost, pos_err_m, rot_err_rad) + 3 x u8 (self, env, jlim masks)
+    PACKED_BYTES_PER_ROW = PACKED_BYTES_PER_ROW  # (cppflow_amd/packed_rows.py)
 
     def __init__(self, spec: RobotSpec, specialize: Optional[bool] = None):
         """`specialize` (default: on unless CPPF_SPECIALIZE=0): a robot that is not one of the shipped tables gets its kernels
@@ -150,6 +123,12 @@ class Robot:
                     )
         return h
 
+    def _call(self, entry: str, dev: torch.device, *args) -> None:
+        """The entry point `entry` on this robot's handle for `dev`, with `args` between the handle and the stream.  The one place
+        that holds for every such call that the stream is the current stream of the device the tensors live on, and that the return
+        code is never dropped."""
+        _hip.check(getattr(_hip.lib(), entry)(self._handle(dev), *args, _stream_ptr(dev)))
+
     def specialization(self, device=None) -> int:
         """>= 0: index of the generated table this robot runs; 1000: kernels compiled for it at run time (hipRTC); -1: generic."""
         dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -231,18 +210,12 @@ class Robot:
 
     # ---- jrl-compatible compute methods --------------------------------------------------------------------------------
     def _x2d(self, x: torch.Tensor, name: str = "x") -> torch.Tensor:
-        x = _require_device_tensor(x, name)
-        assert x.dim() == 2 and x.shape[1] == self.ndof, f"{name} must be [n, {self.ndof}], is {tuple(x.shape)}"
-        return x
+        return rows_tensor(x, self.ndof, name)
 
     def forward_kinematics(self, x: torch.Tensor, out_device=None, dtype=None) -> torch.Tensor:
         x = self._x2d(x)
         poses = torch.empty((x.shape[0], 7), dtype=torch.float32, device=x.device)
-        _hip.check(
-            _hip.lib().cppf_forward_kinematics(
-                self._handle(x.device), x.data_ptr(), x.shape[0], poses.data_ptr(), _stream_ptr(x.device)
-            )
-        )
+        self._call("cppf_forward_kinematics", x.device, x.data_ptr(), x.shape[0], poses.data_ptr())
         if dtype is not None and dtype != torch.float32:
             poses = poses.to(dtype)
         if out_device is not None and torch.device(out_device) != poses.device:
@@ -252,31 +225,20 @@ class Robot:
     def jacobian(self, x: torch.Tensor) -> torch.Tensor:
         x = self._x2d(x)
         J = torch.empty((x.shape[0], 6, self.ndof), dtype=torch.float32, device=x.device)
-        _hip.check(
-            _hip.lib().cppf_jacobian(self._handle(x.device), x.data_ptr(), x.shape[0], J.data_ptr(), _stream_ptr(x.device))
-        )
+        self._call("cppf_jacobian", x.device, x.data_ptr(), x.shape[0], J.data_ptr())
         return J
 
     def self_collision_distances(self, x: torch.Tensor) -> torch.Tensor:
         x = self._x2d(x)
         d = torch.empty((x.shape[0], self.n_collision_pairs), dtype=torch.float32, device=x.device)
-        _hip.check(
-            _hip.lib().cppf_self_collision_distances(
-                self._handle(x.device), x.data_ptr(), x.shape[0], d.data_ptr(), _stream_ptr(x.device)
-            )
-        )
+        self._call("cppf_self_collision_distances", x.device, x.data_ptr(), x.shape[0], d.data_ptr())
         return d
 
     def env_collision_distances(self, x: torch.Tensor, cuboid, Tcuboid) -> torch.Tensor:
         x = self._x2d(x)
         cub, rt = self._pack_obstacles([cuboid], [Tcuboid])
         d = torch.empty((x.shape[0], self.n_capsules), dtype=torch.float32, device=x.device)
-        _hip.check(
-            _hip.lib().cppf_env_collision_distances(
-                self._handle(x.device), x.data_ptr(), x.shape[0], _hip.fptr(cub[0]), _hip.fptr(rt[0]), d.data_ptr(),
-                _stream_ptr(x.device),
-            )  # fmt: skip
-        )
+        self._call("cppf_env_collision_distances", x.device, x.data_ptr(), x.shape[0], _hip.fptr(cub[0]), _hip.fptr(rt[0]), d.data_ptr())
         return d
 
     def self_collision_distances_jacobian(self, x: torch.Tensor, return_distances: bool = False):
@@ -285,12 +247,8 @@ class Robot:
         n = x.shape[0]
         J = torch.zeros((n, self.n_collision_pairs, self.ndof), dtype=torch.float32, device=x.device)
         dist = torch.empty((n, self.n_collision_pairs), dtype=torch.float32, device=x.device) if return_distances else None
-        _hip.check(
-            _hip.lib().cppf_self_collision_distances_jacobian(
-                self._handle(x.device), x.data_ptr(), n, J.data_ptr(), dist.data_ptr() if dist is not None else None,
-                _stream_ptr(x.device),
-            )  # fmt: skip
-        )
+        self._call("cppf_self_collision_distances_jacobian", x.device, x.data_ptr(), n, J.data_ptr(),
+                   dist.data_ptr() if dist is not None else None)  # fmt: skip
         return (J, dist) if return_distances else J
 
     def env_collision_distances_jacobian(self, x: torch.Tensor, cuboid, Tcuboid, return_distances: bool = False):
@@ -300,38 +258,25 @@ class Robot:
         cub, rt = self._pack_obstacles([cuboid], [Tcuboid])
         J = torch.zeros((n, self.n_capsules, self.ndof), dtype=torch.float32, device=x.device)
         dist = torch.empty((n, self.n_capsules), dtype=torch.float32, device=x.device) if return_distances else None
-        _hip.check(
-            _hip.lib().cppf_env_collision_distances_jacobian(
-                self._handle(x.device), x.data_ptr(), n, _hip.fptr(cub[0]), _hip.fptr(rt[0]), J.data_ptr(),
-                dist.data_ptr() if dist is not None else None, _stream_ptr(x.device),
-            )  # fmt: skip
-        )
+        self._call("cppf_env_collision_distances_jacobian", x.device, x.data_ptr(), n, _hip.fptr(cub[0]), _hip.fptr(rt[0]), J.data_ptr(),
+                   dist.data_ptr() if dist is not None else None)  # fmt: skip
         return (J, dist) if return_distances else J
 
     def clamp_to_joint_limits(self, x: torch.Tensor) -> torch.Tensor:
         """In place (and returned), like cppflow/optimization_utils.py:831-833."""
         x_c = self._x2d(x)
         assert x_c.data_ptr() == x.data_ptr(), "clamp_to_joint_limits mutates its argument: x must be contiguous"
-        _hip.check(
-            _hip.lib().cppf_clamp_to_joint_limits(self._handle(x.device), x.data_ptr(), x.shape[0], _stream_ptr(x.device))
-        )
+        self._call("cppf_clamp_to_joint_limits", x.device, x.data_ptr(), x.shape[0])
         return x
 
     # ---- fused entry points ----------------------------------------------------------------------------------------------
     def pose_errors(self, x: torch.Tensor, target: torch.Tensor, want_current_poses: bool = True):
         """get_6d_pose_errors: returns (e [n,6,1], current_poses [n,7]).  `target` is [W,7] with n % W == 0."""
-        x = self._x2d(x)
-        target = _require_device_tensor(target, "target_poses")
-        n, W = x.shape[0], target.shape[0]
-        assert target.dim() == 2 and target.shape[1] == 7 and W > 0 and n % W == 0, (tuple(target.shape), n)
+        x, target, n, W = rows_and_target(x, target, self.ndof)
         e = torch.empty((n, 6, 1), dtype=torch.float32, device=x.device)
         cur = torch.empty((n, 7), dtype=torch.float32, device=x.device) if want_current_poses else None
-        _hip.check(
-            _hip.lib().cppf_pose_errors(
-                self._handle(x.device), x.data_ptr(), target.data_ptr(), n // W, W, e.data_ptr(),
-                cur.data_ptr() if cur is not None else None, _stream_ptr(x.device),
-            )  # fmt: skip
-        )
+        self._call("cppf_pose_errors", x.device, x.data_ptr(), target.data_ptr(), n // W, W, e.data_ptr(),
+                   cur.data_ptr() if cur is not None else None)  # fmt: skip
         return e, cur
 
     def lm_pose_steps(
@@ -374,61 +319,32 @@ class Robot:
         `solver` the precision of the damped solve: `_hip.SOLVER_AUTO` (default: the reference's dtype with the conditioning gate --
         rows whose fp32 solve is estimated to be off by more than 1e-5 in task space redo it in double precision),
         `_hip.SOLVER_F64` (every row in double precision: a verification mode, ~10x the iteration time) or `_hip.SOLVER_F32` (no gate)."""
-        x = self._x2d(x)
-        target = _require_device_tensor(target, "target_path")
-        n, W = x.shape[0], target.shape[0]
-        assert target.dim() == 2 and target.shape[1] == 7, tuple(target.shape)
-        assert W > 0 and n % W == 0, f"x has {n} rows, not a multiple of the {W} target waypoints"
-        dev = x.device
-        if x_out is not None:
-            x_out = _require_output_tensor(x_out, "x_out")
-            assert x_out.shape == x.shape and x_out.device == dev
-        res: Dict[str, torch.Tensor] = {"x": x_out if x_out is not None else torch.empty_like(x)}
+        x, target, n, W = rows_and_target(x, target, self.ndof)
         out = _hip.LmOutputs()
-        out.x_out = res["x"].data_ptr()
-        if packed_out is not None:
-            assert packed_out.dtype == torch.uint8 and packed_out.is_cuda and packed_out.is_contiguous()
-            assert packed_out.numel() == self.PACKED_BYTES_PER_ROW * n and packed_out.data_ptr() % 4 == 0
-            f = packed_out[: 12 * n].view(torch.float32)
-            res["ext_cost"], res["pos_err_m"], res["rot_err_rad"] = f[:n], f[n : 2 * n], f[2 * n :]
-            m = packed_out[12 * n :]
-            res["self_mask"], res["env_mask"], res["jlim_mask"] = m[:n], m[n : 2 * n], m[2 * n :]
-            for k in ("ext_cost", "pos_err_m", "rot_err_rad", "self_mask", "env_mask", "jlim_mask"):
-                setattr(out, k, res[k].data_ptr())
-            want_errors = want_collisions = False
+        res, _ = fill_lm_outputs(out, x, W, x_out if x_out is not None else torch.empty_like(x), packed_out, None, summary_out)
+
+        def on_request(key: str, dtype, *tail: int, field: Optional[str] = None) -> None:
+            res[key] = torch.empty((n, *tail), dtype=dtype, device=x.device)
+            setattr(out, field or key, res[key].data_ptr())
+
         if return_residual:
-            res["J"] = torch.empty((n, 6, self.ndof), dtype=torch.float32, device=dev)
-            res["e"] = torch.empty((n, 6, 1), dtype=torch.float32, device=dev)
-            out.J_out, out.e_out = res["J"].data_ptr(), res["e"].data_ptr()
-        if want_errors:
-            res["pos_err_m"] = torch.empty(n, dtype=torch.float32, device=dev)
-            res["rot_err_rad"] = torch.empty(n, dtype=torch.float32, device=dev)
-            out.pos_err_m, out.rot_err_rad = res["pos_err_m"].data_ptr(), res["rot_err_rad"].data_ptr()
-        if want_collisions:
+            on_request("J", torch.float32, 6, self.ndof, field="J_out")
+            on_request("e", torch.float32, 6, 1, field="e_out")
+        if want_errors and packed_out is None:
+            on_request("pos_err_m", torch.float32)
+            on_request("rot_err_rad", torch.float32)
+        if want_collisions and packed_out is None:
             for k in ("self_mask", "env_mask", "jlim_mask"):
-                res[k] = torch.empty(n, dtype=torch.uint8, device=dev)
-            res["ext_cost"] = torch.empty(n, dtype=torch.float32, device=dev)
-            out.self_mask, out.env_mask, out.jlim_mask = (res[k].data_ptr() for k in ("self_mask", "env_mask", "jlim_mask"))
-            out.ext_cost = res["ext_cost"].data_ptr()
+                on_request(k, torch.uint8)
+            on_request("ext_cost", torch.float32)
             if want_min_dists:
-                res["min_self"] = torch.empty(n, dtype=torch.float32, device=dev)
-                res["min_env"] = torch.empty(n, dtype=torch.float32, device=dev)
-                out.min_self, out.min_env = res["min_self"].data_ptr(), res["min_env"].data_ptr()
-        if summary_out is not None:
-            _check_summary_buffer(summary_out, n // W, dev)
-            out.seed_summary = summary_out.data_ptr()
-            res["seed_summary"] = summary_out
+                on_request("min_self", torch.float32)
+                on_request("min_env", torch.float32)
         if want_iters:
-            res["n_iters"] = torch.empty(n, dtype=torch.int32, device=dev)
-            out.n_iters = res["n_iters"].data_ptr()
+            on_request("n_iters", torch.int32)
         prm = _hip.LmParams(float(lm_lambda), float(alpha_position), float(alpha_rotation), int(n_steps), int(bool(clamp)),
                             float(tol_pos_m), float(tol_rot_rad), int(shape), int(solver))
-        _hip.check(
-            _hip.lib().cppf_lm_pose_steps(
-                self._handle(dev), x.data_ptr(), target.data_ptr(), n // W, W, ctypes.byref(prm), ctypes.byref(out),
-                _stream_ptr(dev),
-            )  # fmt: skip
-        )
+        self._call("cppf_lm_pose_steps", x.device, x.data_ptr(), target.data_ptr(), n // W, W, ctypes.byref(prm), ctypes.byref(out))
         return res
 
     def lm_launch_plan(self, x: torch.Tensor, target: torch.Tensor, lm_lambda: float, alpha_position: float,
@@ -470,12 +386,7 @@ class Robot:
         c = _hip.Constraints(float(constraints.max_allowed_position_error_cm), float(constraints.max_allowed_rotation_error_deg),
                              float(constraints.max_allowed_mjac_deg), float(constraints.max_allowed_mjac_cm),
                              int(bool(self_collisions_ignored)), int(bool(env_collisions_ignored)))  # fmt: skip
-        _hip.check(
-            _hip.lib().cppf_select_valid_seed_gathered(
-                self._handle(s.device), s.data_ptr(), n_chunks, n_groups, S_chunk, ctypes.byref(c), out.data_ptr(),
-                _stream_ptr(s.device),
-            )  # fmt: skip
-        )
+        self._call("cppf_select_valid_seed_gathered", s.device, s.data_ptr(), n_chunks, n_groups, S_chunk, ctypes.byref(c), out.data_ptr())
         return out
 
     def collision_masks(
@@ -484,9 +395,7 @@ class Robot:
         """q [S, W, d] -> self_mask / env_mask / jlim_mask (bool [S,W]) and ext_cost (float [S,W]) in one launch, against
         the obstacles / limit padding last given to set_obstacles / set_joint_limit_padding.  `only` (subset of
         "self", "env", "jlim") restricts the work: the kernel skips what no requested output needs."""
-        q = _require_device_tensor(q, "q")
-        assert q.dim() == 3 and q.shape[2] == self.ndof, f"q must be [k, ntimesteps, {self.ndof}], is {tuple(q.shape)}"
-        S, W, _ = q.shape
+        q, S, W = paths_tensor(q, self.ndof)
         dev = q.device
         parts = ("self", "env", "jlim") if only is None else tuple(only)
         assert set(parts) <= {"self", "env", "jlim"} and len(parts) > 0, parts
@@ -500,13 +409,8 @@ class Robot:
                 res["min_self"] = torch.empty((S, W), dtype=torch.float32, device=dev)
             if "env" in parts:
                 res["min_env"] = torch.empty((S, W), dtype=torch.float32, device=dev)
-
-        _hip.check(
-            _hip.lib().cppf_collision_masks(
-                self._handle(dev), q.data_ptr(), S, W, _ptr(res, "self_mask"), _ptr(res, "env_mask"), _ptr(res, "jlim_mask"),
-                _ptr(res, "ext_cost"), _ptr(res, "min_self"), _ptr(res, "min_env"), _stream_ptr(dev),
-            )  # fmt: skip
-        )
+        self._call("cppf_collision_masks", dev, q.data_ptr(), S, W, _ptr(res, "self_mask"), _ptr(res, "env_mask"), _ptr(res, "jlim_mask"),
+                   _ptr(res, "ext_cost"), _ptr(res, "min_self"), _ptr(res, "min_env"))  # fmt: skip
         for k in ("self_mask", "env_mask", "jlim_mask"):
             if k in res:
                 res[k] = res[k].view(torch.bool)
@@ -525,25 +429,12 @@ class Robot:
         S, W = (1, lead[0]) if q.dim() == 2 else lead
         dev = q.device
         box_lo, box_hi, O = _scene_boxes(box_lo, box_hi, dev)
-        want = tuple(want)
-        assert set(want) <= {"env_mask", "min_env", "nearest_obs", "obs_min"}, want
-        res: Dict[str, torch.Tensor] = {"env_mask": torch.empty(lead, dtype=torch.uint8, device=dev)}
-        if "min_env" in want:
-            res["min_env"] = torch.empty(lead, dtype=torch.float32, device=dev)
-        if "nearest_obs" in want:
-            res["nearest_obs"] = torch.empty(lead, dtype=torch.int32, device=dev)
-        if "obs_min" in want:
-            res["obs_min"] = torch.empty((O,), dtype=torch.float32, device=dev)
-        nbytes = ctypes.c_size_t()
-        _hip.check(_hip.lib().cppf_scene_workspace_bytes(S * W, O, ctypes.byref(nbytes)))
-        work = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-
-        _hip.check(
-            _hip.lib().cppf_scene_env_collisions(
-                self._handle(dev), q.data_ptr(), S, W, box_lo.data_ptr(), box_hi.data_ptr(), O, float(reach), _ptr(res, "env_mask"),
-                _ptr(res, "min_env"), _ptr(res, "nearest_obs"), _ptr(res, "obs_min"), work.data_ptr(), nbytes.value, _stream_ptr(dev),
-            )  # fmt: skip
-        )
+        spec = {"env_mask": torch.uint8, "min_env": torch.float32, "nearest_obs": torch.int32, "obs_min": (torch.float32, (O,))}
+        res = optional_outputs((*want, "env_mask"), spec, lead, dev)
+        work = sized_buffer("cppf_scene_workspace_bytes", dev, S * W, O)
+        self._call("cppf_scene_env_collisions", dev, q.data_ptr(), S, W, box_lo.data_ptr(), box_hi.data_ptr(), O, float(reach),
+                   _ptr(res, "env_mask"), _ptr(res, "min_env"), _ptr(res, "nearest_obs"), _ptr(res, "obs_min"), work.data_ptr(),
+                   work.numel())  # fmt: skip
         res["env_mask"] = res["env_mask"].view(torch.bool)
         return res
 
@@ -575,8 +466,6 @@ class Robot:
     def _voxel_scene(self, source, dev: torch.device, origin, voxel_m: float, dims, q_self, self_margin_m: float, max_cuboids: int,
                      coarsen: bool):
         """the rounds behind `scene_from_points` / `scene_from_depth`; source(grid, tail) makes the library call of one round"""
-        from cppflow_amd.scene import VOXEL_COUNT_NAMES, ObstacleScene
-
         assert 0 <= int(max_cuboids) <= _hip.MAX_SCENE_OBSTACLES, f"max_cuboids must be in 0 .. {_hip.MAX_SCENE_OBSTACLES}"
         origin = [float(v) for v in origin]
         dims = [int(v) for v in dims]
@@ -589,11 +478,9 @@ class Robot:
         voxel, history = float(voxel_m), []
         for rnd in range(4 if coarsen else 1):
             grid = _hip.VoxelGrid((_hip._f * 3)(*origin), voxel, (_hip._i32 * 3)(*dims))
-            nbytes = ctypes.c_size_t()
-            _hip.check(_hip.lib().cppf_voxel_scene_workspace_bytes(ctypes.byref(grid), n_self, ctypes.byref(nbytes)))
-            work = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+            work = sized_buffer("cppf_voxel_scene_workspace_bytes", dev, ctypes.byref(grid), n_self)
             tail = (ctypes.byref(grid), q_ptr, n_self, float(self_margin_m), cap, lo.data_ptr(), hi.data_ptr(), counts.data_ptr(),
-                    work.data_ptr(), nbytes.value, _stream_ptr(dev))  # fmt: skip
+                    work.data_ptr(), work.numel(), _stream_ptr(dev))  # fmt: skip
             with torch.cuda.device(dev):  # (without a handle the library launches on the current device)
                 _hip.check(source(handle, tail))
             c = counts.cpu().tolist()  # (the one device-to-host copy of this round)
@@ -648,8 +535,6 @@ class Robot:
         (nx, ny, nz)) that frames are added to over time, and from which `VoxelMap.scene(min_frames, merge_z)` builds an
         `ObstacleScene` of the cells seen in at least `min_frames` frames (`cppf_voxel_map_*`, `cppf_scene_from_map`;
         include/cppflow_hip.h, "Scenes fused over frames")."""
-        from cppflow_amd.scene import VoxelMap
-
         return VoxelMap(self, origin, voxel_m, dims, device)
 
     def motion_travel_table(self) -> np.ndarray:
@@ -675,32 +560,18 @@ class Robot:
         status (uint8 [S, W-1], always returned): bit 0 certified collision-free, bit 1 hit (a node penetrates), neither: undecided.
         min_clear (float [S, W-1]): the smallest node clearance (cuboids beyond `reach` do not count); hit_node (int32 [S, W-1]):
         the lowest penetrating node, else -1; nodes (float [S, W-1, 2^level + 1, d], only when asked for): the configurations tested."""
-        q = _require_device_tensor(q, "q")
-        assert q.dim() == 3 and q.shape[2] == self.ndof, f"q must be [k, ntimesteps, {self.ndof}], is {tuple(q.shape)}"
-        S, W, _ = q.shape
+        q, S, W = paths_tensor(q, self.ndof)
         dev = q.device
         box_lo, box_hi, O = _scene_boxes(box_lo, box_hi, dev)
-        want = tuple(want)
-        assert set(want) <= {"status", "min_clear", "hit_node", "nodes"}, want
         level = int(level)
         assert 0 <= level <= _hip.MOTION_MAX_LEVEL and W >= 2, (level, W)
-        res: Dict[str, torch.Tensor] = {"status": torch.empty((S, W - 1), dtype=torch.uint8, device=dev)}
-        if "min_clear" in want:
-            res["min_clear"] = torch.empty((S, W - 1), dtype=torch.float32, device=dev)
-        if "hit_node" in want:
-            res["hit_node"] = torch.empty((S, W - 1), dtype=torch.int32, device=dev)
-        if "nodes" in want:
-            res["nodes"] = torch.empty((S, W - 1, (1 << level) + 1, self.ndof), dtype=torch.float32, device=dev)
-        nbytes = ctypes.c_size_t()
-        _hip.check(_hip.lib().cppf_motion_workspace_bytes(S, W, ctypes.byref(nbytes)))
-        work = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-
-        _hip.check(
-            _hip.lib().cppf_motion_clearance(
-                self._handle(dev), q.data_ptr(), S, W, level, box_lo.data_ptr(), box_hi.data_ptr(), O, float(reach), _ptr(res, "status"),
-                _ptr(res, "min_clear"), _ptr(res, "hit_node"), _ptr(res, "nodes"), work.data_ptr(), nbytes.value, _stream_ptr(dev),
-            )  # fmt: skip
-        )
+        spec = {"status": torch.uint8, "min_clear": torch.float32, "hit_node": torch.int32,
+                "nodes": (torch.float32, (S, W - 1, (1 << level) + 1, self.ndof))}  # fmt: skip
+        res = optional_outputs((*want, "status"), spec, (S, W - 1), dev)
+        work = sized_buffer("cppf_motion_workspace_bytes", dev, S, W)
+        self._call("cppf_motion_clearance", dev, q.data_ptr(), S, W, level, box_lo.data_ptr(), box_hi.data_ptr(), O, float(reach),
+                   _ptr(res, "status"), _ptr(res, "min_clear"), _ptr(res, "hit_node"), _ptr(res, "nodes"), work.data_ptr(),
+                   work.numel())  # fmt: skip
         return res
 
     def motion_resolve(self, q: torch.Tensor, box_lo: torch.Tensor, box_hi: torch.Tensor, start_level: int = 0, max_depth: int = 16,
@@ -714,13 +585,9 @@ class Robot:
         clearance of any node evaluated; n_tested (int32): interval tests spent.  `decided` (uint8 or bool [S, W-1]): transitions
         where it is non-zero are not examined; given a uint8 tensor, it is ALSO the status output, so that a status from an earlier
         call is completed in place and the other outputs of such transitions keep what they held (here: zeros)."""
-        q = _require_device_tensor(q, "q")
-        assert q.dim() == 3 and q.shape[2] == self.ndof, f"q must be [k, ntimesteps, {self.ndof}], is {tuple(q.shape)}"
-        S, W, _ = q.shape
+        q, S, W = paths_tensor(q, self.ndof)
         dev = q.device
         box_lo, box_hi, O = _scene_boxes(box_lo, box_hi, dev)
-        want = tuple(want)
-        assert set(want) <= {"status", "depth", "hit_num", "min_clear", "n_tested"}, want
         start_level, max_depth, max_frontier = int(start_level), int(max_depth), int(max_frontier)
         assert 0 <= start_level <= _hip.MOTION_MAX_LEVEL and start_level <= max_depth <= _hip.MOTION_RESOLVE_MAX_DEPTH, (start_level, max_depth)
         assert (1 << start_level) <= max_frontier <= _hip.MOTION_RESOLVE_MAX_FRONTIER and W >= 2, (max_frontier, W)
@@ -731,39 +598,22 @@ class Robot:
             assert decided.shape == (S, W - 1) and decided.device == dev, (tuple(decided.shape), decided.device)
             assert decided.is_contiguous(), "decided must be contiguous"
         in_place = skipping and decided.dtype == torch.uint8
-        # with `decided` the skipped transitions are not written: their outputs must not be uninitialised memory
-        new = torch.zeros if skipping else torch.empty
-        res: Dict[str, torch.Tensor] = {"status": decided if in_place else new((S, W - 1), dtype=torch.uint8, device=dev)}
-        for k, dtype in (("depth", torch.int32), ("hit_num", torch.int32), ("min_clear", torch.float32), ("n_tested", torch.int32)):
-            if k in want:
-                res[k] = new((S, W - 1), dtype=dtype, device=dev)
-        nbytes = ctypes.c_size_t()
-        _hip.check(_hip.lib().cppf_motion_resolve_workspace_bytes(S, W, max_frontier, ctypes.byref(nbytes)))
-        work = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-
-        _hip.check(
-            _hip.lib().cppf_motion_resolve(
-                self._handle(dev), q.data_ptr(), S, W, start_level, max_depth, max_frontier, box_lo.data_ptr(), box_hi.data_ptr(), O,
-                float(reach), decided.data_ptr() if skipping else None, _ptr(res, "status"), _ptr(res, "depth"), _ptr(res, "hit_num"), _ptr(res, "min_clear"),
-                _ptr(res, "n_tested"), work.data_ptr(), nbytes.value, _stream_ptr(dev),
-            )  # fmt: skip
-        )
+        spec = {"status": torch.uint8, "depth": torch.int32, "hit_num": torch.int32, "min_clear": torch.float32, "n_tested": torch.int32}
+        # with `decided` the skipped transitions are not written: their outputs must not be uninitialised memory (torch.zeros)
+        res = optional_outputs((*want, "status"), spec, (S, W - 1), dev, given={"status": decided} if in_place else None,
+                               new=torch.zeros if skipping else torch.empty)  # fmt: skip
+        work = sized_buffer("cppf_motion_resolve_workspace_bytes", dev, S, W, max_frontier)
+        self._call("cppf_motion_resolve", dev, q.data_ptr(), S, W, start_level, max_depth, max_frontier, box_lo.data_ptr(),
+                   box_hi.data_ptr(), O, float(reach), decided.data_ptr() if skipping else None, _ptr(res, "status"), _ptr(res, "depth"),
+                   _ptr(res, "hit_num"), _ptr(res, "min_clear"), _ptr(res, "n_tested"), work.data_ptr(), work.numel())  # fmt: skip
         return res
 
     def pose_error_metrics(self, x: torch.Tensor, target: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """(positional error [n] in metres, rotational error [n] in radians); target [W,7], n % W == 0."""
-        x = self._x2d(x)
-        target = _require_device_tensor(target, "target_path")
-        n, W = x.shape[0], target.shape[0]
-        assert target.dim() == 2 and target.shape[1] == 7 and W > 0 and n % W == 0
+        x, target, n, W = rows_and_target(x, target, self.ndof)
         pe = torch.empty(n, dtype=torch.float32, device=x.device)
         re = torch.empty(n, dtype=torch.float32, device=x.device)
-        _hip.check(
-            _hip.lib().cppf_pose_error_metrics(
-                self._handle(x.device), x.data_ptr(), target.data_ptr(), n // W, W, pe.data_ptr(), re.data_ptr(),
-                _stream_ptr(x.device),
-            )  # fmt: skip
-        )
+        self._call("cppf_pose_error_metrics", x.device, x.data_ptr(), target.data_ptr(), n // W, W, pe.data_ptr(), re.data_ptr())
         return pe, re
 
     def track_paths(self, target_path: torch.Tensor, k: int, n_segments: int = 1, q0: Optional[torch.Tensor] = None,
@@ -796,13 +646,8 @@ class Robot:
         prm = _hip.TrackParams(float(lm_lambda), float(alpha_position), float(alpha_rotation), int(n_restart), int(n_track),
                                int(n_random_restarts), float(tol_pos_m), float(tol_rot_rad), float(max_jump_rad), float(max_jump_m),
                                int(seed) & 0xFFFFFFFF, int(call_index) & 0xFFFFFFFF)  # fmt: skip
-        _hip.check(
-            _hip.lib().cppf_track_paths(
-                self._handle(dev), target.data_ptr(), T, k, S, ctypes.byref(prm), q0.data_ptr() if q0 is not None else None,
-                res["x"].data_ptr(), res["pos_err_m"].data_ptr(), res["rot_err_rad"].data_ptr(), res["status"].data_ptr(),
-                _stream_ptr(dev),
-            )  # fmt: skip
-        )
+        self._call("cppf_track_paths", dev, target.data_ptr(), T, k, S, ctypes.byref(prm), q0.data_ptr() if q0 is not None else None,
+                   res["x"].data_ptr(), res["pos_err_m"].data_ptr(), res["rot_err_rad"].data_ptr(), res["status"].data_ptr())  # fmt: skip
         return res
 
     PLAN_METRIC_FIELDS = ("max_pos_err_cm", "mean_pos_err_cm", "max_rot_err_deg", "mean_rot_err_deg", "mjac_deg", "mjac_cm",
@@ -814,18 +659,11 @@ class Robot:
     def seed_summary(self, x: torch.Tensor, packed: torch.Tensor, S: int, W: int, out: Optional[torch.Tensor] = None):
         """[S,8] per-seed reduction (SEED_SUMMARY_FIELDS) of a fused launch's packed per-row outputs and its x_out."""
         x = self._x2d(x)
-        n = S * W
-        assert x.shape[0] == n and packed.dtype == torch.uint8 and packed.numel() == self.PACKED_BYTES_PER_ROW * n
-        assert packed.is_cuda and packed.is_contiguous() and packed.data_ptr() % 4 == 0
+        assert x.shape[0] == S * W, (tuple(x.shape), S, W)
+        rows = device_packed_views(packed, S * W, x.device)
         if out is None:
             out = torch.empty((S, 8), dtype=torch.float32, device=x.device)
-        base = packed.data_ptr()
-        _hip.check(
-            _hip.lib().cppf_seed_summary(
-                self._handle(x.device), x.data_ptr(), S, W, base, base + 4 * n, base + 8 * n, base + 12 * n, base + 13 * n,
-                base + 14 * n, out.data_ptr(), _stream_ptr(x.device),
-            )  # fmt: skip
-        )
+        self._call("cppf_seed_summary", x.device, x.data_ptr(), S, W, *(rows[k].data_ptr() for k in _SEED_SUMMARY_ROW_ARGS), out.data_ptr())
         return out
 
     def lm_full_step(self, x: torch.Tensor, target: torch.Tensor, opt_params, virtual_configs: Optional[torch.Tensor] = None,
@@ -840,10 +678,7 @@ class Robot:
         `scene` = (box_lo, box_hi), device [O, 3] world-frame corners (`cppflow_amd.scene.ObstacleScene`: `.lo`, `.hi`), O <= 4096:
         the environment rows come from ALL of these cuboids instead of the handle's at most 8, which are then neither read nor
         changed (`cppf_lm_full_step_scene`).  Where a handle could hold the cuboids that penetrate, the result is the same bit for bit."""
-        x = self._x2d(x)
-        target = _require_device_tensor(target, "target_path")
-        n, W = x.shape[0], target.shape[0]
-        assert target.dim() == 2 and target.shape[1] == 7 and W > 0 and n % W == 0
+        x, target, n, W = rows_and_target(x, target, self.ndof)
         p = opt_params
         xv = None
         if virtual_configs is not None and p.use_virtual_configs and virtual_configs.numel() > 0:
@@ -858,22 +693,13 @@ class Robot:
         y = torch.empty(n * d, dtype=torch.float32, device=dev)
         if x_out is None:
             x_out = torch.empty_like(x)
+        head = (x.data_ptr(), target.data_ptr(), xv.data_ptr() if xv is not None else None, n // W, W, ctypes.byref(prm), int(pin))
+        tail = (blocks.data_ptr(), G.data_ptr(), y.data_ptr(), x_out.data_ptr())
         if scene is not None:
             box_lo, box_hi, O = _scene_boxes(*scene, dev, rows="x")
-            _hip.check(
-                _hip.lib().cppf_lm_full_step_scene(
-                    self._handle(dev), x.data_ptr(), target.data_ptr(), xv.data_ptr() if xv is not None else None, n // W, W,
-                    ctypes.byref(prm), int(pin), box_lo.data_ptr() if O else None, box_hi.data_ptr() if O else None, O,
-                    blocks.data_ptr(), G.data_ptr(), y.data_ptr(), x_out.data_ptr(), _stream_ptr(dev),
-                )  # fmt: skip
-            )
-            return x_out
-        _hip.check(
-            _hip.lib().cppf_lm_full_step_pinned(
-                self._handle(dev), x.data_ptr(), target.data_ptr(), xv.data_ptr() if xv is not None else None, n // W, W,
-                ctypes.byref(prm), int(pin), blocks.data_ptr(), G.data_ptr(), y.data_ptr(), x_out.data_ptr(), _stream_ptr(dev),
-            )  # fmt: skip
-        )
+            self._call("cppf_lm_full_step_scene", dev, *head, box_lo.data_ptr() if O else None, box_hi.data_ptr() if O else None, O, *tail)
+        else:
+            self._call("cppf_lm_full_step_pinned", dev, *head, *tail)
         return x_out
 
     @staticmethod
@@ -906,34 +732,23 @@ class Robot:
         """(workspace, control) for `lm_optimize_enqueue`: the workspace (fp32; its first S*W*ndof floats are the snapshot of the last
         valid x) and the loop-control block (int32: records then trace), initialised so that every record leads with a pose step."""
         dev = torch.device(device)
-        nb = ctypes.c_size_t(0)
-        _hip.check(_hip.lib().cppf_lm_optimize_workspace_bytes(self._handle(dev), S, W, ctypes.byref(nb)))
-        workspace = torch.empty(nb.value // 4, dtype=torch.float32, device=dev)
-        _hip.check(_hip.lib().cppf_lm_optimize_control_bytes(S, ctypes.byref(prm), ctypes.byref(nb)))
+        n_floats = query_size("cppf_lm_optimize_workspace_bytes", self._handle(dev), S, W) // 4
         n_records = S if prm.per_trajectory else 1
         init = _hip.optloop_initial_control(n_records, prm.trace_capacity)
-        assert init.nbytes == nb.value
-        control = torch.from_numpy(init).to(dev)
-        return workspace, control
+        assert init.nbytes == query_size("cppf_lm_optimize_control_bytes", S, ctypes.byref(prm))
+        return torch.empty(n_floats, dtype=torch.float32, device=dev), torch.from_numpy(init).to(dev)
 
     def lm_optimize_enqueue(self, x: torch.Tensor, target: torch.Tensor, prm: "_hip.OptloopParams", workspace: torch.Tensor,
                             control: torch.Tensor, n_iterations: int, pin: int = 0) -> None:
         """Enqueue `n_iterations` gated iterations of the alternating loop on x [S*W, d] (in place) and return without
         synchronising; copy `control` back to see what was decided (`_hip.OptloopRecord` per record, then the trace).
         `pin` (`_hip.PIN_FIRST | _hip.PIN_LAST`): the named end rows of every trajectory are never written."""
-        xc = self._x2d(x)
+        xc, target, n, W = rows_and_target(x, target, self.ndof)
         assert xc.data_ptr() == x.data_ptr(), "lm_optimize_enqueue works on x in place: x must be contiguous"
-        target = _require_device_tensor(target, "target_path")
-        n, W = x.shape[0], target.shape[0]
-        assert target.dim() == 2 and target.shape[1] == 7 and W > 0 and n % W == 0
         assert workspace.is_cuda and workspace.dtype == torch.float32 and workspace.is_contiguous()
         assert control.is_cuda and control.dtype == torch.int32 and control.is_contiguous()
-        _hip.check(
-            _hip.lib().cppf_lm_optimize_enqueue_pinned(
-                self._handle(x.device), x.data_ptr(), target.data_ptr(), n // W, W, ctypes.byref(prm), int(pin), workspace.data_ptr(),
-                control.data_ptr(), int(n_iterations), _stream_ptr(x.device),
-            )  # fmt: skip
-        )
+        self._call("cppf_lm_optimize_enqueue_pinned", x.device, x.data_ptr(), target.data_ptr(), n // W, W, ctypes.byref(prm), int(pin),
+                   workspace.data_ptr(), control.data_ptr(), int(n_iterations))  # fmt: skip
 
     def dp_search(self, q: torch.Tensor, ext_cost: torch.Tensor, prismatic_joint_scaling: float = 5.0, method: str = "auto",
                   return_memo: bool = False, return_method: bool = False):
@@ -944,10 +759,8 @@ class Robot:
         (table up to 128 candidates, 192 for chains of more than 8 joints; resident up to 1024; launches beyond).  Bit-identical results.
         `return_method` appends the method that ran ("table" / "resident" / "launches") to the result."""
         assert method in ("auto", "table", "resident", "launches"), method
-        q = _require_device_tensor(q, "q")
+        (q, k, T), d = paths_tensor(q, self.ndof), self.ndof
         ext_cost = _require_device_tensor(ext_cost, "q_costs_external")
-        assert q.dim() == 3 and q.shape[2] == self.ndof, tuple(q.shape)
-        k, T, d = q.shape
         assert ext_cost.shape == (k, T), (tuple(ext_cost.shape), (k, T))
         dev = q.device
         qT = torch.empty((T, k, d), dtype=torch.float32, device=dev)
@@ -955,36 +768,25 @@ class Robot:
         memoT = torch.empty((T, k), dtype=torch.int32, device=dev)
         best_path = torch.empty((T, d), dtype=torch.float32, device=dev)
         best_idx = torch.empty(T, dtype=torch.int32, device=dev)
-        n_table = ctypes.c_size_t(0)
-        _hip.check(_hip.lib().cppf_dp_table_floats(k, T, ctypes.byref(n_table)))
+        n_table = query_size("cppf_dp_table_floats", k, T)
         # measured (scripts/dp_bench.py, profiles/r3_dp_bench.txt): the table form wins up to k = 128 (k = 64: 168 vs 321 us, 128: 365
         # vs 442); from 129 candidates on its rows take the 192-wide register sets (~540 us at T = 256 whatever k) and the resident
         # hand-off form is ahead (k = 175: 491 vs 537 us, 256: 493 vs 812) -- unless the chain has more than 8 joints, whose
         # per-pair arithmetic in front of every hand-off keeps the table form ahead up to k = 192 (12 joints: 551 vs 618 us)
         k_table = 128 if d <= 8 else 192
-        tabled = method == "table" or (method == "auto" and k <= k_table and 2 <= T <= 65536 and n_table.value * 4 <= (1 << 30))
+        tabled = method == "table" or (method == "auto" and k <= k_table and 2 <= T <= 65536 and n_table * 4 <= (1 << 30))
+        head = (q.data_ptr(), ext_cost.data_ptr(), k, T, float(prismatic_joint_scaling), qT.data_ptr(), costsT.data_ptr(), memoT.data_ptr())
         if tabled:
             ran = "table"
-            table = torch.empty(max(n_table.value, 1), dtype=torch.float32, device=dev)
-            _hip.check(
-                _hip.lib().cppf_dp_search_tabled(
-                    self._handle(dev), q.data_ptr(), ext_cost.data_ptr(), k, T, float(prismatic_joint_scaling), qT.data_ptr(),
-                    costsT.data_ptr(), memoT.data_ptr(), table.data_ptr(), best_path.data_ptr(), best_idx.data_ptr(),
-                    _stream_ptr(dev),
-                )  # fmt: skip
-            )
+            table = torch.empty(max(n_table, 1), dtype=torch.float32, device=dev)
+            self._call("cppf_dp_search_tabled", dev, *head, table.data_ptr(), best_path.data_ptr(), best_idx.data_ptr())
         else:
             # ("resident" = this entry point as it decides itself, i.e. resident up to 1024 candidates unless the handle's
             # CPPF_TUNE_DP_PERSISTENT test switch is 0; "launches" forces one launch per waypoint for this call only)
             mode = _hip.DP_LAUNCHES if method == "launches" else _hip.DP_AUTO
             resident_on = self._tuning.get(_hip.TUNE_KEYS["dp_persistent"], 1) not in (0,)
             ran = "resident" if T >= 2 and k <= 1024 and mode == _hip.DP_AUTO and resident_on else "launches"
-            _hip.check(
-                _hip.lib().cppf_dp_search(
-                    self._handle(dev), q.data_ptr(), ext_cost.data_ptr(), k, T, float(prismatic_joint_scaling), qT.data_ptr(),
-                    costsT.data_ptr(), memoT.data_ptr(), best_path.data_ptr(), best_idx.data_ptr(), mode, _stream_ptr(dev),
-                )  # fmt: skip
-            )
+            self._call("cppf_dp_search", dev, *head, best_path.data_ptr(), best_idx.data_ptr(), mode)
         res = (best_path, best_idx, costsT) + ((memoT,) if return_memo else ())
         return res + ((ran,) if return_method else ())
 
@@ -995,38 +797,27 @@ class Robot:
         (paths [n_paths,T,d], path_idx [n_paths,T] int32, path_cost [n_paths], n_found [1] int32 -- a DEVICE tensor: nothing is
         synchronised here).  Slot 0 is the search's own best path; slots from n_found on are NaN / -1 / +inf; n_found = -1 when the
         tables carry the resident search's timed-out flag."""
-        q = _require_device_tensor(q, "q")
+        (q, k, T), d = paths_tensor(q, self.ndof), self.ndof
         costsT = _require_device_tensor(costsT, "costsT")
         memoT = _require_device_tensor(memoT, "memoT", torch.int32)
-        assert q.dim() == 3 and q.shape[2] == self.ndof, tuple(q.shape)
-        k, T, d = q.shape
         assert costsT.shape == (T, k) and memoT.shape == (T, k), (tuple(costsT.shape), tuple(memoT.shape), (T, k))
         n_paths = int(n_paths)
         dev = q.device
-        nbytes = ctypes.c_size_t(0)
-        _hip.check(_hip.lib().cppf_dp_nbest_workspace_bytes(k, T, n_paths, ctypes.byref(nbytes)))
-        workspace = torch.empty(nbytes.value // 4, dtype=torch.int32, device=dev)
+        work = sized_buffer("cppf_dp_nbest_workspace_bytes", dev, k, T, n_paths)
         paths = torch.empty((n_paths, T, d), dtype=torch.float32, device=dev)
         path_idx = torch.empty((n_paths, T), dtype=torch.int32, device=dev)
         path_cost = torch.empty(n_paths, dtype=torch.float32, device=dev)
         n_found = torch.empty(1, dtype=torch.int32, device=dev)
-        _hip.check(
-            _hip.lib().cppf_dp_nbest(
-                self._handle(dev), q.data_ptr(), costsT.data_ptr(), memoT.data_ptr(), k, T, n_paths, float(min_separation),
-                float(prismatic_joint_scaling), workspace.data_ptr(), paths.data_ptr(), path_idx.data_ptr(), path_cost.data_ptr(),
-                n_found.data_ptr(), _stream_ptr(dev),
-            )  # fmt: skip
-        )
+        self._call("cppf_dp_nbest", dev, q.data_ptr(), costsT.data_ptr(), memoT.data_ptr(), k, T, n_paths, float(min_separation),
+                   float(prismatic_joint_scaling), work.data_ptr(), paths.data_ptr(), path_idx.data_ptr(), path_cost.data_ptr(),
+                   n_found.data_ptr())  # fmt: skip
         return paths, path_idx, path_cost, n_found
 
     def plan_metrics(self, x: torch.Tensor, target: torch.Tensor, self_mask: Optional[torch.Tensor] = None,
                      env_mask: Optional[torch.Tensor] = None, q_init: Optional[torch.Tensor] = None) -> torch.Tensor:  # fmt: skip
         """[S,16] `Plan` metrics (cppflow/data_types.py:140-264) of S paths in one launch; columns PLAN_METRIC_FIELDS.
         x [S*W,d] (or [S,W,d]); masks are per-row uint8 / bool tensors of the same rows (optional); q_init [d] or [1,d]."""
-        x = self._x2d(x.reshape(-1, self.ndof) if x.dim() == 3 else x)
-        target = _require_device_tensor(target, "target_path")
-        n, W = x.shape[0], target.shape[0]
-        assert target.dim() == 2 and target.shape[1] == 7 and W > 0 and n % W == 0
+        x, target, n, W = rows_and_target(x.reshape(-1, self.ndof) if x.dim() == 3 else x, target, self.ndof)
         ptrs = []
         for m, nm in ((self_mask, "self_mask"), (env_mask, "env_mask")):
             if m is None:
@@ -1040,92 +831,30 @@ class Robot:
             qi = _require_device_tensor(q_init, "q_init").reshape(-1).contiguous()
             assert qi.numel() == self.ndof, tuple(q_init.shape)
         out = torch.empty((n // W, 16), dtype=torch.float32, device=x.device)
-        _hip.check(
-            _hip.lib().cppf_plan_metrics(
-                self._handle(x.device), x.data_ptr(), target.data_ptr(), n // W, W,
-                ptrs[0].data_ptr() if ptrs[0] is not None else None, ptrs[1].data_ptr() if ptrs[1] is not None else None,
-                qi.data_ptr() if qi is not None else None, out.data_ptr(), _stream_ptr(x.device),
-            )  # fmt: skip
-        )
+        self._call("cppf_plan_metrics", x.device, x.data_ptr(), target.data_ptr(), n // W, W,
+                   ptrs[0].data_ptr() if ptrs[0] is not None else None, ptrs[1].data_ptr() if ptrs[1] is not None else None,
+                   qi.data_ptr() if qi is not None else None, out.data_ptr())  # fmt: skip
         return out
 
     def mjacs(self, q: torch.Tensor, prismatic_joint_scaling: float = 5.0) -> torch.Tensor:
         """q [k,T,d] -> [k,k,T-1] maximum (wrapped, prismatic-scaled) joint change from candidate j at t to candidate i at
         t+1 (cppflow/search.py:100-125).  `dp_search` does not use it -- it is the tensor the reference builds."""
-        q = _require_device_tensor(q, "q")
-        assert q.dim() == 3 and q.shape[2] == self.ndof, tuple(q.shape)
-        k, T, _ = q.shape
+        q, k, T = paths_tensor(q, self.ndof)
         out = torch.empty((k, k, max(T - 1, 0)), dtype=torch.float32, device=q.device)
-        _hip.check(
-            _hip.lib().cppf_mjacs(
-                self._handle(q.device), q.contiguous().data_ptr(), k, T, float(prismatic_joint_scaling), out.data_ptr(),
-                _stream_ptr(q.device),
-            )
-        )
+        self._call("cppf_mjacs", q.device, q.data_ptr(), k, T, float(prismatic_joint_scaling), out.data_ptr())
         return out
 
     def seed_validity(self, x: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
         """[S,4]: per seed max position error (cm), max rotation error (deg), mjac revolute (deg), mjac prismatic (cm)."""
-        x = self._x2d(x)
-        target = _require_device_tensor(target, "target_path")
-        n, W = x.shape[0], target.shape[0]
-        assert target.dim() == 2 and target.shape[1] == 7 and W > 0 and n % W == 0
+        x, target, n, W = rows_and_target(x, target, self.ndof)
         out = torch.empty((n // W, 4), dtype=torch.float32, device=x.device)
-        _hip.check(
-            _hip.lib().cppf_seed_validity(
-                self._handle(x.device), x.data_ptr(), target.data_ptr(), n // W, W, out.data_ptr(), _stream_ptr(x.device)
-            )
-        )
+        self._call("cppf_seed_validity", x.device, x.data_ptr(), target.data_ptr(), n // W, W, out.data_ptr())
         return out
 
 
-def _check_summary_buffer(t: torch.Tensor, S: int, dev) -> None:
-    assert t.shape == (S, 8) and t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and t.device == dev, (
-        f"summary_out must be a contiguous fp32 [{S}, 8] tensor on {dev}"
-    )
-
-
-class LmLaunchPlan:
-    def __init__(self, robot: Robot, x, target, lm_lambda, alpha_position, alpha_rotation, n_steps, x_out, packed_out, clamp,
-                 summary_out=None, shape=_hip.SHAPE_AUTO, solver=_hip.SOLVER_AUTO, errors_out=None):  # fmt: skip
-        x = robot._x2d(x)
-        x_out = _require_output_tensor(x_out, "x_out")
-        target = _require_device_tensor(target, "target_path")
-        n, W = x.shape[0], target.shape[0]
-        assert target.dim() == 2 and target.shape[1] == 7 and W > 0 and n % W == 0 and x_out.shape == x.shape
-        self._keep = (robot, x, target, x_out, packed_out)  # the plan owns references to every buffer it points at
-        self._summary_keep = summary_out
-        self.outputs: Dict[str, torch.Tensor] = {"x": x_out}
-        out = _hip.LmOutputs()
-        out.x_out = x_out.data_ptr()
-        if packed_out is not None:
-            assert packed_out.dtype == torch.uint8 and packed_out.is_cuda and packed_out.is_contiguous()
-            assert packed_out.numel() == robot.PACKED_BYTES_PER_ROW * n and packed_out.data_ptr() % 4 == 0
-            f = packed_out[: 12 * n].view(torch.float32)
-            m = packed_out[12 * n :]
-            views = dict(ext_cost=f[:n], pos_err_m=f[n : 2 * n], rot_err_rad=f[2 * n :], self_mask=m[:n],
-                         env_mask=m[n : 2 * n], jlim_mask=m[2 * n :])  # fmt: skip
-            for k, v in views.items():
-                setattr(out, k, v.data_ptr())
-            self.outputs.update(views)
-        if errors_out is not None:
-            assert packed_out is None, "packed_out already holds the pose errors"
-            pe, re = (_require_output_tensor(t, nm) for t, nm in zip(errors_out, ("pos_err_m", "rot_err_rad")))
-            assert pe.numel() == n and re.numel() == n
-            out.pos_err_m, out.rot_err_rad = pe.data_ptr(), re.data_ptr()
-            self.outputs.update(pos_err_m=pe, rot_err_rad=re)
-            self._keep = self._keep + (pe, re)
-        if summary_out is not None:
-            _check_summary_buffer(summary_out, n // W, x.device)
-            out.seed_summary = summary_out.data_ptr()
-            self.outputs["seed_summary"] = summary_out
-        self._out = out
-        self._prm = _hip.LmParams(float(lm_lambda), float(alpha_position), float(alpha_rotation), int(n_steps), int(bool(clamp)),
-                                  0.0, 0.0, int(shape), int(solver))
-        self._fn = _hip.lib().cppf_lm_pose_steps
-        self._args = (robot._handle(x.device), x.data_ptr(), target.data_ptr(), n // W, W, ctypes.byref(self._prm),
-                      ctypes.byref(self._out))  # fmt: skip
-        self._device = x.device
+class _PreboundLaunch:
+    """A launch held ready: `_fn(*_args, stream)` is ONE C call on pre-marshalled arguments for the device `_device`, its return
+    code checked only when it is not zero.  This is the timed hot path of bench.py and `ShardedRefiner`: nothing else runs in it."""
 
     def launch(self) -> None:
         rc = self._fn(*self._args, torch.cuda.current_stream(self._device).cuda_stream)
@@ -1139,6 +868,21 @@ class LmLaunchPlan:
         if rc:
             _hip.check(rc)
 
+
+class LmLaunchPlan(_PreboundLaunch):
+    def __init__(self, robot: Robot, x, target, lm_lambda, alpha_position, alpha_rotation, n_steps, x_out, packed_out, clamp,
+                 summary_out=None, shape=_hip.SHAPE_AUTO, solver=_hip.SOLVER_AUTO, errors_out=None):  # fmt: skip
+        x, target, n, W = rows_and_target(x, target, robot.ndof)
+        self._out = _hip.LmOutputs()
+        self.outputs, keep = fill_lm_outputs(self._out, x, W, x_out, packed_out, errors_out, summary_out)
+        self._keep = [robot, x, target] + keep  # the plan owns references to every buffer it points at
+        self._prm = _hip.LmParams(float(lm_lambda), float(alpha_position), float(alpha_rotation), int(n_steps), int(bool(clamp)),
+                                  0.0, 0.0, int(shape), int(solver))
+        self._fn = _hip.lib().cppf_lm_pose_steps
+        self._args = (robot._handle(x.device), x.data_ptr(), target.data_ptr(), n // W, W, ctypes.byref(self._prm),
+                      ctypes.byref(self._out))  # fmt: skip
+        self._device = x.device
+
     def set_summary_out(self, summary_out: torch.Tensor) -> None:
         """Point the next launches' per-seed summary at another [S,8] buffer (a ring of buffers in flight on the wire)."""
         _check_summary_buffer(summary_out, self._args[3], self._device)
@@ -1147,15 +891,12 @@ class LmLaunchPlan:
 
     def summary_launcher(self, out: torch.Tensor):
         """A zero-allocation callable that reduces this plan's per-row outputs into `out` [S,8] (`Robot.seed_summary`)."""
-        robot, x, target, x_out, packed = self._keep[:5]
-        assert packed is not None, "the plan has no packed per-row outputs"
-        n, W = x.shape[0], target.shape[0]
-        assert out.shape == (n // W, 8) and out.dtype == torch.float32 and out.is_cuda and out.is_contiguous()
-        base = packed.data_ptr()
+        assert "ext_cost" in self.outputs, "the plan has no packed per-row outputs"
+        handle, S, W, device = self._args[0], self._args[3], self._args[4], self._device
+        _check_summary_buffer(out, S, device)
         fn = _hip.lib().cppf_seed_summary
-        args = (robot._handle(self._device), x_out.data_ptr(), n // W, W, base, base + 4 * n, base + 8 * n, base + 12 * n,
-                base + 13 * n, base + 14 * n, out.data_ptr())  # fmt: skip
-        device = self._device
+        args = (handle, self.outputs["x"].data_ptr(), S, W, *(self.outputs[k].data_ptr() for k in _SEED_SUMMARY_ROW_ARGS),
+                out.data_ptr())  # fmt: skip
 
         def launch() -> None:
             rc = fn(*args, torch.cuda.current_stream(device).cuda_stream)
@@ -1165,7 +906,7 @@ class LmLaunchPlan:
         return launch
 
 
-class LmBatchPlan:
+class LmBatchPlan(_PreboundLaunch):
     """`Robot.lm_batch_plan`: owns a cppf_lm_batch (a device table of the items' pointers) and references to every buffer in it."""
 
     def __init__(self, robot: Robot, items, lm_lambda, alpha_position, alpha_rotation, n_steps, clamp=True, solver=_hip.SOLVER_AUTO):
@@ -1173,57 +914,19 @@ class LmBatchPlan:
         arr = (_hip.LmBatchItem * len(items))()
         self._keep, self.outputs, dev = [robot], [], None
         for i, it in enumerate(items):
-            x = robot._x2d(it["x"])
-            target = _require_device_tensor(it["target"], "target_path")
-            x_out = _require_output_tensor(it["x_out"], "x_out")
-            n, W = x.shape[0], target.shape[0]
-            assert target.dim() == 2 and target.shape[1] == 7 and W > 0 and n % W == 0 and x_out.shape == x.shape
+            x, target, n, W = rows_and_target(it["x"], it["target"], robot.ndof)
             dev = x.device if dev is None else dev
-            assert x.device == dev and target.device == dev and x_out.device == dev, "every buffer of a batch lives on one device"
+            assert x.device == dev and target.device == dev, "every buffer of a batch lives on one device"
             arr[i].x_in, arr[i].target, arr[i].S, arr[i].W = x.data_ptr(), target.data_ptr(), n // W, W
-            out, views = arr[i].out, {"x": x_out}
-            out.x_out = x_out.data_ptr()
-            self._keep += [x, target, x_out]
-            packed = it.get("packed_out")
-            if packed is not None:
-                assert packed.dtype == torch.uint8 and packed.is_cuda and packed.is_contiguous() and packed.device == dev
-                assert packed.numel() == robot.PACKED_BYTES_PER_ROW * n and packed.data_ptr() % 4 == 0
-                f, m = packed[: 12 * n].view(torch.float32), packed[12 * n :]
-                v = dict(ext_cost=f[:n], pos_err_m=f[n : 2 * n], rot_err_rad=f[2 * n :], self_mask=m[:n], env_mask=m[n : 2 * n],
-                         jlim_mask=m[2 * n :])  # fmt: skip
-                for k, t in v.items():
-                    setattr(out, k, t.data_ptr())
-                views.update(v)
-                self._keep.append(packed)
-            if it.get("errors_out") is not None:
-                assert packed is None, "packed_out already holds the pose errors"
-                pe, re = (_require_output_tensor(t, nm) for t, nm in zip(it["errors_out"], ("pos_err_m", "rot_err_rad")))
-                assert pe.numel() == n and re.numel() == n
-                out.pos_err_m, out.rot_err_rad = pe.data_ptr(), re.data_ptr()
-                views.update(pos_err_m=pe, rot_err_rad=re)
-                self._keep += [pe, re]
-            if it.get("summary_out") is not None:
-                _check_summary_buffer(it["summary_out"], n // W, dev)
-                out.seed_summary = it["summary_out"].data_ptr()
-                views["seed_summary"] = it["summary_out"]
-                self._keep.append(it["summary_out"])
+            views, keep = fill_lm_outputs(arr[i].out, x, W, it["x_out"], it.get("packed_out"), it.get("errors_out"), it.get("summary_out"))
             self.outputs.append(views)
+            self._keep += [x, target] + keep
         prm = _hip.LmParams(float(lm_lambda), float(alpha_position), float(alpha_rotation), int(n_steps), int(bool(clamp)),
                             0.0, 0.0, _hip.SHAPE_ROW, int(solver))
         self._h = ctypes.c_void_p()
         self._lib = _hip.lib()
         _hip.check(self._lib.cppf_lm_batch_create(robot._handle(dev), len(items), arr, ctypes.byref(prm), ctypes.byref(self._h)))
-        self._fn, self._device, self.n_items = self._lib.cppf_lm_batch_launch, dev, len(items)
-
-    def launch(self) -> None:
-        rc = self._fn(self._h, torch.cuda.current_stream(self._device).cuda_stream)
-        if rc:
-            _hip.check(rc)
-
-    def launch_on(self, stream: "torch.cuda.Stream") -> None:
-        rc = self._fn(self._h, stream.cuda_stream)
-        if rc:
-            _hip.check(rc)
+        self._fn, self._args, self._device, self.n_items = self._lib.cppf_lm_batch_launch, (self._h,), dev, len(items)
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None

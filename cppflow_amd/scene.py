@@ -13,6 +13,8 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
+from cppflow_amd import _hip
+from cppflow_amd._marshal import _require_device_tensor, sized_buffer
 from cppflow_amd.robot_model import MAX_OBSTACLES
 
 MAX_SCENE_OBSTACLES = 4096  # CPPF_MAX_SCENE_OBSTACLES
@@ -84,8 +86,6 @@ class VoxelMap:
     so `scene(min_frames=2)` drops what only one view ever saw.  Counters only grow until `clear()`."""
 
     def __init__(self, robot, origin, voxel_m: float, dims, device):
-        from cppflow_amd import _hip
-
         self.robot = robot
         self.device = torch.device(device)
         assert self.device.type == "cuda", f"a VoxelMap lives on the MI355X, not on '{self.device}' (no CPU fallback)"
@@ -96,12 +96,9 @@ class VoxelMap:
         self.dims = tuple(int(v) for v in dims)
         assert len(self.origin) == 3 and len(self.dims) == 3, "origin and dims have three entries"
         self._grid = _hip.VoxelGrid((_hip._f * 3)(*self.origin), self.voxel_m, (_hip._i32 * 3)(*self.dims))
-        nbytes = ctypes.c_size_t()
-        _hip.check(_hip.lib().cppf_voxel_map_bytes(ctypes.byref(self._grid), ctypes.byref(nbytes)))
-        self._map = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
+        self._map = sized_buffer("cppf_voxel_map_bytes", self.device, ctypes.byref(self._grid))
         # one workspace for every call: that of an add with the most self-filter configurations serves the others
-        _hip.check(_hip.lib().cppf_voxel_scene_workspace_bytes(ctypes.byref(self._grid), _hip.VOXEL_MAX_SELF, ctypes.byref(nbytes)))
-        self._work = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
+        self._work = sized_buffer("cppf_voxel_scene_workspace_bytes", self.device, ctypes.byref(self._grid), _hip.VOXEL_MAX_SELF)
         self._add_counts = torch.zeros((8,), dtype=torch.int32, device=self.device)
         self.clear()
 
@@ -110,15 +107,11 @@ class VoxelMap:
 
     def clear(self) -> None:
         """every counter and `frames` to zero (one launch)"""
-        from cppflow_amd import _hip
-
         with torch.cuda.device(self.device):  # (the map's calls without a handle launch on the current device)
             _hip.check(_hip.lib().cppf_voxel_map_clear(self._map.data_ptr(), self._map.numel(), ctypes.byref(self._grid), self._stream()))
             self._add_counts.zero_()
 
     def _add(self, call, q_self, self_margin_m: float) -> None:
-        from cppflow_amd import _hip
-
         q_self, n_self, q_ptr, handle = self.robot._voxel_self(q_self, self.device)
         tail = (ctypes.byref(self._grid), q_ptr, n_self, float(self_margin_m), self._map.data_ptr(), self._map.numel(),
                 self._add_counts.data_ptr(), self._work.data_ptr(), self._work.numel(), self._stream())  # fmt: skip
@@ -128,9 +121,6 @@ class VoxelMap:
     def add_points(self, points: torch.Tensor, q_self: Optional[torch.Tensor] = None, self_margin_m: float = 0.03) -> None:
         """one frame from a world-frame point cloud [n, 3] (device); the arguments are `Robot.scene_from_points`'s.  No
         device-to-host copy: `last_counts()` fetches what the frame did."""
-        from cppflow_amd import _hip
-        from cppflow_amd.robots import _require_device_tensor
-
         points = _require_device_tensor(points, "points")
         assert points.dim() == 2 and points.shape[1] == 3, f"points must be [n, 3], is {tuple(points.shape)}"
         assert points.device == self.device, "points must be on the map's device"
@@ -142,8 +132,6 @@ class VoxelMap:
                   q_self: Optional[torch.Tensor] = None, self_margin_m: float = 0.03) -> None:
         """one frame from a depth image [H, W] (device, fp32 metres); the arguments are `Robot.scene_from_depth`'s.  No
         device-to-host copy."""
-        from cppflow_amd import _hip
-
         depth, h, w, k, rt = self.robot._voxel_camera(depth, intrinsics, cam_to_world)
         assert depth.device == self.device, "depth must be on the map's device"
         self._add(lambda handle, tail: _hip.lib().cppf_voxel_map_add_depth(handle, depth.data_ptr() if h * w else None, h, w,
@@ -170,8 +158,6 @@ class VoxelMap:
         "frames", "min_frames", "merge_z" and the grid.  One device-to-host copy (the counts).  A truncated scene is never returned:
         more boxes than `max_cuboids` raise RuntimeError.  There is no coarsening round as `Robot.scene_from_points` has one: a map
         cannot be voxelised again from points that are gone -- raise `min_frames`, or keep a second, coarser map beside this one."""
-        from cppflow_amd import _hip
-
         cap = int(max_cuboids)
         assert 0 <= cap <= _hip.MAX_SCENE_OBSTACLES, f"max_cuboids must be in 0 .. {_hip.MAX_SCENE_OBSTACLES}"
         assert 1 <= int(min_frames) <= 255, "min_frames must be in 1 .. 255"

@@ -123,6 +123,26 @@ def test_batch_contract_violations_are_refused():
         rb.lm_batch_plan([ok] * (_hip.MAX_BATCH + 1), n_steps=2, **LM)
     with pytest.raises(AssertionError):  # clamp = 0 is only defined for a single step, as for cppf_lm_pose_steps
         rb.lm_batch_plan([ok], n_steps=2, clamp=False, **LM)
+    # an output buffer on the host is refused on every route, on the host, before anything is launched (x_out keeps its sentinel)
+    S, W = 2, 4
+    xs, tgs = (dev(a) for a in H.lm_problem("panda", S, W, seed=2))
+    x_out = torch.full_like(xs, float("nan"))
+    packed = torch.empty(rb.PACKED_BYTES_PER_ROW * S * W, dtype=torch.uint8, device=DEV)
+    errs = (torch.empty(S * W, device=DEV), torch.empty(S * W, device=DEV))
+    summary = torch.empty((S, 8), dtype=torch.float32, device=DEV)
+    on_host = [dict(packed_out=packed.cpu()), dict(errors_out=(errs[0].cpu(), errs[1])), dict(errors_out=(errs[0], errs[1].cpu())),
+               dict(summary_out=summary.cpu()), dict(packed_out=packed, summary_out=summary.cpu())]  # fmt: skip
+    routes = {"lm_pose_steps": lambda kw: rb.lm_pose_steps(xs, tgs, n_steps=2, x_out=x_out, **kw, **LM),
+              "lm_launch_plan": lambda kw: rb.lm_launch_plan(xs, tgs, n_steps=2, x_out=x_out, **kw, **LM),
+              "lm_batch_plan": lambda kw: rb.lm_batch_plan([dict(x=xs, target=tgs, x_out=x_out, **kw)], n_steps=2, **LM)}  # fmt: skip
+    for route, call in routes.items():
+        for kw in on_host:
+            if route == "lm_pose_steps" and "errors_out" in kw:
+                continue  # (not an argument of lm_pose_steps)
+            with pytest.raises((AssertionError, RuntimeError)):
+                call(kw)
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(x_out).all())
     # the C ABI refuses the quad shape and the outputs a batch cannot produce
     arr = (_hip.LmBatchItem * 1)()
     arr[0].x_in, arr[0].target, arr[0].S, arr[0].W = x.data_ptr(), tg.data_ptr(), 2, 64

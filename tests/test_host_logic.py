@@ -255,6 +255,43 @@ def test_seed_shard_and_packed_layout():
     assert Robot.PACKED_BYTES_PER_ROW == PACKED_BYTES_PER_ROW
 
 
+def test_packed_views_pin_the_layout_as_byte_offsets():
+    """The packed per-row buffer as numbers, not as another spelling of the slicing code: for n rows the six views start 0, 4n, 8n,
+    12n, 13n and 14n bytes into the buffer (fp32 x 3, then u8 x 3, n values each); `unpack_rows` hands out those same views in its
+    documented order; and a buffer that cannot be one (a byte more or less, another dtype, strided, not 4-byte aligned) is refused."""
+    from cppflow_amd.packed_rows import packed_views
+
+    names = ("ext_cost", "pos_err_m", "rot_err_rad", "self_mask", "env_mask", "jlim_mask")
+    for n in (1, 3, 4, 256):
+        packed = torch.zeros(15 * n, dtype=torch.uint8)
+        views = packed_views(packed, n)
+        assert tuple(views) == names
+        offsets = [views[k].data_ptr() - packed.data_ptr() for k in names]
+        assert offsets == [0, 4 * n, 8 * n, 12 * n, 13 * n, 14 * n], (n, offsets)
+        assert [views[k].dtype for k in names] == [torch.float32] * 3 + [torch.uint8] * 3
+        assert all(views[k].shape == (n,) and views[k].is_contiguous() for k in names)
+        rows = unpack_rows(packed, n)
+        assert len(rows) == 6
+        for got, k in zip(rows, names):
+            assert got.data_ptr() == views[k].data_ptr() and got.dtype == views[k].dtype and got.shape == (n,), (n, k)
+        # a write through a view lands at its offset, and nowhere else
+        for i, k in enumerate(names):
+            views[k][n - 1] = i + 1
+        fp32_last, u8_last = 4 * (n - 1), n - 1
+        for i, off in enumerate(offsets):
+            at = off + (fp32_last if i < 3 else u8_last)
+            got = packed[at : at + 4].view(torch.float32).item() if i < 3 else packed[at].item()
+            assert got == i + 1, (n, names[i])
+        big = torch.zeros(15 * n + 8, dtype=torch.uint8)
+        for bad in (torch.zeros(15 * n + 1, dtype=torch.uint8), torch.zeros(15 * n - 1, dtype=torch.uint8),
+                    torch.zeros(15 * n, dtype=torch.int8), torch.zeros(30 * n, dtype=torch.uint8)[::2], big[1 : 15 * n + 1]):  # fmt: skip
+            assert bad.numel() != 15 * n or bad.dtype != torch.uint8 or not bad.is_contiguous() or bad.data_ptr() % 4 != 0
+            with pytest.raises(AssertionError):
+                packed_views(bad, n)
+            with pytest.raises(AssertionError):
+                unpack_rows(bad, n)
+
+
 def test_plan_container_mirrors_the_reference_properties():
     """`Plan` (cppflow/data_types.py:86-350): with a metrics row (as cppf_plan_metrics produces) every scalar property is
     read from it; without one the torch fall-backs give the same numbers; the verdict is the reference's conjunction."""
