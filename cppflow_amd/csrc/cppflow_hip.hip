@@ -988,8 +988,8 @@ int collision_masks_gated(const cppf_robot* robot, const float* q, int S, int W,
 }
 
 // Which elimination a coupled step of S trajectories of W waypoints resolves to on this handle (see the comments at the launches
-// in lm_full_step_gated).  Depends on the sizes, the parameters and the handle's tuning only, so a caller can know it before it
-// launches anything.
+// in run_full_step).  Depends on the sizes, the parameters and the handle's tuning only (t_pcr_lds: CPPF_TUNE_PCR_LDS as the plan
+// read it), so plan_full_step knows it before anything is launched.
 enum class FullStepForm {
     LaneVar,  // individually weighted differencing rows: one lane per trajectory, couplings read from memory
     Pcr,      // parallel in time
@@ -998,63 +998,60 @@ enum class FullStepForm {
     Lane,     // one lane per trajectory
     Local,    // the pose block without differencing rows: no elimination, every waypoint solved where its block is built, in fp64
 };
-FullStepForm full_step_form(const cppf_robot* robot, size_t n, int W, bool use_pose, bool use_diff, bool var_coupling) {
+FullStepForm full_step_form(const cppf_robot* robot, size_t n, int W, bool use_pose, bool use_diff, bool var_coupling, int t_pcr_lds) {
     const int ndof = robot->desc.ndof;
     const int t_pcr_rows = tune(robot, CPPF_TUNE_PCR_MAX_ROWS);
-    const bool g_pcr_lds = tune(robot, CPPF_TUNE_PCR_LDS) != 0;
     const bool g_rows_pose = tune(robot, CPPF_TUNE_ROWS_POSE) != 0, g_full_rows = tune(robot, CPPF_TUNE_FULL_ROWS) != 0;
-    const size_t pcr_rows = t_pcr_rows >= 0 ? (size_t)t_pcr_rows : (size_t)((W <= 256 && g_pcr_lds) ? kPcrMaxRowsLds : kPcrMaxRowsGlobal);
+    const size_t pcr_rows = t_pcr_rows >= 0 ? (size_t)t_pcr_rows : (size_t)((W <= 256 && t_pcr_lds != 0) ? kPcrMaxRowsLds : kPcrMaxRowsGlobal);
     const size_t pcr_limit = pcr_rows * (ndof <= 7 ? 100 : 50) / 100;
     if (use_pose && !use_diff) return FullStepForm::Local;
     if (var_coupling) return FullStepForm::LaneVar;
     if (!use_pose && W <= 512 && n <= pcr_limit && ndof >= 3 && ndof <= 8) return FullStepForm::Pcr;
     if ((!use_pose || g_rows_pose) && g_full_rows && ndof >= 3 && ndof <= 12 && W <= (1 << 19)) return FullStepForm::Rows;
-    // with the pose block the one-lane kernel keeps the case (see lm_full_step_gated); 9 .. 12 joints have no one-wavefront form
+    // with the pose block the one-lane kernel keeps the case (see run_full_step); 9 .. 12 joints have no one-wavefront form
     return ndof <= 8 && !use_pose ? FullStepForm::Wave : FullStepForm::Lane;
 }
-inline bool full_step_gateable(FullStepForm form) { return form == FullStepForm::Pcr || form == FullStepForm::Rows; }
-const char* const kGatedFormRefusal =
-    "cppflow_hip: the device-side optimiser loop gates the parallel-in-time and the row-per-lane "
-    "elimination only (no pose block, no individually weighted differencing rows, CPPF_TUNE_FULL_ROWS on)";
 
-// What a pinned coupled step refuses, from its arguments alone (before a device is selected, let alone anything launched)
-int full_step_pin_check(const cppf_robot* robot, int S, int W, const cppf_full_params* params, int pin) {
-    CPPF_REQUIRE(pin >= 0 && pin <= (CPPF_PIN_FIRST | CPPF_PIN_LAST), "pin_mask must be a combination of CPPF_PIN_FIRST and CPPF_PIN_LAST");
-    if (pin == 0) return CPPF_OK;
+// Everything a coupled step is once its arguments are known: made and checked by plan_full_step, launched by run_full_step
+enum class FullBlocks { Plain, Occ, Scene };  // full_blocks_kernel: the handle's cuboids, at two occupancies, or a scene's
+struct FullStepPlan {
+    FullK prm;  // (fold included)
+    FullStepForm form;
+    FullBlocks blocks;  // (under FullStepForm::Local the fp64 build of Plain or Scene)
+    // the parallel-in-time sub-form: the state in LDS, and then split over 512 lanes | its lanes per trajectory (256 or 512), the
+    // workgroups of the row-per-lane pair and of the one-lane kernels | the LDS bytes of the first two, and where in work_G the
+    // individually weighted couplings live (in floats)
+    bool pcr_in_lds, pcr_split;
+    unsigned pcr_block, rows_wgs, lane_grid;
+    size_t pcr_lds, rows_lds, w2next;
+};
+
+// The one place a coupled step is checked and decided: cppf_lm_full_step(_pinned), _scene (`scene`: its cuboids; never together with
+// `gated`) and the differencing step of the optimiser loop on the device (`gated`).  From the arguments and the handle's tuning alone,
+// each switch read once: no device is touched and nothing launched, so every refusal holds for a host-only handle too.
+int plan_full_step(const cppf_robot* robot, int S, int W, const cppf_full_params* params, int pin, bool gated, const SceneStepK* scene,
+                   FullStepPlan& plan) {
     CPPF_ROBOT_ALIVE(robot);
     CPPF_REQUIRE(params, "params is NULL");
-    if (params->differencing_mode != 0 || params->pose_do_scale_down_satisfied)
-        return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: a pinned end waypoint is not combined with the \"satisfied\" row options "
-                                          "(differencing_mode != 0, pose_do_scale_down_satisfied)");
-    // full_solve_wave_kernel: up to 8 joints, no pose block, and neither the parallel-in-time nor the row-per-lane form -- which is
-    // CPPF_TUNE_FULL_ROWS = 0 beyond the parallel-in-time sizes, and also fewer than 3 joints or more than 2^19 waypoints, where the
-    // row-per-lane form does not exist.
-    if (S >= 1 && W >= 1 && (size_t)S * W <= 0x7fffffffu &&
-        full_step_form(robot, (size_t)S * W, W, params->use_pose != 0, params->use_differencing != 0, false) == FullStepForm::Wave)
-        return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: the one-wavefront-per-trajectory elimination (what a step resolves to under "
-                                          "CPPF_TUNE_FULL_ROWS = 0, with fewer than 3 joints or beyond 2^19 waypoints) takes no "
-                                          "pinned end waypoint");
-    return CPPF_OK;
-}
-
-// cppf_lm_full_step(_pinned); with a gate (the optimiser loop on the device) only the trajectories it opens are stepped
-// `scene` (cppf_lm_full_step_scene; never together with a gate): the environment rows come from its cuboids, not the handle's
-int lm_full_step_gated(const cppf_robot* robot, const float* x_in, const float* target, const float* virtual_configs, int S, int W,
-                       const cppf_full_params* params, int pin, float* work_blocks, float* work_G, float* work_y, float* x_out,
-                       void* stream, const StepGateK gate, const SceneStepK* scene = nullptr) {
-    if (int rc = full_step_pin_check(robot, S, W, params, pin)) return rc;
-    CPPF_ENTER(robot);
-    CPPF_REQUIRE(params, "params is NULL");
+    CPPF_REQUIRE(pin >= 0 && pin <= (CPPF_PIN_FIRST | CPPF_PIN_LAST), "pin_mask must be a combination of CPPF_PIN_FIRST and CPPF_PIN_LAST");
     CPPF_REQUIRE(S >= 0 && W >= 1, "S < 0 or W < 1");
+    const size_t n = (size_t)S * W;
+    CPPF_REQUIRE(n <= 0x7fffffffu, "S*W exceeds 2^31-1 rows");
+    CPPF_REQUIRE(!scene || (scene->n_obs >= 0 && scene->n_obs <= CPPF_MAX_SCENE_OBSTACLES), "n_obs out of range (0 .. CPPF_MAX_SCENE_OBSTACLES)");
+    CPPF_REQUIRE(!scene || scene->n_obs == 0 || (scene->box_lo && scene->box_hi), "box_lo / box_hi is NULL");
     CPPF_REQUIRE(params->lm_lambda > 0.f, "lm_lambda must be > 0");
     CPPF_REQUIRE(!params->use_virtual_configs || (params->n_virtual_configs > 0 && 2 * params->n_virtual_configs < W),
                  "2 * n_virtual_configs must be < number of waypoints (optimization_utils.py:449-451)");
-    CPPF_REQUIRE(x_out != x_in, "x_out must not alias x_in (the back substitution reads x_in)");
-    if (S == 0) return CPPF_OK;
-    CPPF_REQUIRE(x_in && target && work_blocks && work_G && work_y && x_out, "NULL pointer");
-    const size_t n = (size_t)S * W;
-    CPPF_REQUIRE(n <= 0x7fffffffu, "S*W exceeds 2^31-1 rows");
-    FullK prm;
+    // the "satisfied" row options (cppflow/optimization_utils.py:514-533, 548-606)
+    CPPF_REQUIRE(params->differencing_mode >= 0 && params->differencing_mode <= 2, "differencing_mode must be 0, 1 or 2");
+    CPPF_REQUIRE(!params->pose_do_scale_down_satisfied || (params->pose_scale_down >= 0.f && params->pose_scale_down < 1.f),
+                 "pose scale-down must be in [0, 1) (optimization_utils.py:305)");
+    CPPF_REQUIRE(params->differencing_mode != 2 || (params->differencing_scale_down >= 0.f && params->differencing_scale_down < 1.f),
+                 "differencing scale-down must be in [0, 1) (optimization_utils.py:367)");
+    if (pin != 0 && (params->differencing_mode != 0 || params->pose_do_scale_down_satisfied))
+        return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: a pinned end waypoint is not combined with the \"satisfied\" row options "
+                                          "(differencing_mode != 0, pose_do_scale_down_satisfied)");
+    FullK& prm = plan.prm;
     prm.lm_lambda = params->lm_lambda;
     prm.a_pos = params->alpha_position;
     prm.a_rot = params->alpha_rotation;
@@ -1072,12 +1069,6 @@ int lm_full_step_gated(const cppf_robot* robot, const float* x_in, const float* 
     prm.S = S;
     prm.W = W;
     prm.pin = pin;
-    // the "satisfied" row options (cppflow/optimization_utils.py:514-533, 548-606)
-    CPPF_REQUIRE(params->differencing_mode >= 0 && params->differencing_mode <= 2, "differencing_mode must be 0, 1 or 2");
-    CPPF_REQUIRE(!params->pose_do_scale_down_satisfied || (params->pose_scale_down >= 0.f && params->pose_scale_down < 1.f),
-                 "pose scale-down must be in [0, 1) (optimization_utils.py:305)");
-    CPPF_REQUIRE(params->differencing_mode != 2 || (params->differencing_scale_down >= 0.f && params->differencing_scale_down < 1.f),
-                 "differencing scale-down must be in [0, 1) (optimization_utils.py:367)");
     prm.pose_scale_satisfied = params->use_pose && params->pose_do_scale_down_satisfied;
     prm.pose_thr_m = params->pose_threshold_m;
     prm.pose_thr_rad = params->pose_threshold_rad;
@@ -1090,83 +1081,107 @@ int lm_full_step_gated(const cppf_robot* robot, const float* x_in, const float* 
     // Individually weighted differencing rows: the coupling between waypoints t and t + 1 is no longer the same constant for
     // every t, which the tuned elimination kernels assume; such a step goes through the one-lane-per-trajectory kernel with the
     // couplings read from memory (w2next: the spare tail of work_G -- that kernel keeps d(d+1)/2 of the d*d floats per row).
-    const bool var_coupling = prm.diff_mode != 0;
-    float* const w2next = work_G + n * (size_t)(robot->desc.ndof * (robot->desc.ndof + 1) / 2);
-    // which elimination kernel: see the comments at the launches below
+    const int d = robot->desc.ndof;
+    plan.w2next = n * (size_t)(d * (d + 1) / 2);
     const int t_pcr_lds = tune(robot, CPPF_TUNE_PCR_LDS);
-    const bool g_pcr_lds = t_pcr_lds != 0, g_pcr_split = t_pcr_lds != 1;
-    const FullStepForm form = full_step_form(robot, n, W, prm.use_pose != 0, prm.use_diff != 0, var_coupling);
-    prm.fold = form != FullStepForm::Pcr;  // (the parallel-in-time kernel assembles the terms itself: FullK::fold)
-    if (gate.ctl != nullptr && !full_step_gateable(form)) return fail(CPPF_ERR_UNSUPPORTED, kGatedFormRefusal);
+    plan.form = full_step_form(robot, n, W, prm.use_pose != 0, prm.use_diff != 0, /*var_coupling=*/prm.diff_mode != 0, t_pcr_lds);
+    prm.fold = plan.form != FullStepForm::Pcr;  // (the parallel-in-time kernel assembles the terms itself: FullK::fold)
+    // full_solve_wave_kernel: up to 8 joints, no pose block, and neither the parallel-in-time nor the row-per-lane form -- which is
+    // CPPF_TUNE_FULL_ROWS = 0 beyond the parallel-in-time sizes, and also fewer than 3 joints or more than 2^19 waypoints, where the
+    // row-per-lane form does not exist.
+    if (pin != 0 && S >= 1 && plan.form == FullStepForm::Wave)
+        return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: the one-wavefront-per-trajectory elimination (what a step resolves to under "
+                                          "CPPF_TUNE_FULL_ROWS = 0, with fewer than 3 joints or beyond 2^19 waypoints) takes no "
+                                          "pinned end waypoint");
+    if (gated && plan.form != FullStepForm::Pcr && plan.form != FullStepForm::Rows)
+        return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: the device-side optimiser loop gates the parallel-in-time and the row-per-lane "
+                                          "elimination only (no pose block, no individually weighted differencing rows, CPPF_TUNE_FULL_ROWS on)");
+    // Local -- six pose rows against seven or eight joints and nothing else on the diagonal but lambda: the blocks in fp64, solved
+    // by the lane that builds them (full_local_solve), which writes x_out.  The unconstrained build at every size: the fp64 block
+    // is 2 x d(d+3)/2 registers on top of the rows'.
+    // A scene -- outside Local, too, ONE instantiation per robot, the unconstrained build: a planner steps S <= 8 trajectories, far
+    // below the row count at which the occupancy-bound build of the handle form pays.  (A handle specialised at run time takes the
+    // generic form, like every coupled step: for_robot.)
+    plan.blocks = scene ? FullBlocks::Scene : n >= 131072 && plan.form != FullStepForm::Local ? FullBlocks::Occ : FullBlocks::Plain;
+    // the parallel-in-time sub-forms: the state in LDS (W <= 256: 256 x ((d(d+1)/2 + d + d^2) | 1) floats), on 256 lanes or split over
+    // 512 (see kPcrSplitMaxD; CPPF_TUNE_PCR_LDS = 3 forces the split form), else in the workspace, on 256 or 512 lanes
+    plan.pcr_in_lds = W <= 256 && t_pcr_lds != 0;
+    plan.pcr_split = plan.pcr_in_lds && t_pcr_lds != 1 && (d <= kPcrSplitMaxD || t_pcr_lds == 3);
+    plan.pcr_block = plan.pcr_split || W > 256 ? 512 : 256;
+    plan.pcr_lds = plan.pcr_in_lds ? 256 * (size_t)((d * (d + 1) / 2 + d + d * d) | 1) * sizeof(float) : 0;
+    // row-per-lane kernels: 8 trajectories per one-wavefront workgroup and two workgroups (the two ends of the path) per 8
+    // trajectories; the LDS reservation caps the workgroups per compute unit at ceil(#workgroups / 256) (160 KB per compute
+    // unit), which spreads a small launch over distinct compute units
+    const int rows_tpw = d <= 8 ? 8 : 4;  // trajectories per wavefront: 8 or 16 lanes each
+    plan.rows_wgs = 2u * (unsigned)((S + rows_tpw - 1) / rows_tpw);
+    const unsigned rows_per_cu = (plan.rows_wgs + 255) / 256;
+    plan.rows_lds = rows_per_cu == 1 ? 96 * 1024 : rows_per_cu == 2 ? 64 * 1024 : rows_per_cu == 3 ? 48 * 1024 : 0;
+    plan.lane_grid = (unsigned)((S + 63) / 64);
+    return CPPF_OK;
+}
+
+// The launches of a planned coupled step.  With a gate (the optimiser loop on the device) only the trajectories it opens are stepped;
+// `scene` is the one the plan was made with (the environment rows come from its cuboids, not the handle's).  The pointers are the
+// last thing checked, still before the device is selected.
+int run_full_step(const cppf_robot* robot, const FullStepPlan& plan, const float* x_in, const float* target, const float* virtual_configs,
+                  float* work_blocks, float* work_G, float* work_y, float* x_out, void* stream, const StepGateK gate,
+                  const SceneStepK* scene = nullptr) {
+    const FullK& prm = plan.prm;
+    const int S = prm.S;
+    CPPF_REQUIRE(x_out != x_in, "x_out must not alias x_in (the back substitution reads x_in)");
+    CPPF_REQUIRE(S == 0 || (x_in && target && work_blocks && work_G && work_y && x_out), "NULL pointer");
+    CPPF_ENTER(robot);
+    if (S == 0) return CPPF_OK;
+    float* const w2next = work_G + plan.w2next;
     hipStream_t st = (hipStream_t)stream;
+    const bool local = plan.form == FullStepForm::Local;
     const int rc = for_robot(robot, [&](auto tag) {
         using RB = typename decltype(tag)::type;
-        // Local -- six pose rows against seven or eight joints and nothing else on the diagonal but lambda: the blocks in fp64, solved
-        // by the lane that builds them (full_local_solve), which writes x_out.  The unconstrained build at every size: the fp64 block
-        // is 2 x d(d+3)/2 registers on top of the rows'.
-        const bool local = form == FullStepForm::Local;
         // one argument list for the five instantiations in use; they differ in the tail: the scene's cuboids or the gate
         const auto blocks = [&](auto kernel, const auto& tail) {
-            return launch(kernel, dim3(grid_for(n)), dim3(kBlock), robot->lds_bytes, st, robot->chain, robot->coll, prm, x_in, target,
-                          virtual_configs, work_blocks, w2next, tail, local ? x_out : (float*)nullptr);
+            return launch(kernel, dim3(grid_for((size_t)S * prm.W)), dim3(kBlock), robot->lds_bytes, st, robot->chain, robot->coll, prm, x_in,
+                          target, virtual_configs, work_blocks, w2next, tail, local ? x_out : (float*)nullptr);
         };
-        if (scene != nullptr) {
-            // Outside Local, too, ONE instantiation per robot, the unconstrained build: a planner steps S <= 8 trajectories, far below
-            // the row count at which the occupancy-bound build of the handle form pays.  (A handle specialised at run time takes the
-            // generic form, like every coupled step: for_robot.)
+        if (plan.blocks == FullBlocks::Scene) {
             SceneStepK sc = *scene;
             sc.tile_cull2 = tile_cull_threshold(robot, 0.f);
             // (dynamic LDS as for the handle form beside it: chain12's 13 capsules are 78 KB in both)
             return blocks(local ? full_blocks_kernel<RB, 0, true, true> : full_blocks_kernel<RB, 0, true>, sc);
         }
-        return blocks(local             ? full_blocks_kernel<RB, 0, false, true>
-                      : n >= 131072 ? full_blocks_kernel<RB, full_blocks_occ<RB>()>
-                                    : full_blocks_kernel<RB>,
+        return blocks(local                             ? full_blocks_kernel<RB, 0, false, true>
+                      : plan.blocks == FullBlocks::Occ ? full_blocks_kernel<RB, full_blocks_occ<RB>()>
+                                                        : full_blocks_kernel<RB>,
                       gate);
     });
     if (rc) return rc;
-    if (form == FullStepForm::Local) return check_launch();
-    // row-per-lane kernels: 8 trajectories per one-wavefront workgroup and two workgroups (the two ends of the path) per 8
-    // trajectories; the LDS reservation caps the workgroups per compute unit at ceil(#workgroups / 256) (160 KB per compute
-    // unit), which spreads a small launch over distinct compute units
-    const int rows_tpw = robot->desc.ndof <= 8 ? 8 : 4;  // trajectories per wavefront: 8 or 16 lanes each
-    const unsigned rows_wgs = 2u * (unsigned)((S + rows_tpw - 1) / rows_tpw);
-    const unsigned rows_per_cu = (rows_wgs + 255) / 256;
-    const size_t rows_lds = rows_per_cu == 1 ? 96 * 1024 : rows_per_cu == 2 ? 64 * 1024 : rows_per_cu == 3 ? 48 * 1024 : 0;
     const uint32_t pris_mask = robot->chain.pris_mask;
-    const dim3 lane_grid((unsigned)((S + 63) / 64));
     return for_ndof(robot->desc.ndof, [&](auto dof) {
         constexpr int D = decltype(dof)::D;
-        switch (form) {
+        switch (plan.form) {
             case FullStepForm::LaneVar:
-                hipLaunchKernelGGL((full_solve_kernel<D, true>), lane_grid, dim3(64), 0, st, prm, pris_mask, x_in, work_blocks, work_G,
-                                   work_y, x_out, w2next);
+                hipLaunchKernelGGL((full_solve_kernel<D, true>), dim3(plan.lane_grid), dim3(64), 0, st, prm, pris_mask, x_in, work_blocks,
+                                   work_G, work_y, x_out, w2next);
                 break;
             case FullStepForm::Pcr:
                 // Up to ~128k rows (the planner's cadence is one trajectory): parallel cyclic reduction, one workgroup per
                 // trajectory, one lane per waypoint; beyond that its O(T log T) work and traffic lose against the
                 // waypoint-after-waypoint kernels.
                 if constexpr (D <= 8) {  // (full_step_form: the parallel-in-time form exists for 3 .. 8 joints)
-                    // the four forms: the state in LDS (W <= 256: 256 x ((d(d+1)/2 + d + d^2) | 1) floats), on 256 lanes or split over 512
-                    // (see kPcrSplitMaxD; CPPF_TUNE_PCR_LDS = 3 forces the split form), else in the workspace, on 256 or 512 lanes
-                    constexpr size_t kState = 256 * (size_t)((D * (D + 1) / 2 + D + D * D) | 1) * sizeof(float);
-                    const bool in_lds = W <= 256 && g_pcr_lds;
-                    const bool split = in_lds && g_pcr_split && (D <= kPcrSplitMaxD || t_pcr_lds == 3);
-                    const auto kernel = split      ? full_solve_pcr_kernel<D, 512, true, true>
-                                        : in_lds   ? full_solve_pcr_kernel<D, 256, true>
-                                        : W <= 256 ? full_solve_pcr_kernel<D, 256>
-                                                   : full_solve_pcr_kernel<D, 512>;
-                    if (int rc2 = launch(kernel, dim3((unsigned)S), dim3(split || W > 256 ? 512 : 256), in_lds ? kState : 0, st, robot->chain, prm,
-                                         x_in, virtual_configs, work_blocks, work_G, x_out, gate))
+                    const auto kernel = plan.pcr_split          ? full_solve_pcr_kernel<D, 512, true, true>
+                                        : plan.pcr_in_lds       ? full_solve_pcr_kernel<D, 256, true>
+                                        : plan.pcr_block == 256 ? full_solve_pcr_kernel<D, 256>
+                                                                : full_solve_pcr_kernel<D, 512>;
+                    if (int rc2 = launch(kernel, dim3((unsigned)S), dim3(plan.pcr_block), plan.pcr_lds, st, robot->chain, prm, x_in,
+                                         virtual_configs, work_blocks, work_G, x_out, gate))
                         return rc2;
                 }
                 break;
             case FullStepForm::Rows:  // (every ndof; sixteen lanes per trajectory at 9 .. 12 joints, see rows_tpw)
-                if (int rc2 = launch(full_rows_eliminate_kernel<D>, dim3(rows_wgs), dim3(64), rows_lds, st, prm, pris_mask, work_blocks, work_G,
-                                     work_y, gate))
+                if (int rc2 = launch(full_rows_eliminate_kernel<D>, dim3(plan.rows_wgs), dim3(64), plan.rows_lds, st, prm, pris_mask,
+                                     work_blocks, work_G, work_y, gate))
                     return rc2;
-                if (int rc2 = launch(full_rows_substitute_kernel<D>, dim3(rows_wgs), dim3(64), rows_lds, st, prm, pris_mask, x_in, work_blocks,
-                                     work_G, work_y, x_out, gate))
+                if (int rc2 = launch(full_rows_substitute_kernel<D>, dim3(plan.rows_wgs), dim3(64), plan.rows_lds, st, prm, pris_mask, x_in,
+                                     work_blocks, work_G, work_y, x_out, gate))
                     return rc2;
                 break;
             case FullStepForm::Wave:  // one trajectory per wavefront (8 x 8 lane tile), up to 8 joints
@@ -1174,12 +1189,12 @@ int lm_full_step_gated(const cppf_robot* robot, const float* x_in, const float* 
                     hipLaunchKernelGGL((full_solve_wave_kernel<D>), dim3((unsigned)S), dim3(64), 0, st, prm, pris_mask, x_in, work_blocks,
                                        work_G, work_y, x_out);
                 break;
-            case FullStepForm::Local: break;  // (returned above)
+            case FullStepForm::Local: break;  // (full_blocks_kernel solved it)
             case FullStepForm::Lane:
                 // With the pose block and differencing rows the d x d blocks are J^T J + a small diagonal (rank 6 of 7, cond ~1e7): this kernel's Cholesky
                 // with floored pivots copes with that better than the explicit Gauss-Jordan inverse, so it keeps that case.
-                hipLaunchKernelGGL((full_solve_kernel<D>), lane_grid, dim3(64), 0, st, prm, pris_mask, x_in, work_blocks, work_G, work_y,
-                                   x_out, nullptr);
+                hipLaunchKernelGGL((full_solve_kernel<D>), dim3(plan.lane_grid), dim3(64), 0, st, prm, pris_mask, x_in, work_blocks, work_G,
+                                   work_y, x_out, nullptr);
                 break;
         }
         return check_launch();
@@ -1539,8 +1554,9 @@ int cppf_plan_metrics(const cppf_robot* robot, const float* x, const float* targ
 int cppf_lm_full_step_pinned(const cppf_robot* robot, const float* x_in, const float* target, const float* virtual_configs, int S,
                              int W, const cppf_full_params* params, int pin_mask, float* work_blocks, float* work_G, float* work_y,
                              float* x_out, void* stream) {
-    return lm_full_step_gated(robot, x_in, target, virtual_configs, S, W, params, pin_mask, work_blocks, work_G, work_y, x_out,
-                              stream, StepGateK{nullptr, 0, 0u});
+    FullStepPlan plan;
+    if (int rc = plan_full_step(robot, S, W, params, pin_mask, false, nullptr, plan)) return rc;
+    return run_full_step(robot, plan, x_in, target, virtual_configs, work_blocks, work_G, work_y, x_out, stream, StepGateK{nullptr, 0, 0u});
 }
 
 int cppf_lm_full_step(const cppf_robot* robot, const float* x_in, const float* target, const float* virtual_configs, int S,
@@ -1553,18 +1569,11 @@ int cppf_lm_full_step(const cppf_robot* robot, const float* x_in, const float* t
 int cppf_lm_full_step_scene(const cppf_robot* robot, const float* x_in, const float* target, const float* virtual_configs, int S,
                             int W, const cppf_full_params* params, int pin_mask, const float* box_lo, const float* box_hi,
                             int n_obs, float* work_blocks, float* work_G, float* work_y, float* x_out, void* stream) {
-    // every argument is checked before the device is selected (CPPF_ENTER), so that the checks hold for a host-only handle too
-    CPPF_ROBOT_ALIVE(robot);
-    CPPF_REQUIRE(params, "params is NULL");
-    CPPF_REQUIRE(pin_mask >= 0 && pin_mask <= (CPPF_PIN_FIRST | CPPF_PIN_LAST),
-                 "pin_mask must be a combination of CPPF_PIN_FIRST and CPPF_PIN_LAST");
-    CPPF_REQUIRE(n_obs >= 0 && n_obs <= CPPF_MAX_SCENE_OBSTACLES, "n_obs out of range (0 .. CPPF_MAX_SCENE_OBSTACLES)");
-    CPPF_REQUIRE(n_obs == 0 || (box_lo && box_hi), "box_lo / box_hi is NULL");
-    CPPF_REQUIRE(S >= 0 && W >= 1, "S < 0 or W < 1");
-    CPPF_REQUIRE(S == 0 || (x_in && target && work_blocks && work_G && work_y && x_out), "NULL pointer");
-    const SceneStepK scene{box_lo, box_hi, n_obs, 0.f};  // (the tile threshold: lm_full_step_gated, from the handle's radii)
-    return lm_full_step_gated(robot, x_in, target, virtual_configs, S, W, params, pin_mask, work_blocks, work_G, work_y, x_out,
-                              stream, StepGateK{nullptr, 0, 0u}, &scene);
+    const SceneStepK scene{box_lo, box_hi, n_obs, 0.f};  // (the tile threshold: run_full_step, from the handle's radii)
+    FullStepPlan plan;
+    if (int rc = plan_full_step(robot, S, W, params, pin_mask, false, &scene, plan)) return rc;
+    return run_full_step(robot, plan, x_in, target, virtual_configs, work_blocks, work_G, work_y, x_out, stream, StepGateK{nullptr, 0, 0u},
+                         &scene);
 }
 
 }  // extern "C"
@@ -1631,10 +1640,6 @@ int cppf_lm_optimize_enqueue_pinned(const cppf_robot* robot, float* x, const flo
     CPPF_REQUIRE(params->per_trajectory == 0 || params->per_trajectory == 1, "per_trajectory must be 0 or 1");
     CPPF_REQUIRE(params->trace_capacity >= 0, "trace_capacity must be >= 0");
     CPPF_REQUIRE(params->convergence_threshold >= 0.0, "convergence_threshold must be >= 0");
-    CPPF_REQUIRE(params->diff.lm_lambda > 0.f, "diff.lm_lambda must be > 0");
-    if (int rc = full_step_pin_check(robot, S, W, &params->diff, pin_mask)) return rc;
-    CPPF_REQUIRE(!params->diff.use_virtual_configs || (params->diff.n_virtual_configs > 0 && 2 * params->diff.n_virtual_configs < W),
-                 "2 * n_virtual_configs must be < number of waypoints (optimization_utils.py:449-451)");
     cppf_lm_params lp = {};
     lp.lm_lambda = params->pose_lm_lambda;
     lp.alpha_position = params->pose_alpha_position;
@@ -1656,8 +1661,10 @@ int cppf_lm_optimize_enqueue_pinned(const cppf_robot* robot, float* x, const flo
         return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: the device-side optimiser loop needs the quad-shape pose step (ndof >= 6, S*W within its row limit)");
     if (params->diff.use_pose || params->diff.differencing_mode != 0)
         return fail(CPPF_ERR_UNSUPPORTED, "cppflow_hip: the device-side optimiser loop takes a coupled step without pose block and without weighted differencing rows");
-    // ... and so is the elimination of the coupled step: decided here, before the pose step's launch writes x_new
-    if (!full_step_gateable(full_step_form(robot, n, W, false, true, false))) return fail(CPPF_ERR_UNSUPPORTED, kGatedFormRefusal);
+    // ... and so is the coupled step, whole: checked and decided here, once for every iteration, before the pose step's launch
+    // writes x_new
+    FullStepPlan diff_step;
+    if (int rc = plan_full_step(robot, S, W, &params->diff, pin_mask, true, nullptr, diff_step)) return rc;
     if (n_iterations == 0) return CPPF_OK;
     CPPF_ENTER(robot);
     prm.n = (int)n;
@@ -1680,8 +1687,7 @@ int cppf_lm_optimize_enqueue_pinned(const cppf_robot* robot, float* x, const flo
     const size_t total = n * (size_t)d;
     for (int it = 0; it < n_iterations; ++it) {
         if (int rc = launch_quad(robot, false, n, st, prm, x, target, oq, g_pose)) return rc;
-        if (int rc = lm_full_step_gated(robot, x, target, x, S, W, &params->diff, pin_mask, ws + L.blocks, ws + L.G, ws + L.y, x_new, stream, g_diff))
-            return rc;
+        if (int rc = run_full_step(robot, diff_step, x, target, x, ws + L.blocks, ws + L.G, ws + L.y, x_new, stream, g_diff)) return rc;
         hipLaunchKernelGGL(optloop_clamp_kernel, dim3(grid_for(total)), dim3(kBlock), 0, st, robot->chain, total, W, pin_mask, x_new, x, g_live);
         if (want_masks)
             if (int rc = collision_masks_gated(robot, x, S, W, self_m, env_m, nullptr, nullptr, nullptr, nullptr, stream, g_live)) return rc;

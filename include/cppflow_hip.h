@@ -614,7 +614,10 @@ typedef struct cppf_full_params {
  * target [W,7]; virtual_configs [S*W, d] or NULL (= x_in, which is what the loop sets at optimization.py:253).
  * Obstacles are those of cppf_set_obstacles.  The normal matrix is never formed densely: it is block-tridiagonal and is
  * eliminated per trajectory.  Workspace (device): work_blocks [S*W * (d(d+1)/2 + d)], work_G [S*W * d*d],
- * work_y [S*W * d] floats.  x_out [S*W, d] must not alias x_in. */
+ * work_y [S*W * d] floats.  x_out [S*W, d] must not alias x_in.  CPPF_ERR_INVALID, before a device is selected or anything
+ * launched: a NULL / destroyed handle, NULL params, S < 0, W < 1 or S*W beyond 2^31-1, lm_lambda <= 0, 2 * n_virtual_configs >= W,
+ * a differencing_mode outside 0 .. 2, a scale-down in use outside [0, 1), x_out == x_in, and (S > 0) a NULL pointer other than
+ * virtual_configs. */
 int cppf_lm_full_step(const cppf_robot* robot, const float* x_in, const float* target, const float* virtual_configs, int S,
                       int W, const cppf_full_params* params, float* work_blocks, float* work_G, float* work_y,
                       float* x_out, void* stream);
@@ -629,7 +632,8 @@ int cppf_lm_full_step(const cppf_robot* robot, const float* x_in, const float* t
  * with both ends pinned) x_out == x_in.  Same workspaces as cppf_lm_full_step.  Served by the parallel-in-time, the row-per-lane
  * and the one-lane elimination; CPPF_ERR_UNSUPPORTED -- before anything is launched or a device selected -- together with the
  * "satisfied" row options (differencing_mode != 0, pose_do_scale_down_satisfied) and for the one-wavefront-per-trajectory
- * cross-check kernel (CPPF_TUNE_FULL_ROWS = 0 beyond the parallel-in-time form's sizes). */
+ * cross-check kernel (CPPF_TUNE_FULL_ROWS = 0 beyond the parallel-in-time form's sizes).  CPPF_ERR_INVALID, before a device is
+ * selected: everything cppf_lm_full_step refuses, and a pin_mask outside CPPF_PIN_FIRST | CPPF_PIN_LAST. */
 #define CPPF_PIN_FIRST 1
 #define CPPF_PIN_LAST 2
 int cppf_lm_full_step_pinned(const cppf_robot* robot, const float* x_in, const float* target, const float* virtual_configs, int S,
@@ -651,7 +655,7 @@ int cppf_lm_full_step_pinned(const cppf_robot* robot, const float* x_in, const f
  * params->use_env_collisions = 0 (the scene is then not read).  A handle specialised at run time (cppf_robot_specialize) is served
  * by the generic kernels, as for every coupled step: same bits.  CPPF_ERR_INVALID, before a device is selected: a NULL / destroyed
  * handle, NULL pointers (box_lo / box_hi may be NULL only with n_obs = 0), n_obs out of range, a pin_mask outside
- * CPPF_PIN_FIRST | CPPF_PIN_LAST.  The device-side optimiser loop (cppf_lm_optimize_enqueue) does not take a scene. */
+ * CPPF_PIN_FIRST | CPPF_PIN_LAST, and every value cppf_lm_full_step refuses.  The device-side optimiser loop (cppf_lm_optimize_enqueue) does not take a scene. */
 int cppf_lm_full_step_scene(const cppf_robot* robot, const float* x_in, const float* target, const float* virtual_configs, int S,
                             int W, const cppf_full_params* params, int pin_mask, const float* box_lo, const float* box_hi,
                             int n_obs, float* work_blocks, float* work_G, float* work_y, float* x_out, void* stream);

@@ -84,6 +84,16 @@ def _params(**kw):
     return P
 
 
+# what a coupled step refuses by the values in its cppf_full_params, whichever entry point takes them (this file, test_pin_abi.py,
+# test_scene_step_abi.py): (fields, word in the message)
+FULL_STEP_VALUE_CASES = [
+    (dict(lm_lambda=0.0), "lm_lambda"),
+    (dict(differencing_mode=3), "differencing_mode"),
+    (dict(differencing_mode=2, differencing_scale_down=1.5), "scale-down"),
+    (dict(pose_do_scale_down_satisfied=1, pose_scale_down=2.0), "scale-down"),
+]
+
+
 def test_null_robot_is_refused_with_a_message(lib):
     from cppflow_amd import _hip
 
@@ -124,6 +134,8 @@ def test_bad_arguments_are_refused_before_any_launch_and_sizes_are_as_documented
             (dict(pose_alpha_position=0.0), dict(), "alpha_position"),
             (dict(diff_lm_lambda=0.0), dict(), "lm_lambda"),
             (dict(), dict(W=8), "n_virtual_configs"),  # 2 * 4 virtual configs need more than 8 waypoints
+            # (without a pose block the step never reads the factor; refused before the pose step's launch all the same)
+            (dict(diff_pose_do_scale_down_satisfied=1, diff_pose_scale_down=2.0), dict(), "scale-down"),
         ]
         for pkw, akw, word in cases:
             a = dict(x=buf, target=buf, S=1, W=16, workspace=buf, control=buf, n=1)

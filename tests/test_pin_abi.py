@@ -84,6 +84,25 @@ def test_the_satisfied_row_options_are_refused_with_a_pin(lib, handle, pin):
     assert _enqueue(lib, handle, _params(diff_differencing_mode=1), pin) == _hip.CPPF_ERR_UNSUPPORTED
 
 
+@pytest.mark.parametrize("pin", [1, 2, 3])
+def test_an_invalid_value_is_invalid_with_a_pin_too(lib, handle, pin):
+    """the value checks come before what a pin does not combine with: a "satisfied" option out of range is CPPF_ERR_INVALID, not
+    CPPF_ERR_UNSUPPORTED -- on the step and, for what the device loop's own refusals let through, on the loop"""
+    from cppflow_amd import _hip
+    from tests.test_optloop_abi import FULL_STEP_VALUE_CASES
+
+    for fields, word in FULL_STEP_VALUE_CASES:
+        P = _params(**{"diff_" + k: v for k, v in fields.items()})
+        assert _full_step(lib, handle, P, pin) == _hip.CPPF_ERR_INVALID, (fields, lib.cppf_last_error().decode())
+        assert word in lib.cppf_last_error().decode(), (fields, lib.cppf_last_error().decode())
+        if "differencing_mode" not in fields:  # (the loop refuses weighted differencing rows as unsupported, whatever their values)
+            assert _enqueue(lib, handle, P, pin) == _hip.CPPF_ERR_INVALID, (fields, lib.cppf_last_error().decode())
+            assert word in lib.cppf_last_error().decode(), (fields, lib.cppf_last_error().decode())
+    assert _full_step(lib, handle, _params(), pin, W=8) == _hip.CPPF_ERR_INVALID and "n_virtual_configs" in lib.cppf_last_error().decode()
+    # with everything in order the pinned step passes every check and ends where the device would be selected
+    assert _full_step(lib, handle, _params(), pin) == _hip.CPPF_ERR_HIP, lib.cppf_last_error().decode()
+
+
 def test_the_one_wavefront_cross_check_kernel_refuses_a_pin(lib, handle):
     """full_rows = 0 beyond the parallel-in-time form's sizes resolves to full_solve_wave_kernel, which takes no pin"""
     from cppflow_amd import _hip

@@ -35,13 +35,19 @@ def handle(lib):
 BUF = ctypes.c_void_p(0x1000)  # never dereferenced: every call below is refused before any launch
 
 
-def _call(lib, h, **kw):
+FULL_STEP_ENTRY_POINTS = ("cppf_lm_full_step", "cppf_lm_full_step_pinned", "cppf_lm_full_step_scene")
+
+
+def _call(lib, h, entry="cppf_lm_full_step_scene", **kw):
+    """one coupled step through `entry` with everything in order but `kw` (the plain step takes no pin, only the scene step cuboids)"""
     P = _params()
     a = dict(x_in=BUF, target=BUF, virtual_configs=None, S=3, W=24, params=ctypes.byref(P.diff), pin=0, box_lo=BUF, box_hi=BUF, n_obs=9,
              blocks=BUF, G=BUF, y=BUF, x_out=ctypes.c_void_p(0x2000))  # fmt: skip
     a.update(kw)
-    return lib.cppf_lm_full_step_scene(h, a["x_in"], a["target"], a["virtual_configs"], a["S"], a["W"], a["params"], a["pin"], a["box_lo"],
-                                       a["box_hi"], a["n_obs"], a["blocks"], a["G"], a["y"], a["x_out"], None)  # fmt: skip
+    head = [h, a["x_in"], a["target"], a["virtual_configs"], a["S"], a["W"], a["params"]]
+    mid = {"cppf_lm_full_step": [], "cppf_lm_full_step_pinned": [a["pin"]],
+           "cppf_lm_full_step_scene": [a["pin"], a["box_lo"], a["box_hi"], a["n_obs"]]}[entry]  # fmt: skip
+    return getattr(lib, entry)(*head, *mid, a["blocks"], a["G"], a["y"], a["x_out"], None)
 
 
 def test_the_entry_point_is_declared_bound_and_exported(lib):
@@ -83,6 +89,25 @@ def test_bad_arguments_are_refused_before_the_device_is_selected(lib, handle):
     # argument check (it ends at selecting the device of a host-only handle, or returns at once: nothing is launched either way)
     assert _call(lib, handle, box_lo=None, box_hi=None, n_obs=0, S=0) != _hip.CPPF_ERR_INVALID
     assert _call(lib, handle, box_lo=None, box_hi=None, n_obs=1, S=0) == _hip.CPPF_ERR_INVALID
+
+
+@pytest.mark.parametrize("entry", FULL_STEP_ENTRY_POINTS)
+def test_every_entry_point_refuses_what_the_step_refuses_before_the_device_is_selected(lib, handle, entry):
+    """the step's one plan checks for all three: each fault alone is CPPF_ERR_INVALID on a handle whose device cannot be selected"""
+    from cppflow_amd import _hip
+    from tests.test_optloop_abi import FULL_STEP_VALUE_CASES
+
+    cases = [(dict(**{name: None}), "NULL") for name in ("x_in", "target", "blocks", "G", "y", "x_out")]
+    cases += [(dict(x_out=BUF), "alias"), (dict(W=8), "n_virtual_configs")]  # 2 * 4 virtual configs need more than 8 waypoints
+    for fields, word in FULL_STEP_VALUE_CASES:
+        P = _params(**{"diff_" + k: v for k, v in fields.items()})
+        cases.append((dict(params=ctypes.byref(P.diff)), word))
+    for kw, word in cases:
+        assert _call(lib, handle, entry, **kw) == _hip.CPPF_ERR_INVALID, (kw, lib.cppf_last_error().decode())
+        assert word in lib.cppf_last_error().decode(), (kw, lib.cppf_last_error().decode())
+    # with everything in order the call passes every check and ends where the device would be selected: nothing was launched
+    assert _call(lib, handle, entry) == _hip.CPPF_ERR_HIP, lib.cppf_last_error().decode()
+    assert "device" in lib.cppf_last_error().decode()
 
 
 def test_the_pinned_steps_unsupported_cases_are_kept(lib, handle):
